@@ -3,7 +3,7 @@
 synthetic 1920x1080 pairs, HessianAffine + RootSIFT, one identity view per image
 (BASELINE.json configs[1]).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step = one batch of --pairs-per-step (default 256) image pairs through the whole hot path, SURVEY.md 8d's boundary:
 two decoded 8-bit grey images in (pinned) host memory -> upload -> detect, describe, match, duplicate filter, LO-RANSAC ->
@@ -25,6 +25,9 @@ Rank 0 prints one JSON line.  Besides the contract fields it carries
                    patches and the measurement-region extraction, regions / s of SIFT (isolated leg, HIP-event scopes per stage)
   harder_verification - the same pipeline on pairs where only 40 % of image 2 follows the homography (tens of RANSAC samples per
                    pair instead of 3): a short driver-timed leg behind the timed steps
+
+--dump-outputs DIR writes what the last timed step returned for each of its pairs (H, the counts, the verified matches) as
+DIR/<name>.npy.  The inputs depend on the arguments only (seeded synthetic pairs), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -52,6 +55,35 @@ def pmc_blur_traffic():
         except OSError:
             pass
     return None
+
+
+DUMP_MAX_MATCHES = 1 << 17          # rows fetched per pair for --dump-outputs (n_inliers is far below this)
+DUMP_MAX_BYTES = (64 << 20) - (1 << 16)     # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir, results, matches, pair_index):
+    """--dump-outputs: the per-pair results of one step as .npy files (float64).  matches.npy stacks the verified matches of the
+    step's pairs (x1, y1, x2, y2), match_offsets.npy says where each pair's rows begin.  Should the matches not fit in
+    DUMP_MAX_BYTES, a fixed, seeded sample of their rows is written and match_rows.npy names the rows kept."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"pair_index": np.asarray(pair_index, np.float64),
+              "H": np.array([list(r.H) for r in results], np.float64).reshape(-1, 3, 3)}
+    for f in ("n_detected", "n_described"):
+        arrays[f] = np.array([list(getattr(r, f)) for r in results], np.float64)
+    for f in ("n_tentatives", "n_unique", "n_inliers", "ransac_samples", "ransac_lo", "ransac_rejects"):
+        arrays[f] = np.array([getattr(r, f) for r in results], np.float64)
+    m = np.concatenate([np.asarray(x, np.float64).reshape(-1, 4) for x in matches]) if matches else np.zeros((0, 4))
+    arrays["match_offsets"] = np.concatenate([[0], np.cumsum([len(x) for x in matches])]).astype(np.float64)
+    room = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())
+    if m.nbytes > room:
+        keep = room // (4 * 8 + 8)      # a sampled row costs its four values and its index in match_rows
+        rows = np.sort(np.random.default_rng(0).choice(len(m), size=keep, replace=False))
+        arrays["match_rows"] = rows.astype(np.float64)
+        m = m[rows]
+    arrays["matches"] = m
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(img1, img2, seed):
@@ -443,7 +475,7 @@ def main():
                     help="where a pair lives when its step starts: 8-bit grey in pinned host memory (default: the boundary of the "
                          "reference's step loop), fp32 in pinned host memory, or fp32 resident in HBM")
     ap.add_argument("--no-match-leg", action="store_true", help="skip the configs[4]-sized match measurement (roofline_match)")
-    ap.add_argument("--no-harder-leg", action="store_true", help="skip the short leg on pairs with 40 % inliers (harder_verification)")
+    ap.add_argument("--no-harder-leg", action="store_true", help="skip the short leg on pairs with 40 %% inliers (harder_verification)")
     ap.add_argument("--scene", default="planar", choices=["planar", "two_planes"],
                     help="--config c5: one plane (SURVEY 8d's generator: every sample is H-degenerate) or two planes with parallax")
     ap.add_argument("--ladder", default="full", choices=["full", "hessian"],
@@ -459,7 +491,14 @@ def main():
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="BASELINE.json configs[]: c2 = the headline 1080p pair (default, what the driver runs); c3 = view-synthesis "
                          "ladder on a hard 1080p pair; c4 = 1-MP pairs (throughput); c5 = 4096x4096 pair with DEGENSAC F verification")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (per pair: H, the counts, the "
+                         "verified matches) as DIR/<name>.npy, float64 (headline configuration, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "c2":
+        ap.error("--dump-outputs is implemented for the headline configuration (--config c2) only")
     if args.config == "c3":
         return config_c3(args)
     if args.config != "c2":
@@ -538,8 +577,11 @@ def main():
     pkg.ransac_pin_seed(12345)
     pipe = None if args.serial else pkg.Pipeline(device, W, H, params, args.gpu_workers, args.verify_workers, args.pairs_per_batch)
 
-    def step(i):
-        res, _ = pkg.match_pair_dev(ctx, pairs_dev[i % len(pairs_dev)].data_ptr(), W, H, params)
+    def step(i, matches=None):
+        res, m = pkg.match_pair_dev(ctx, pairs_dev[i % len(pairs_dev)].data_ptr(), W, H, params,
+                                    max_matches=0 if matches is None else DUMP_MAX_MATCHES)
+        if matches is not None:
+            matches.append(m)
         return res
 
     def submit(i):
@@ -549,17 +591,26 @@ def main():
         else:
             pipe.submit_host(pinned[k].ptr.value, i, u8=(args.input == "host_u8"))
 
-    def run(n_steps):
-        """n_steps pairs through the hot path; returns the per-pair results in step order."""
+    def run(n_steps, keep_from=None, kept=None):
+        """n_steps pairs through the hot path; returns the per-pair results in step order.  With keep_from, the verified matches
+        of every pair from that one on are appended to kept (the same results, fetched with their match lists)."""
         if pipe is None:
-            return [step(i) for i in range(n_steps)]
+            return [step(i, kept if keep_from is not None and i >= keep_from else None) for i in range(n_steps)]
         out, pending = [], 0
+
+        def take():
+            if keep_from is not None and len(out) >= keep_from:
+                r, _, m = pipe.next_matches(DUMP_MAX_MATCHES)
+                kept.append(m)
+                out.append(r)
+            else:
+                out.append(pipe.next()[0])
         for i in range(n_steps):
             if pending >= pipe.capacity - 1:
-                out.append(pipe.next()[0]); pending -= 1
+                take(); pending -= 1
             submit(i); pending += 1
         while pending:
-            out.append(pipe.next()[0]); pending -= 1
+            take(); pending -= 1
         return out
 
     pps = max(1, args.pairs_per_step or 256)
@@ -576,7 +627,8 @@ def main():
     thr0 = thread_cpu_ns()
     t0 = time.perf_counter()
     replays0 = pipe.graph_replays() if pipe is not None else 0
-    results = run(args.steps * pps)
+    last_matches = []
+    results = run(args.steps * pps, keep_from=(args.steps - 1) * pps if args.dump_outputs else None, kept=last_matches)
     torch.cuda.synchronize()
     replays = (pipe.graph_replays() - replays0) if pipe is not None else 0
     cpu_s = time.process_time() - cpu0          # every thread of this rank: submit loop, GPU workers, verify workers, RANSAC task pool
@@ -592,6 +644,9 @@ def main():
         tot, cnt, top = by_name.get(nm, (0, 0, 0))
         by_name[nm] = (tot + v, cnt + (1 if v > 0 else 0), max(top, v))
     by_thread = sorted(by_name.items(), key=lambda kv: -kv[1][0])
+    if args.dump_outputs and rank == 0:
+        first = (args.steps - 1) * pps
+        dump_outputs(args.dump_outputs, results[first:], last_matches, [i % len(pairs_dev) for i in range(first, first + pps)])
     # instrumented leg: HIP events around every blur launch, on the streams the launches go to (the workers' streams), while the
     # pipeline runs as in the timed steps (eager launches: the timers switch the graph replay off)
     timed = pipe if pipe is not None else ctx

@@ -158,6 +158,16 @@ def loransac_f(u6, laf, err_threshold=4.0, conf=0.99, max_samples=1000000, laf_c
     return mask, F, len(good), stats
 
 
+def hmatrix_filter_case(err_type, n=4000):
+    """(u6, H) of the HMatrixFiltering test for error type err_type: points on both sides of the 4 px threshold."""
+    rng = np.random.default_rng(17 + err_type)
+    H = np.array([[0.9, 0.12, 30.0], [-0.08, 1.05, -12.0], [1e-4, -6e-5, 1.0]])
+    x1 = np.c_[rng.uniform(0, 800, n), rng.uniform(0, 600, n), np.ones(n)]
+    p = x1 @ H.T
+    x2 = p[:, :2] / p[:, 2:3] + rng.normal(0, 1.0, (n, 2)) * rng.choice([0.3, 3.0, 30.0], (n, 1))
+    return np.ascontiguousarray(np.c_[x1[:, 0], x1[:, 1], np.ones(n), x2[:, 0], x2[:, 1], np.ones(n)]), H
+
+
 def hmatrix_filter(u6, H, err_threshold=4.0, err="sampson"):
     """HMatrixFiltering, matching.cpp:917-1012, on top of the reference's own HDs / HDsSymMax / HDsSym (oracle/_ref): the second
     image's point first, the column-major H, th = (float)(err_threshold^2).  H: row-major img1 -> img2."""

@@ -10,6 +10,10 @@
                  scenes, Sampson / symmetric error, with and without the symmetric check
   stages.npz     small inputs/outputs of the CPU oracle (regression pins for every stage; the
                  reference itself cannot produce them: it needs OpenCV)
+  hmatrix_filter.npz  the masks HMatrixFiltering computes with the REFERENCE's HDs / HDsSymMax / HDsSym on the inputs of
+                 tests/pipeline_oracle.py:hmatrix_filter_case (bit-packed)
+  ftools_ref.npz the REFERENCE's answers to the degensac calls of tests/test_cpu_ftools.py (recorded by that test itself
+                 under MODS_RECORD_GOLDEN=1), so that it runs where oracle/_ref is not built
   views.npz      view-synthesis geometry (sizes, H, warp matrices, sigmas; plain double + libm) for a table of
                  (w, h, tilt, phi, zoom), one synthesised view, and the per-view region list of the oracle
 """
@@ -134,7 +138,23 @@ def gen_views():
     np.savez_compressed(os.path.join(GOLD, "views.npz"), **out)
 
 
+def gen_hmatrix():
+    import pipeline_oracle as po
+    out = {}
+    for err_type, err in enumerate(("sampson", "symm_max", "symm_sum")):
+        u6, H = po.hmatrix_filter_case(err_type)
+        out["mask_" + err] = np.packbits(po.hmatrix_filter(u6, H, 4.0, err))
+    np.savez_compressed(os.path.join(GOLD, "hmatrix_filter.npz"), **out)
+
+
+def gen_ftools():
+    import subprocess
+    assert refdeg.available(), "oracle/_ref is needed"
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", os.path.join(ROOT, "tests", "test_cpu_ftools.py")],
+                          cwd=ROOT, env=dict(os.environ, MODS_RECORD_GOLDEN="1"))
+
+
 if __name__ == "__main__":
-    gen_ransac(); gen_rand(); gen_stages(); gen_ransac_f(); gen_views()
+    gen_ransac(); gen_rand(); gen_stages(); gen_ransac_f(); gen_views(); gen_hmatrix(); gen_ftools()
     for f in sorted(os.listdir(GOLD)):
         print(f, os.path.getsize(os.path.join(GOLD, f)))
