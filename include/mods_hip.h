@@ -350,7 +350,8 @@ typedef struct mods_ransac_params {
   double HLAFCoef;          /* 12 */
   int errorType;            /* 0 */
   int doSymmCheck;          /* 1 */
-  int useF;                 /* 0: homography (ver_type "Homog"), 1: epipolar geometry (DEGENSAC, ver_type "Epipolar") */
+  int useF;                 /* 0: homography (ver_type "Homog"), 1: epipolar geometry (DEGENSAC, ver_type "Epipolar"),
+                             * 2: epipolar geometry verified by ORSA (RANSAC_mode_t ORSA; mods_orsa_f) */
   /* ver_type 1 of the command line (GR_TRUTH, mods.cpp:290-320): verification against a known homography.
    * groundTruth 0: off; 1: HMatrixFiltering of the tentatives only; 2: doBothRANSACgroundTruth - LORANSACFiltering first, then
    * HMatrixFiltering of its inliers (the verified list), next to HMatrixFiltering of all tentatives for the log. */
@@ -379,6 +380,38 @@ int mods_loransac_h(const double *u6, const double *laf, int n, const mods_ransa
  * stats3 = {samples drawn, LO runs, plane consensus *Ih}. */
 int mods_loransac_f(const double *u6, const double *laf, int n, const mods_ransac_params *par, unsigned char *mask,
                     double *F_out, int *n_inliers, int *stats3);
+/* Replaces  int ORSAFiltering(TentativeCorrespListExt &in, TentativeCorrespListExt &out, double *F, const RANSACPars pars, int w,
+ *           int h)  (matching/matching.cpp:824-914) for useF = 2: orsa() (orsa.cpp:371-678) in mode 2 with t = 10000, seeded as
+ * srand(time(NULL)) (mods_ransac_pin_seed / MODS_RANSAC_SEED pin it), hypotheses scored on the GPU (csrc/orsa.hip).  w, h: the
+ * image size the reference passes (in the step loop ((w1 + w2) / 2, (h1 + h2) / 2), mods.cpp:347-350).  When log(nfa) < -2 the
+ * verified list is the first miniall + 1 tentatives in input order (the reference's own rule), then F_LAF_check (FDs for
+ * errorType 0, FDsSym otherwise; bound LAFCoef * err_threshold), cleared below 8; mask[i] = 1 for those.  F_out: the matrix as
+ * ransac_corresp.H receives it (the transpose of orsa()'s Fout), all -1 when not significant or n < 8.  log_nfa: orsa()'s
+ * return value (10000 when nothing was scored).  index_out (n entries or NULL): the sorted indices of the most meaningful subset,
+ * *n_index = miniall of them.  stats3 = {iterations, models scored, rewinds of a block after an optimisation trigger}. */
+int mods_orsa_f(const double *u6, const double *laf, int n, int w, int h, const mods_ransac_params *par, unsigned char *mask,
+                double *F_out, int *n_inliers, float *log_nfa, int *index_out, int *n_index, int *stats3);
+/* the same with the scoring back end chosen: on_device 0 = the host scalar path (matcherrorn + glibc qsort per model, no device
+ * needed; the device's oracle); batch = iterations solved and scored per block, wg_keys = key slots a workgroup packs models into
+ * (<= 0: MODS_ORSA_BATCH / MODS_ORSA_WG_KEYS or 512 / 1024).  Results do not depend on batch, wg_keys or MODS_RANSAC_THREADS. */
+int mods_orsa_f_ex(const double *u6, const double *laf, int n, int w, int h, const mods_ransac_params *par, unsigned char *mask,
+                   double *F_out, int *n_inliers, float *log_nfa, int *index_out, int *n_index, int *stats3, int on_device, int batch,
+                   int wg_keys);
+/* the calling thread's last mods_orsa_f[_ex] call: ms5 = {host 7-point solves, scoring (device round trips or host), scoring
+ * kernels (HIP events), replay, whole call}, *launches = scoring launches */
+int mods_orsa_last_profile(double *ms5, long *launches);
+/* self-test hooks of ORSA's host pieces (no device needed): epipolar() on the 7 points k7 of p1 / p2 (n x 2 floats each) -> F1, F2
+ * (row-major), z[3], returns the number of roots; the logcombi tables of n (n + 1 entries each); (float)log10((double)x) as glibc
+ * rounds it.  mods_test_orsa_score: the per-model results {nfa bits, first argmin, logalpha bits, NaN flag} of m models F (m x 9
+ * row-major) over the normalised points p1 / p2 of an image w x h, through the device kernel (on_device 1) or the host path. */
+int mods_test_orsa_epipolar(const float *p1, const float *p2, const int *k7, float *F1, float *F2, float *z);
+int mods_test_orsa_tables(int n, float *logcn, float *logc7);
+int mods_test_orsa_log10(const float *x, int n, float *out);
+int mods_test_orsa_score(const float *p1, const float *p2, int n, int w, int h, const float *F, int m, int on_device, int wg_keys,
+                         int *out4);
+/* the device's (float)log10((double)x) against glibc's for the float bit patterns [begin, begin + count): the number of
+ * mismatches (< 0: MODS_E_*), the first max_list of them in list */
+long long mods_test_orsa_log10_sweep(unsigned begin, unsigned count, unsigned *list, int max_list);
 /* The verification half of one step of the reference's loop (mods.cpp:278-368), in place on (tent, u6, laf):
  *   par->dup_before_ransac = 1 ([DuplicateFiltering] doBeforeRANSAC): DuplicateFiltering (mods.cpp:283), then LORANSACFiltering;
  *   par->dup_before_ransac = 0: LORANSACFiltering on every tentative, then DuplicateFiltering on the verified list
@@ -391,6 +424,11 @@ int mods_verify_tentatives(int device, const struct mods_pair_params *par, mods_
 /* the same with the three ground-truth counts of mods_ladder_result (gt3, may be NULL; zeros outside ground-truth mode) */
 int mods_verify_tentatives_ex(int device, const struct mods_pair_params *par, mods_tentative *tent, double *u6, double *laf, int n,
                               int *n_unique, int *n_verified, double *H_out, int *stats3, int *gt3, double *ms_dup, double *ms_ransac);
+/* the same with the image size (w, h) that useF = 2 (ORSA, mods_orsa_f) needs; the two calls above have none and return MODS_E_ARG
+ * for useF = 2.  mods_match_pair_dev and the pipeline pass their frame size. */
+int mods_verify_tentatives_wh(int device, const struct mods_pair_params *par, mods_tentative *tent, double *u6, double *laf, int n,
+                              int w, int h, int *n_unique, int *n_verified, double *H_out, int *stats3, int *gt3, double *ms_dup,
+                              double *ms_ransac);
 /* GPU used by the degensac entry points of the calling thread (default 0). */
 int mods_ransac_set_device(int device);
 /* The reference seeds with srand(time(NULL)) (exp_ranH.c:823).  seed >= 0 makes every call behave as if

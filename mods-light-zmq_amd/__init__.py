@@ -551,9 +551,85 @@ def loransac_f(u6, laf, params=None, seed_time=12345):
     return mask[:n].astype(bool), F, ninl.value, list(stats)
 
 
-def verify_tentatives(tent, u6, laf, params, device=0, seed_time=None):
+def orsa_f(u6, laf, w, h, params=None, seed_time=12345, on_device=True, batch=0, wg_keys=0):
+    """ORSAFiltering (useF = 2): ORSA a-contrario F verification, hypotheses scored on the GPU (on_device=False: the host
+    scoring path, no device needed).  Returns dict(mask, F as ransac_corresp.H holds it, n, log_nfa, index, stats)."""
+    params = params or RansacParams.default(useF=2)
+    if seed_time is not None:
+        ransac_pin_seed(seed_time)
+    u = np.ascontiguousarray(u6, np.float64)
+    if u.ndim != 2 or u.shape[1] != 6:
+        raise ValueError("u6 must be n x 6 (x1 y1 1 x2 y2 1)")
+    n = len(u)
+    lf = np.ascontiguousarray(laf, np.float64) if laf is not None else None
+    if lf is not None and lf.shape != (n, 14):
+        raise ValueError("laf must be n x 14")
+    mask = np.zeros(max(n, 1), np.uint8)
+    F = np.zeros(9, np.float64)
+    index = np.zeros(max(n, 1), np.int32)
+    ninl, nidx, nfa = C.c_int(), C.c_int(), C.c_float()
+    stats = (C.c_int * 3)()
+    _check(lib().mods_orsa_f_ex(u.ctypes.data_as(C.c_void_p), lf.ctypes.data_as(C.c_void_p) if lf is not None else None, n,
+                                int(w), int(h), C.byref(params), mask.ctypes.data_as(C.c_void_p), F.ctypes.data_as(C.c_void_p),
+                                C.byref(ninl), C.byref(nfa), index.ctypes.data_as(C.c_void_p), C.byref(nidx), stats,
+                                1 if on_device else 0, int(batch), int(wg_keys)))
+    return dict(mask=mask[:n].astype(bool), F=F, n=ninl.value, log_nfa=np.float32(nfa.value), index=index[:nidx.value].copy(),
+                stats=list(stats))
+
+
+def orsa_last_profile():
+    """ms of the calling thread's last orsa_f call: solve, score, kernel, replay, total; and the scoring launches."""
+    ms = (C.c_double * 5)()
+    launches = C.c_long()
+    _check(lib().mods_orsa_last_profile(ms, C.byref(launches)))
+    return dict(zip(("solve", "score", "kernel", "replay", "total"), list(ms)), launches=launches.value)
+
+
+def orsa_test_epipolar(p1, p2, k7):
+    p1 = np.ascontiguousarray(p1, np.float32); p2 = np.ascontiguousarray(p2, np.float32)
+    k = np.ascontiguousarray(k7, np.int32)
+    F1, F2, z = np.zeros(9, np.float32), np.zeros(9, np.float32), np.zeros(3, np.float32)
+    m = lib().mods_test_orsa_epipolar(_fp(p1), _fp(p2), k.ctypes.data_as(C.c_void_p), _fp(F1), _fp(F2), _fp(z))
+    return F1, F2, z, m
+
+
+def orsa_test_tables(n):
+    a, b = np.zeros(n + 1, np.float32), np.zeros(n + 1, np.float32)
+    _check(lib().mods_test_orsa_tables(int(n), _fp(a), _fp(b)))
+    return a, b
+
+
+def orsa_test_log10(x):
+    x = np.ascontiguousarray(x, np.float32)
+    out = np.zeros_like(x)
+    _check(lib().mods_test_orsa_log10(_fp(x), len(x), _fp(out)))
+    return out
+
+
+def orsa_test_score(p1, p2, w, h, F, on_device=True, wg_keys=0):
+    """per-model (nfa, first argmin, logalpha, NaN flag) of models F (m x 9) over normalised points"""
+    p1 = np.ascontiguousarray(p1, np.float32); p2 = np.ascontiguousarray(p2, np.float32)
+    F = np.ascontiguousarray(F, np.float32).reshape(-1, 9)
+    out = np.zeros((len(F), 4), np.int32)
+    _check(lib().mods_test_orsa_score(_fp(p1), _fp(p2), len(p1) // 2, int(w), int(h), _fp(F), len(F), 1 if on_device else 0,
+                                      int(wg_keys), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def orsa_log10_sweep(begin, count, max_list=1024):
+    L = lib()
+    L.mods_test_orsa_log10_sweep.restype = C.c_longlong
+    lst = np.zeros(max_list, np.uint32)
+    bad = L.mods_test_orsa_log10_sweep(C.c_uint(begin), C.c_uint(count), lst.ctypes.data_as(C.c_void_p), max_list)
+    if bad < 0:
+        _check(int(bad))
+    return int(bad), lst[:min(bad, max_list)].copy()
+
+
+def verify_tentatives(tent, u6, laf, params, device=0, seed_time=None, wh=None):
     """mods_verify_tentatives: duplicate filtering + LORANSACFiltering in the order [DuplicateFiltering] doBeforeRANSAC asks for
-    (mods.cpp:278-368).  Returns (verified tentatives, their u6, their laf, n_unique, H, stats)."""
+    (mods.cpp:278-368).  Returns (verified tentatives, their u6, their laf, n_unique, H, stats).  wh = (w, h): the image size,
+    required by useF = 2 (ORSA; mods_verify_tentatives_wh)."""
     if seed_time is not None:
         ransac_pin_seed(seed_time)
     tent = np.ascontiguousarray(tent).copy()
@@ -562,9 +638,14 @@ def verify_tentatives(tent, u6, laf, params, device=0, seed_time=None):
     nu, nv = C.c_int(), C.c_int()
     H = np.zeros(9, np.float64)
     stats = (C.c_int * 3)()
-    _check(lib().mods_verify_tentatives(device, C.byref(params), tent.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p),
-                                        lf.ctypes.data_as(C.c_void_p), len(tent), C.byref(nu), C.byref(nv),
-                                        H.ctypes.data_as(C.c_void_p), stats, None, None))
+    if wh is None:
+        _check(lib().mods_verify_tentatives(device, C.byref(params), tent.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p),
+                                            lf.ctypes.data_as(C.c_void_p), len(tent), C.byref(nu), C.byref(nv),
+                                            H.ctypes.data_as(C.c_void_p), stats, None, None))
+    else:
+        _check(lib().mods_verify_tentatives_wh(device, C.byref(params), tent.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p),
+                                               lf.ctypes.data_as(C.c_void_p), len(tent), int(wh[0]), int(wh[1]), C.byref(nu),
+                                               C.byref(nv), H.ctypes.data_as(C.c_void_p), stats, None, None, None))
     m = nv.value
     return tent[:m].copy(), u[:m].copy(), lf[:m].copy(), nu.value, H, list(stats)
 

@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "detmath.hpp"
 #include "ransac_host.hpp"
+#include "f_laf.hpp"
 #include <cstdarg>
 #include <algorithm>
 #include <cmath>
@@ -1028,25 +1029,7 @@ int mods_loransac_f(const double *u6, const double *laf, int n, const mods_ransa
   if (stats3) { stats3[0] = data_out[0]; stats3[1] = data_out[1]; stats3[2] = I_H; }
   std::vector<int> cur;
   for (int i = 0; i < n; i++) if (inl2[i]) cur.push_back(i);
-  const double affineFerror = par->LAFCoef * par->err_threshold;
-  if (affineFerror > 0 && laf) {
-    std::vector<int> good;
-    const double ks = 3.0;   // k_sigma, matching.cpp:171
-    for (int i : cur) {
-      const double *f = laf + (size_t)i * 14;
-      double u[18], err[3];
-      u[0] = f[0]; u[1] = f[1]; u[2] = 1.0;
-      u[3] = f[7]; u[4] = f[8]; u[5] = 1.0;
-      u[6] = u[0] + ks * f[3] * f[6]; u[7] = u[1] + ks * f[5] * f[6]; u[8] = 1.0;
-      u[9] = u[3] + ks * f[10] * f[13]; u[10] = u[4] + ks * f[12] * f[13]; u[11] = 1.0;
-      u[12] = u[0] + ks * f[2] * f[6]; u[13] = u[1] + ks * f[4] * f[6]; u[14] = 1.0;
-      u[15] = u[3] + ks * f[9] * f[13]; u[16] = u[4] + ks * f[11] * f[13]; u[17] = 1.0;
-      fds(u, Floran, err, 3);
-      const double sumErr = std::sqrt(err[0]) + std::sqrt(err[1]) + std::sqrt(err[2]);
-      if (!(sumErr > affineFerror)) good.push_back(i);
-    }
-    cur.swap(good);
-  }
+  f_laf_check(laf, Floran, par->LAFCoef * par->err_threshold, fds, cur);
   if ((int)cur.size() < MIN_POINTS) cur.clear();
   for (int i : cur) mask[i] = 1;
   *n_inliers = (int)cur.size();
@@ -1361,8 +1344,18 @@ int mods_verify_tentatives(int device, const mods_pair_params *par, mods_tentati
 
 int mods_verify_tentatives_ex(int device, const mods_pair_params *par, mods_tentative *tent, double *u6, double *laf, int n,
                               int *n_unique, int *n_verified, double *H_out, int *stats3, int *gt3, double *ms_dup, double *ms_ransac) {
+  return mods_verify_tentatives_wh(device, par, tent, u6, laf, n, 0, 0, n_unique, n_verified, H_out, stats3, gt3, ms_dup, ms_ransac);
+}
+
+int mods_verify_tentatives_wh(int device, const mods_pair_params *par, mods_tentative *tent, double *u6, double *laf, int n, int w,
+                              int h, int *n_unique, int *n_verified, double *H_out, int *stats3, int *gt3, double *ms_dup,
+                              double *ms_ransac) {
   if (gt3) gt3[0] = gt3[1] = gt3[2] = 0;
   if (!par || !n_unique || !n_verified || (n > 0 && (!tent || !u6 || !laf))) { set_error("verify_tentatives: null argument"); return MODS_E_ARG; }
+  if (par->ransac.useF == 2 && !par->ransac.groundTruth && (w <= 0 || h <= 0)) {
+    set_error("verify_tentatives: useF = 2 (ORSA) needs the image size: call mods_verify_tentatives_wh");
+    return MODS_E_ARG;
+  }
   int rc;
   const double t0 = now_ms();
   int nu = n;
@@ -1399,7 +1392,9 @@ int mods_verify_tentatives_ex(int device, const mods_pair_params *par, mods_tent
     }
     memcpy(H, par->ransac.gtH, sizeof(H));     // true_corresp.H = the ground truth, row-major again (matching.cpp:1002-1010)
   } else {
-    if (par->ransac.useF) rc = mods_loransac_f(u6, laf, nu, &par->ransac, mask.data(), H, &ninl, stats);
+    if (par->ransac.useF == 2)
+      rc = mods_orsa_f(u6, laf, nu, w, h, &par->ransac, mask.data(), H, &ninl, nullptr, nullptr, nullptr, stats);
+    else if (par->ransac.useF) rc = mods_loransac_f(u6, laf, nu, &par->ransac, mask.data(), H, &ninl, stats);
     else rc = mods_loransac_h(u6, laf, nu, &par->ransac, mask.data(), H, &ninl, stats);
     if (rc) return rc;
   }
@@ -1426,13 +1421,13 @@ int mods_verify_tentatives_ex(int device, const mods_pair_params *par, mods_tent
 }
 
 int mods_pair_verify_stage(int device, const mods_pair_params *par, mods_pair_result *res, std::vector<mods_tentative> *tent,
-                           std::vector<double> *u6, std::vector<double> *laf, double *matches_out, int max_matches) {
+                           std::vector<double> *u6, std::vector<double> *laf, double *matches_out, int max_matches, int w, int h) {
   int stats[3] = {0, 0, 0};
   // a list the GPU stage has already filtered (DuplicateFiltering on the device, dedup.hip) arrives with n_unique = its length
   mods_pair_params p2;
   if (!tent->empty() && res->n_unique == (int)tent->size() && par->dup_before_ransac) { p2 = *par; p2.dup_dist = 0; par = &p2; }
-  const int rc = mods_verify_tentatives(device, par, tent->data(), u6->data(), laf->data(), (int)tent->size(), &res->n_unique,
-                                        &res->n_inliers, res->H, stats, &res->ms_duplicates, &res->ms_ransac);
+  const int rc = mods_verify_tentatives_wh(device, par, tent->data(), u6->data(), laf->data(), (int)tent->size(), w, h, &res->n_unique,
+                                           &res->n_inliers, res->H, stats, nullptr, &res->ms_duplicates, &res->ms_ransac);
   if (rc) return rc;
   res->ransac_samples = stats[0]; res->ransac_lo = stats[1]; res->ransac_rejects = stats[2];
   if (matches_out)
@@ -1448,7 +1443,7 @@ int mods_match_pair_dev(mods_ctx *c, const float *img_dev, int w, int h, int str
   if (!c) { set_error("match_pair: null context"); return MODS_E_ARG; }
   int rc = mods_pair_gpu_stage(c, img_dev, w, h, stride, par, res, &c->h_tent, &c->h_u6, &c->h_laf);
   if (rc) return rc;
-  return mods_pair_verify_stage(c->device, par, res, &c->h_tent, &c->h_u6, &c->h_laf, matches_out, max_matches);
+  return mods_pair_verify_stage(c->device, par, res, &c->h_tent, &c->h_u6, &c->h_laf, matches_out, max_matches, w, h);
 }
 
 // ---- single primitives -------------------------------------------------------------------

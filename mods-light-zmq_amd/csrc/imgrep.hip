@@ -256,15 +256,16 @@ static void gather_tentatives(mods_ctx *c, const std::vector<TentList> lists[2])
     }
 }
 
-// DuplicateFiltering + LORANSACFiltering of the gathered list (mods.cpp:278-383)
-static int verify_gathered(mods_ctx *c, const mods_pair_params *par, mods_ladder_result *res) {
+// DuplicateFiltering + LORANSACFiltering (ORSAFiltering for useF = 2) of the gathered list (mods.cpp:278-383); w, h: the size
+// ORSA normalises by, ((w1 + w2) / 2, (h1 + h2) / 2) in the step loop (mods.cpp:347-350), 0 where the caller has none
+static int verify_gathered(mods_ctx *c, const mods_pair_params *par, mods_ladder_result *res, int w, int h) {
   const int n = (int)c->h_tent.size();
   res->n_tentatives = n;
   int stats[3] = {0, 0, 0};
   double ms_dup = 0, ms_ran = 0;
   int gt3[3] = {0, 0, 0};
-  const int rc = mods_verify_tentatives_ex(c->device, par, c->h_tent.data(), c->h_u6.data(), c->h_laf.data(), n, &res->n_unique, &res->n_inliers,
-                                           res->H, stats, gt3, &ms_dup, &ms_ran);
+  const int rc = mods_verify_tentatives_wh(c->device, par, c->h_tent.data(), c->h_u6.data(), c->h_laf.data(), n, w, h, &res->n_unique,
+                                           &res->n_inliers, res->H, stats, gt3, &ms_dup, &ms_ran);
   if (rc) return rc;
   res->ms_duplicates += ms_dup; res->ms_ransac += ms_ran;
   res->ransac_samples = stats[0]; res->ransac_lo = stats[1]; res->ransac_rejects = stats[2];
@@ -292,7 +293,7 @@ static int match_verify_banks(mods_ctx *c, mods_imgrep *rep1, mods_imgrep *rep2,
   if (fginn_ratio_half > 0 && (rc = match_into(c, rep1h, rep2h, fginn_ratio_half, par, &lists[1][0]))) return rc;
   gather_tentatives(c, lists);
   res->ms_match += now_ms2() - t1;
-  return verify_gathered(c, par, res);
+  return verify_gathered(c, par, res, 0, 0);   // banks only: no image size (useF = 2 is refused)
 }
 
 // One synthesised view of one image for one detector of a step, and where its regions were left
@@ -578,7 +579,7 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
     }
     gather_tentatives(c, lists);
     res->ms_match += now_ms2() - t1;
-    if ((rc = verify_gathered(c, par, res))) return rc;
+    if ((rc = verify_gathered(c, par, res, (w1 + w2) / 2, (h1 + h2) / 2))) return rc;
     curr_matches = stop_count(par, res);
     res->steps_done = step + 1;
   }

@@ -432,8 +432,8 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
     int stats[3] = {0, 0, 0};
     double ms_dup = 0, ms_ran = 0;
     int gt3[3] = {0, 0, 0};
-    rc = mods_verify_tentatives_ex(m->dev[0], par, tent.data(), u6.data(), laf.data(), (int)tent.size(), &res->n_unique, &res->n_inliers,
-                                   res->H, stats, gt3, &ms_dup, &ms_ran);
+    rc = mods_verify_tentatives_wh(m->dev[0], par, tent.data(), u6.data(), laf.data(), (int)tent.size(), (w1 + w2) / 2, (h1 + h2) / 2,
+                                   &res->n_unique, &res->n_inliers, res->H, stats, gt3, &ms_dup, &ms_ran);
     if (rc) return rc;
     res->ms_duplicates += ms_dup; res->ms_ransac += ms_ran;
     res->ransac_samples = stats[0]; res->ransac_lo = stats[1]; res->ransac_rejects = stats[2];

@@ -28,7 +28,8 @@ extern "C" int mods_pairs_gpu_stage(mods_ctx *c, const void *const *img, const i
                                     mods_pair_result **res, std::vector<mods_tentative> **tent, std::vector<double> **u6,
                                     std::vector<double> **laf);
 extern "C" int mods_pair_verify_stage(int device, const mods_pair_params *par, mods_pair_result *res, std::vector<mods_tentative> *tent,
-                                      std::vector<double> *u6, std::vector<double> *laf, double *matches_out, int max_matches);
+                                      std::vector<double> *u6, std::vector<double> *laf, double *matches_out, int max_matches,
+                                      int w, int h);
 
 namespace mods {
 
@@ -130,7 +131,7 @@ static void verify_worker(mods_pipeline *p) {
     }
     if (j->rc == MODS_OK) {
       const long long c0 = thread_cpu_ns();
-      j->rc = mods_pair_verify_stage(p->device, &p->par, &j->res, &j->tent, &j->u6, &j->laf, nullptr, 0);
+      j->rc = mods_pair_verify_stage(p->device, &p->par, &j->res, &j->tent, &j->u6, &j->laf, nullptr, 0, p->w, p->h);
       p->cpu_verify_ns.fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed);
       if (j->rc) j->err = mods_last_error();
     }
