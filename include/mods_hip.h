@@ -655,6 +655,21 @@ int mods_dev_free(void *p);
 int mods_dev_upload(void *dst_dev, const void *src_host, size_t bytes);
 int mods_dev_download(void *dst_host, const void *src_dev, size_t bytes);
 
+/* ---- CLAHE -------------------------------------------------------------------------------------------
+ * Replaces the [Matching] doCLAHE branch of mods.cpp:133-189: createCLAHE() with setClipLimit(4) on an 8 x 8 tile grid, applied to
+ * the 8-bit grey images before the ImageRepresentation converts them to float.  The arithmetic restates OpenCV's CPU clahe.cpp
+ * for CV_8UC1: tile histograms (the image padded with BORDER_REFLECT_101 when the grid does not divide it),
+ * clip limit max((int)(clip_limit * tile pixels / 256), 1) (clip_limit <= 0: no clipping), redistribution, LUT, bilinear blend of
+ * the four neighbouring tiles' LUTs in float32.  Images are 8-bit only, as OpenCV's CLAHE takes them. */
+typedef struct mods_clahe_params { double clip_limit; int tiles_x, tiles_y; } mods_clahe_params;   /* mods.cpp: 4, 8, 8 */
+/* n_img images [n_img][h][src_stride] (bytes) in HBM -> [n_img][h][dst_stride] u8 (dst_f32 = 0; may be src itself, same stride) or
+ * fp32 (dst_f32 != 0; dst_stride in floats) in HBM.  Tiles in [1, 64] each way; w * h at most the context's max_w * max_h, any
+ * n_img.  Runs on the context's stream and is complete on return.  Arguments are checked before any device call (MODS_E_ARG). */
+int mods_clahe_dev(mods_ctx *ctx, const unsigned char *src_dev, int n_img, int w, int h, int src_stride,
+                   const mods_clahe_params *par, void *dst_dev, int dst_stride, int dst_f32);
+/* one contiguous w x h image, host in, host out (dst_host may be src_host) */
+int mods_clahe(mods_ctx *ctx, const unsigned char *src_host, int w, int h, const mods_clahe_params *par, unsigned char *dst_host);
+
 /* ---- pair pipeline ----------------------------------------------------------------------------------
  * Throughput form of the same path: `gpu_workers` threads (one context each) run detect/describe/match
  * while `verify_workers` threads run duplicate filtering + LO-RANSAC of earlier pairs (mods.cpp overlaps
@@ -671,6 +686,11 @@ int mods_pipeline_create(int device, int w, int h, const mods_pair_params *par, 
  * launches (same results; larger launches, fewer of them per pair) */
 int mods_pipeline_create_ex(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
                             int pairs_per_batch, mods_pipeline **out);
+/* the same with CLAHE (mods_clahe_params, e.g. {4, 8, 8}) in front of detection: 8-bit submissions (mods_pipeline_submit_host_u8)
+ * are equalised on the GPU on their way to fp32, one LUT and one apply launch per batch; fp32 submissions are refused (MODS_E_ARG).
+ * clahe = NULL: mods_pipeline_create_ex */
+int mods_pipeline_create_clahe(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
+                               int pairs_per_batch, const mods_clahe_params *clahe, mods_pipeline **out);
 int mods_pipeline_capacity(const mods_pipeline *p);    /* pairs that may be in flight before submit blocks */
 /* HIP-event timing of the workers' contexts (sums over them); enable/read while nothing is in flight */
 int mods_pipeline_timing_enable(mods_pipeline *p, int stage_mask);

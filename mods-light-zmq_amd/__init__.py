@@ -138,6 +138,15 @@ def view_ctx_dims(w, h):
     return d, d
 
 
+class ClaheParams(C.Structure):
+    """mods_clahe_params: [Matching] doCLAHE of mods.cpp:133-189 (createCLAHE(), setClipLimit(4): 8 x 8 tiles)."""
+    _fields_ = [("clip_limit", C.c_double), ("tiles_x", C.c_int), ("tiles_y", C.c_int)]
+
+    @staticmethod
+    def reference():
+        return ClaheParams(4.0, 8, 8)
+
+
 class Context:
     def __init__(self, device=0, max_w=1920, max_h=1080, batch=1, nonblocking=False):
         self.h = C.c_void_p()
@@ -405,6 +414,22 @@ class Context:
                                          C.c_double(threshold), out.ctypes.data_as(C.c_void_p),
                                          u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return out[:n.value].copy(), u6[:n.value].copy()
+
+    def clahe(self, img_u8, clip_limit=4.0, tiles=(8, 8)):
+        """mods_clahe: CLAHE of one 8-bit grey image [h, w] (host in, host out); tiles = (tiles_x, tiles_y)"""
+        a = np.ascontiguousarray(img_u8, np.uint8)
+        h, w = a.shape
+        out = np.empty_like(a)
+        par = ClaheParams(clip_limit, tiles[0], tiles[1])
+        _check(lib().mods_clahe(self.h, a.ctypes.data_as(C.c_void_p), w, h, C.byref(par), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def clahe_dev(self, src_ptr, n_img, w, h, dst_ptr, clip_limit=4.0, tiles=(8, 8), f32=True, src_stride=None, dst_stride=None):
+        """mods_clahe_dev: n_img 8-bit images [n_img][h][src_stride] in HBM -> [n_img][h][dst_stride] fp32 (f32) or u8 in HBM;
+        complete on return"""
+        par = ClaheParams(clip_limit, tiles[0], tiles[1])
+        _check(lib().mods_clahe_dev(self.h, C.c_void_p(src_ptr), n_img, w, h, src_stride or w, C.byref(par), C.c_void_p(dst_ptr),
+                                    dst_stride or w, 1 if f32 else 0))
 
     def match_dev(self, img_q, img_t, ratio=0.8, contrad=10.0, nn=50, cap=1 << 18):
         out = np.zeros(cap, TENT_DTYPE)
@@ -965,11 +990,17 @@ class Pipeline:
     """mods_pipeline_*: GPU workers (detect/describe/match) overlapped with verify workers (duplicate
     filter + LO-RANSAC) across pairs; results in submission order."""
 
-    def __init__(self, device, w, h, params=None, gpu_workers=1, verify_workers=1, pairs_per_batch=1):
+    def __init__(self, device, w, h, params=None, gpu_workers=1, verify_workers=1, pairs_per_batch=1, clahe=None):
+        """clahe: a ClaheParams - 8-bit submissions are equalised with CLAHE on the GPU, fp32 submissions are refused"""
         self.params = params or PairParams.default()
         self.h = C.c_void_p()
-        _check(lib().mods_pipeline_create_ex(device, w, h, C.byref(self.params), gpu_workers, verify_workers, pairs_per_batch,
-                                             C.byref(self.h)))
+        if clahe is not None:
+            self.clahe = clahe
+            _check(lib().mods_pipeline_create_clahe(device, w, h, C.byref(self.params), gpu_workers, verify_workers, pairs_per_batch,
+                                                    C.byref(self.clahe), C.byref(self.h)))
+        else:
+            _check(lib().mods_pipeline_create_ex(device, w, h, C.byref(self.params), gpu_workers, verify_workers, pairs_per_batch,
+                                                 C.byref(self.h)))
         self.capacity = lib().mods_pipeline_capacity(self.h)
 
     def submit(self, dev_ptr, tag=0):

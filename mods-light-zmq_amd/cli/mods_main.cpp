@@ -56,6 +56,7 @@ struct Config {
   int group_pos = 0;
   int max_steps = 4, min_matches = 15;
   int load_color = 1;
+  int do_clahe = 0;                // [Matching] doCLAHE (io_mods.cpp:526): CLAHE on both 8-bit grey images before detection
   int verbose = 0, time_log = 1, write_keypoints = 1, write_matches = 1, output_h = 0;
   // [zmqDescriptor] (io_mods.cpp:395-407): used when a step asks for the "ZMQ" descriptor instead of RootSIFT
   bool use_zmq = false;
@@ -180,6 +181,7 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->output_h = (int)ini.GetInteger("TextOutput", "outputEstimatedHorF", 0);
   if (ini.GetInteger("TextOutput", "outputAllTentatives", 0)) std::cerr << "Warning: outputAllTentatives is not supported, only verified matches are written" << std::endl;
   cfg->load_color = (int)ini.GetInteger("Computing", "LoadColor", 1);
+  cfg->do_clahe = (int)ini.GetInteger("Matching", "doCLAHE", 0);
   if (ini.Has("zmqDescriptor", "port")) cfg->zmq_port = ini.GetString("zmqDescriptor", "port", "");
   cfg->zmq_mr = ini.GetDouble("zmqDescriptor", "mrSize", cfg->zmq_mr);
   cfg->zmq_ps = (int)ini.GetInteger("zmqDescriptor", "patchSize", cfg->zmq_ps);
@@ -574,6 +576,20 @@ int main(int argc, char **argv) {
   // One run of one pair: further contexts for the views of a step (MODS_LADDER_WORKERS) take longer to set up than they save
   setenv("MODS_LADDER_WORKERS", "1", 0);
   if (mods_ctx_create(device, (int)diag, (int)diag, 2, &ctx)) return fail("context");
+  // mods.cpp:133-189: createCLAHE() (8 x 8 tiles), setClipLimit(4), on the 8-bit grey image (convertTo(CV_8UC1) of the colour average,
+  // or imread's grey bytes); ImageRepresentation then takes the float of the result.  Before everything else, so that every path
+  // below (one GPU, MODS_DEVICES, the ladders) sees the same pixels; the pre-extracted mode has no use for the images
+  if (cfg.do_clahe && !pre_extracted) {
+    const double t0 = now_s();
+    const mods_clahe_params cp = {4.0, 8, 8};
+    for (GreyImage *im : {&img1, &img2}) {
+      std::vector<unsigned char> u8(im->px.size());
+      for (size_t i = 0; i < u8.size(); i++) u8[i] = (unsigned char)std::min(std::max(std::rint(im->px[i]), 0.0f), 255.0f);
+      if (mods_clahe(ctx, u8.data(), im->w, im->h, &cp, u8.data())) return fail("CLAHE");
+      for (size_t i = 0; i < u8.size(); i++) im->px[i] = (float)u8[i];
+    }
+    if (cfg.verbose) std::cerr << " CLAHE done in " << now_s() - t0 << " seconds" << std::endl;
+  }
   for (int d = 0; d < n_det; d++)
     if (mods_imgrep_create(ctx, 1 << 20, &reps1[d]) || mods_imgrep_create(ctx, 1 << 20, &reps2[d])) return fail("region banks");
   if (mods_dev_alloc(sizeof(float) * img1.px.size(), &d1) || mods_dev_alloc(sizeof(float) * img2.px.size(), &d2)) return fail("device memory");

@@ -248,7 +248,7 @@ void mods_ctx_destroy(mods_ctx *c) {
     for (auto &p : t.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
     for (auto &e : t.pool) (void)hipEventDestroy(e);
   }
-  (void)hipFree(c->pyr_dev); (void)hipFree(c->plane_pool); (void)hipFree(c->omap_pool); (void)hipFree(c->input_dev); (void)hipFree(c->u8_stage_dev);
+  (void)hipFree(c->pyr_dev); (void)hipFree(c->plane_pool); (void)hipFree(c->omap_pool); (void)hipFree(c->input_dev); (void)hipFree(c->u8_stage_dev); (void)hipFree(c->clahe_lut);
   (void)hipFree(c->tmp_dev); (void)hipFree(c->alt_taps_dev); (void)hipFree(c->alt_planes); (void)hipFree(c->view_dev); (void)hipFree(c->gauss_taps_dev); (void)hipFree(c->smm_mask_dev); if (c->baum_stats_dev) (void)hipFree(c->baum_stats_dev); (void)hipFree(c->cand);
   (void)hipFree(c->cand_count); (void)hipFree(c->keys_dev); (void)hipFree(c->sort_keys); (void)hipFree(c->sort_idx); (void)hipFree(c->rank_dev); (void)hipFree(c->nms_mask);
   (void)hipHostFree(c->host_counts); (void)hipHostFree(c->pin_arena);
@@ -1179,25 +1179,29 @@ int mods_ctx_warmup(mods_ctx *c, int n_img, int w, int h, const mods_pair_params
 int mods_pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds, int n_pairs, int w, int h, const mods_pair_params *par,
                          mods_pair_result **res, std::vector<mods_tentative> **tent, std::vector<double> **u6, std::vector<double> **laf) {
   if (!c || !img || !par || !res || n_pairs < 1) { set_error("match_pairs: null argument"); return MODS_E_ARG; }
-  if (n_pairs == 1 && (!kinds || kinds[0] == 0)) return mods_pair_gpu_stage(c, (const float *)img[0], w, h, w, par, res[0], tent[0], u6[0], laf[0]);
+  if (n_pairs == 1 && (!kinds || kinds[0] == 0) && !c->clahe_on) return mods_pair_gpu_stage(c, (const float *)img[0], w, h, w, par, res[0], tent[0], u6[0], laf[0]);
   if (c->batch < 2 * n_pairs) { set_error("match_pairs: context batch %d < %d images", c->batch, 2 * n_pairs); return MODS_E_ARG; }
   if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("match_pairs: image larger than the context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
   const size_t plane2 = (size_t)2 * w * h;
   const int n_img = 2 * n_pairs;
+  // CLAHE pipeline (mods_pipeline_create_clahe): the 8-bit pairs are staged side by side and equalised in one LUT + one apply launch
+  // over the batch's 2 n_pairs images, the apply launch writing fp32 into input_dev in the place of u8_to_f32_kernel
+  const bool clahe = c->clahe_on;
   for (int i = 0; i < n_pairs; i++) {
     memset(res[i], 0, sizeof(*res[i]));
     for (int q = 0; q < 9; q++) res[i]->H[q] = -1;
     const int kind = kinds ? kinds[i] : 0;
+    if (clahe && kind != 2) { set_error("match_pairs: a CLAHE pipeline takes 8-bit images only"); return MODS_E_ARG; }
     if (kind == 2) {
       if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
       unsigned char *st = c->u8_stage_dev + plane2 * i;
-      if ((plane2 & 3) || ((uintptr_t)st & 3)) { set_error("match_pairs: 8-bit input needs w*h*2 divisible by 4"); return MODS_E_ARG; }
+      if (!clahe && ((plane2 & 3) || ((uintptr_t)st & 3))) { set_error("match_pairs: 8-bit input needs w*h*2 divisible by 4"); return MODS_E_ARG; }
       // (reading page-locked host images from the conversion kernel itself - no staging copy - was measured: 610 against 636
       // pairs/s, the kernel's waves sit on PCIe reads; the copy engine path stays)
       MODS_HIP_CHECK(hipMemcpyAsync(st, img[i], plane2, hipMemcpyHostToDevice, c->stream));
       const unsigned char *src = st;
-      hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, c->input_dev + plane2 * i, plane2 / 4);
+      if (!clahe) hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, c->input_dev + plane2 * i, plane2 / 4);
     } else {
       MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev + plane2 * i, img[i], sizeof(float) * plane2,
                                     kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
@@ -1206,6 +1210,8 @@ int mods_pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds, 
   MODS_HIP_CHECK(hipGetLastError());
   std::vector<int> nd(n_img), nr(n_img);
   int rc;
+  // (queued ahead of the detect stage's scope: no MODS_STAGE_* bracket includes these two launches, rocprofv3 shows their time)
+  if (clahe && (rc = clahe_launch(c, c->u8_stage_dev, n_img, w, h, w, &c->clahe_par, c->input_dev, w, 1))) return rc;
   const double t0 = now_ms();
   if ((rc = mods_detect_describe_dev(c, c->input_dev, n_img, w, h, w, &par->det, &par->desc, nd.data(), nr.data()))) return rc;
   const double t1 = now_ms();

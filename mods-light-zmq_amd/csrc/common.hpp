@@ -147,6 +147,11 @@ struct mods_ctx {
   int *key_count = nullptr;          // [batch]
   int *host_counts = nullptr;        // pinned
   unsigned char *u8_stage_dev = nullptr;   // [batch][max_h][max_w] staging of 8-bit host images (pair pipeline), lazily allocated
+  // CLAHE (clahe.hip): LUT scratch [n_img][tiles_y * tiles_x][256] (clahe_reserve); clahe_on: the pair pipeline's 8-bit batches are
+  // equalised with clahe_par on their way to fp32 (mods_pipeline_create_clahe)
+  unsigned char *clahe_lut = nullptr; size_t clahe_lut_cap = 0;
+  bool clahe_on = false;
+  mods_clahe_params clahe_par = {0.0, 0, 0};
   char *pin_arena = nullptr;         // pinned host staging of a batch's tentative lists (pair pipeline), lazily allocated
   size_t pin_arena_cap = 0;
   mods_hessaff_params par;
@@ -255,6 +260,11 @@ int gauss_ksize(float sigma);
 void gauss_kernel_host(int n, double sigma, float *out);
 void gauss_mask_host(int size, float *out);
 void circular_gauss_mask_host(int size, float sigma, float *out);
+
+// clahe.hip
+int clahe_reserve(mods_ctx *ctx, int n_img, const mods_clahe_params *par);   // LUT scratch of n_img images (hipMalloc when it grows)
+int clahe_launch(mods_ctx *ctx, const unsigned char *src, int n_img, int w, int h, int src_stride, const mods_clahe_params *par,
+                 void *dst, int dst_stride, int dst_f32);                    // LUT + apply launches on ctx->stream, no wait
 
 // detect.hip
 int detect_run(mods_ctx *ctx);       // NMS -> localise -> dedup -> Baumberg -> sort, for the configured batch

@@ -64,6 +64,8 @@ struct mods_pipeline {
   // CPU time the workers' own threads spent inside their stages (CLOCK_THREAD_CPUTIME_ID; the RANSAC task pool's helper threads,
   // which the verify stage of a hard pair spreads its model fits over, are not in it: the process clock is)
   std::atomic<long long> cpu_gpu_ns{0}, cpu_verify_ns{0};
+  bool clahe = false;             // mods_pipeline_create_clahe: 8-bit submissions only, equalised on the GPU
+  mods_clahe_params clahe_par = {0.0, 0, 0};
 };
 static long long thread_cpu_ns() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (long long)ts.tv_sec * 1000000000ll + ts.tv_nsec; }
 
@@ -81,13 +83,25 @@ static void worker_ready(mods_pipeline *p, int rc) {
   p->cv_ready.notify_all();
 }
 
+// the LUT scratch of a full batch and both CLAHE kernels loaded, ahead of the running pipeline (u8_stage_dev: mods_ctx_warmup)
+static int clahe_warmup(mods_ctx *c, int n_img, int w, int h, const mods_clahe_params *par) {
+  int rc = clahe_reserve(c, n_img, par);
+  if (rc) return rc;
+  MODS_HIP_CHECK(fill_wait(c->stream, c->u8_stage_dev, 0, (size_t)n_img * w * h));
+  if ((rc = clahe_launch(c, c->u8_stage_dev, n_img, w, h, w, par, c->input_dev, w, 1))) return rc;
+  MODS_HIP_CHECK(stream_wait(c->stream));
+  return MODS_OK;
+}
+
 static void gpu_worker(mods_pipeline *p, mods_ctx *ctx) {
   (void)hipSetDevice(p->device);
   pthread_setname_np(pthread_self(), "mods-gpu");
   wait_mode_for_worker(50000);    // a batch takes tens of milliseconds: 50 us between looks
   // every pool a full batch needs (pyramid planes, candidate / region / matcher buffers, code objects) is allocated now: a
   // hipMalloc inside the running pipeline synchronises the whole device
-  worker_ready(p, mods_ctx_warmup(ctx, 2 * p->pairs_per_batch, p->w, p->h, &p->par));
+  int rc = mods_ctx_warmup(ctx, 2 * p->pairs_per_batch, p->w, p->h, &p->par);
+  if (!rc && p->clahe) rc = clahe_warmup(ctx, 2 * p->pairs_per_batch, p->w, p->h, &p->clahe_par);
+  worker_ready(p, rc);
   for (;;) {
     std::vector<std::shared_ptr<Job>> js;
     {
@@ -200,16 +214,27 @@ int mods_pipeline_cpu_seconds(mods_pipeline *p, double *gpu_workers_s, double *v
 
 int mods_pipeline_create_ex(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
                             int pairs_per_batch, mods_pipeline **out) {
+  return mods_pipeline_create_clahe(device, w, h, par, gpu_workers, verify_workers, pairs_per_batch, nullptr, out);
+}
+
+int mods_pipeline_create_clahe(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
+                               int pairs_per_batch, const mods_clahe_params *clahe, mods_pipeline **out) {
   if (!par || !out || gpu_workers < 1 || verify_workers < 1 || gpu_workers > 8 || verify_workers > 32 || pairs_per_batch < 1 ||
       pairs_per_batch > 16) { set_error("pipeline: bad arguments"); return MODS_E_ARG; }
+  if (clahe && (clahe->tiles_x < 1 || clahe->tiles_x > 64 || clahe->tiles_y < 1 || clahe->tiles_y > 64 || w < 1 || h < 1)) {
+    set_error("pipeline: CLAHE tile grid %d x %d outside [1, 64] or image %d x %d", clahe->tiles_x, clahe->tiles_y, w, h);
+    return MODS_E_ARG;
+  }
   std::unique_ptr<mods_pipeline> p(new mods_pipeline());
   p->device = device; p->w = w; p->h = h; p->par = *par;
   p->pairs_per_batch = pairs_per_batch;
+  if (clahe) { p->clahe = true; p->clahe_par = *clahe; }
   p->max_in_flight = 2 * gpu_workers * pairs_per_batch + 2 * verify_workers;
   for (int i = 0; i < gpu_workers; i++) {
     mods_ctx *c = nullptr;
     int rc = mods_ctx_create_ex(device, w, h, 2 * pairs_per_batch, 1, &c);   // non-blocking streams: the workers overlap on the GPU
     if (rc) { for (auto *q : p->ctxs) mods_ctx_destroy(q); return rc; }
+    c->clahe_on = p->clahe; c->clahe_par = p->clahe_par;
     // One stream per worker, eager launches.  A worker's own side stream (the small octaves of the scale space, pyramid.hip) and the
     // replay of its launch chain as a hipGraph (capi.hip: dd_run) both put a dependency between two streams in front of the runtime,
     // and this runtime resolves such a dependency on its own thread, SPINNING until the awaited work is done (tools/ubench/
@@ -256,10 +281,21 @@ static int submit_any(mods_pipeline *p, const void *img, int kind, long tag) {
   return MODS_OK;
 }
 
-int mods_pipeline_submit(mods_pipeline *p, const float *img_dev, long tag) { return submit_any(p, img_dev, 0, tag); }
+// OpenCV's CLAHE takes 8-bit images only: a CLAHE pipeline refuses fp32 pairs
+static int refuse_f32(mods_pipeline *p) {
+  if (p && p->clahe) { set_error("pipeline: CLAHE takes 8-bit images (mods_pipeline_submit_host_u8)"); return MODS_E_ARG; }
+  return MODS_OK;
+}
+int mods_pipeline_submit(mods_pipeline *p, const float *img_dev, long tag) {
+  if (const int rc = refuse_f32(p)) return rc;
+  return submit_any(p, img_dev, 0, tag);
+}
 // The same with the pair in host memory ([2][h][w], fp32 or 8-bit grey; pinned memory makes the upload asynchronous): the
 // boundary of the reference's step loop, mods.cpp:184-383 (decoded images in host memory in, verified matches + H / F out).
-int mods_pipeline_submit_host(mods_pipeline *p, const float *img_host, long tag) { return submit_any(p, img_host, 1, tag); }
+int mods_pipeline_submit_host(mods_pipeline *p, const float *img_host, long tag) {
+  if (const int rc = refuse_f32(p)) return rc;
+  return submit_any(p, img_host, 1, tag);
+}
 int mods_pipeline_submit_host_u8(mods_pipeline *p, const unsigned char *img_host, long tag) { return submit_any(p, img_host, 2, tag); }
 
 // Result of the oldest submitted pair (blocks until it is verified).  Returns MODS_E_ARG when nothing
