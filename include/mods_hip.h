@@ -239,6 +239,29 @@ int mods_ctx_set_external_descriptor(mods_ctx *ctx, mods_descriptor_fn fn, void 
  * patch.  Same callback type as the descriptor (libmodszmq's mods_zmq_descriptor_hook with the daemon's endpoint as user). */
 int mods_ctx_set_external_shape(mods_ctx *ctx, mods_descriptor_fn fn, void *user, double mrSize, int patchSize);
 int mods_ctx_set_external_orientation(mods_ctx *ctx, mods_descriptor_fn fn, void *user, double mrSize, int patchSize);
+/* The same three networks in-process (nets.hip): AffNet, OriNet and HardNet as HIP kernels, fp32 with fp32 accumulation, inference
+ * mode, on 32 x 32 patches.  A patch's output is a function of that patch and the weights only (not of the number of patches in
+ * the call, their order or the chunking).  Outputs per patch are what the reference's daemons reply: AffNet (a11, a21, a22) with
+ * +1 on the first and the last, OriNet (y, x), HardNet 128 values clip(210 * (d + 0.45), 0, 255) truncated to integers.
+ * tensors, in network order: per block weight, running_mean, running_var; then the head's weight and bias (AffNet / OriNet) or
+ * weight, running_mean, running_var (HardNet); n_floats[i] = elements of tensors[i] (checked against the architecture).
+ * A mods_net is immutable after creation and may be used by several contexts and threads at once. */
+typedef struct mods_net mods_net;
+enum { MODS_NET_AFFNET = 0, MODS_NET_ORINET = 1, MODS_NET_HARDNET = 2 };
+int  mods_net_create(int device, int kind, const float *const *tensors, const size_t *n_floats, int n_tensors, mods_net **out);
+void mods_net_destroy(mods_net *net);
+int  mods_net_dim(const mods_net *net);                       /* 3, 2, 128 */
+int  mods_net_chunk(void);                                    /* patches per set of launches (a call of more is cut into chunks) */
+/* patches: [n][32][32] fp32 in 0..255.  quantise_u8 = 1 first rounds them as the wire to a daemon does (round half to even,
+ * clamp to 0..255); 0 feeds the floats.  out: [n][dim].  The _dev form enqueues on hip_stream (a hipStream_t) and does not wait. */
+int  mods_net_forward(mods_net *net, const float *patches_host, int n, int quantise_u8, float *out_host);
+int  mods_net_forward_dev(mods_net *net, void *hip_stream, const float *patches_dev, int n, int quantise_u8, float *out_dev);
+/* A built-in network in the slot of the external shape / orientation / descriptor function (NULL: off): the describe stage feeds
+ * it the patch store in HBM, and only its values per patch go to the host, where the per-keypoint arithmetic of the callback
+ * path runs unchanged.  Setting a network clears the slot's callback and the other way round; the kind must fit the slot. */
+int  mods_ctx_set_builtin_shape(mods_ctx *ctx, mods_net *net, double mrSize, int quantise_u8);
+int  mods_ctx_set_builtin_orientation(mods_ctx *ctx, mods_net *net, double mrSize, int quantise_u8);
+int  mods_ctx_set_builtin_descriptor(mods_ctx *ctx, mods_net *net, double mrSize, int quantise_u8);
 int mods_patches_fetch(mods_ctx *ctx, int img, int ps, float *out, int max_regions, int *n_out);   /* patches of the last describe call */
 /* Baumberg work counters of image slot img (bench.py's per-keypoint figures): keypoints that entered the affine-shape iteration and
  * iterations run since mods_baumberg_stats_enable(ctx, 1); one iteration = smmWindowSize^2 bilinear taps (affine.cpp:26-158). */

@@ -147,6 +147,100 @@ class ClaheParams(C.Structure):
         return ClaheParams(4.0, 8, 8)
 
 
+NET_KINDS = {"affnet": 0, "orinet": 1, "hardnet": 2}
+NET_DIMS = {"affnet": 3, "orinet": 2, "hardnet": 128}
+_NET_SLOTS = {"shape": "affnet", "orientation": "orinet", "descriptor": "hardnet"}
+
+
+def net_tensor_spec(kind):
+    """[(name, shape)] of the tensors a network of `kind` takes, in network order, under the names of the daemon's state dict
+    (zmq_daemon.build_model; `<kind>.` stripped from the arrays of a --weights FILE.npz)."""
+    if kind not in NET_KINDS:
+        raise ModsError("unknown network kind %r (one of %s)" % (kind, ", ".join(sorted(NET_KINDS))))
+    c = 32 if kind == "hardnet" else 16
+    spec = []
+    for i, (cin, cout) in enumerate([(1, c), (c, c), (c, 2 * c), (2 * c, 2 * c), (2 * c, 4 * c), (4 * c, 4 * c)]):
+        spec += [("features.%d.weight" % (3 * i), (cout, cin, 3, 3)), ("features.%d.running_mean" % (3 * i + 1), (cout,)),
+                 ("features.%d.running_var" % (3 * i + 1), (cout,))]
+    if kind == "hardnet":
+        spec += [("features.19.weight", (128, 128, 8, 8)), ("features.20.running_mean", (128,)), ("features.20.running_var", (128,))]
+    else:
+        spec += [("features.19.weight", (NET_DIMS[kind], 64, 8, 8)), ("features.19.bias", (NET_DIMS[kind],))]
+    return spec
+
+
+def net_tensors(kind, state):
+    """The arrays of `state` (name -> array) in network order as contiguous float32, after checking that none is missing, surplus or
+    wrongly shaped (BatchNorm's num_batches_tracked counters of a PyTorch state dict are not tensors of the network and are ignored)."""
+    spec = net_tensor_spec(kind)
+    have = {k: v for k, v in dict(state).items() if not k.endswith("num_batches_tracked")}
+    missing = [n for n, _ in spec if n not in have]
+    if missing:
+        raise ModsError("%s: missing tensors: %s" % (kind, ", ".join(missing)))
+    surplus = sorted(set(have) - {n for n, _ in spec})
+    if surplus:
+        raise ModsError("%s: tensors the network does not have: %s" % (kind, ", ".join(surplus)))
+    out = []
+    for n, shape in spec:
+        a = have[n]
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if tuple(a.shape) != shape:
+            raise ModsError("%s: tensor %s has shape %s, %s expected" % (kind, n, tuple(a.shape), shape))
+        out.append(np.ascontiguousarray(a, np.float32))
+    return out
+
+
+def _slot_check(slot, net):
+    if net is not None and getattr(net, "kind", None) != _NET_SLOTS[slot]:
+        raise ModsError("the built-in %s slot takes a Net of kind %r, not %r" % (slot, _NET_SLOTS[slot], getattr(net, "kind", None)))
+
+
+def net_chunk():
+    """patches one set of launches of a Net takes; a longer list is cut into chunks of this size"""
+    return int(lib().mods_net_chunk())
+
+
+class Net:
+    """AffNet / OriNet / HardNet as HIP kernels (mods_net_*): kind "affnet" | "orinet" | "hardnet", state = the tensors by the
+    names of the daemon's state dict.  Immutable; several contexts and threads may use one Net."""
+
+    def __init__(self, kind, state, device=0):
+        self.h = C.c_void_p()
+        tensors = net_tensors(kind, state)                     # raises before any device call
+        self.kind, self.dim, self.device = kind, NET_DIMS[kind], device
+        ptrs = (C.POINTER(C.c_float) * len(tensors))(*[_fp(t) for t in tensors])
+        sizes = (C.c_size_t * len(tensors))(*[t.size for t in tensors])
+        _check(lib().mods_net_create(device, NET_KINDS[kind], ptrs, sizes, len(tensors), C.byref(self.h)))
+
+    def forward(self, patches, quantise=True):
+        """patches [n][32][32] (values 0..255) -> float32 [n][dim]; quantise: round to 8 bits first, as the wire to a daemon does."""
+        p = np.ascontiguousarray(patches, np.float32)
+        if p.ndim == 4 and p.shape[1] == 1:
+            p = p[:, 0]
+        if p.ndim != 3 or p.shape[1:] != (32, 32):
+            raise ModsError("Net.forward: patches of shape %s, [n][32][32] expected" % (tuple(p.shape),))
+        p = np.ascontiguousarray(p)
+        out = np.zeros((len(p), self.dim), np.float32)
+        _check(lib().mods_net_forward(self.h, _fp(p), len(p), 1 if quantise else 0, _fp(out)))
+        return out
+
+    def forward_dev(self, stream, patches_ptr, n, out_ptr, quantise=True):
+        """device pointers ([n][32][32] fp32 in, [n][dim] fp32 out) on hipStream_t `stream` (an integer address); does not wait"""
+        _check(lib().mods_net_forward_dev(self.h, C.c_void_p(stream), C.c_void_p(patches_ptr), n, 1 if quantise else 0, C.c_void_p(out_ptr)))
+
+    def close(self):
+        if self.h:
+            lib().mods_net_destroy.restype = None
+            lib().mods_net_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, max_w=1920, max_h=1080, batch=1, nonblocking=False):
         self.h = C.c_void_p()
@@ -317,6 +411,24 @@ class Context:
     def set_external_orientation(self, fn_ptr, user, mr_size=3.0 * np.sqrt(3.0), patch_size=32):
         """OriNet in the place of the dominant gradient orientation: fn returns (y, x) per patch.  None: off."""
         _check(lib().mods_ctx_set_external_orientation(self.h, C.c_void_p(fn_ptr), C.c_void_p(user), C.c_double(mr_size), patch_size))
+
+    def set_builtin_shape(self, net, mr_size=3.0 * np.sqrt(3.0), quantise=True):
+        """AffNet in-process (a Net of kind "affnet") in the place of Baumberg; clears an external shape function.  None: off."""
+        _slot_check("shape", net)
+        _check(lib().mods_ctx_set_builtin_shape(self.h, net.h if net is not None else None, C.c_double(mr_size), 1 if quantise else 0))
+        self._nets = dict(getattr(self, "_nets", {}), shape=net)          # keeps the network alive while the context uses it
+
+    def set_builtin_orientation(self, net, mr_size=3.0 * np.sqrt(3.0), quantise=True):
+        """OriNet in-process (a Net of kind "orinet") in the place of the dominant gradient orientation.  None: off."""
+        _slot_check("orientation", net)
+        _check(lib().mods_ctx_set_builtin_orientation(self.h, net.h if net is not None else None, C.c_double(mr_size), 1 if quantise else 0))
+        self._nets = dict(getattr(self, "_nets", {}), orientation=net)
+
+    def set_builtin_descriptor(self, net, mr_size=3.0 * np.sqrt(3.0), quantise=True):
+        """HardNet in-process (a Net of kind "hardnet") in the place of RootSIFT.  None: off."""
+        _slot_check("descriptor", net)
+        _check(lib().mods_ctx_set_builtin_descriptor(self.h, net.h if net is not None else None, C.c_double(mr_size), 1 if quantise else 0))
+        self._nets = dict(getattr(self, "_nets", {}), descriptor=net)
 
     def patches_fetch(self, img, ps, max_regions=1 << 17):
         n = C.c_int()

@@ -68,6 +68,8 @@ struct Config {
   std::string aff_port = "tcp://localhost:5556", ori_port = "tcp://localhost:5557";
   double aff_mr = 3.0 * 1.7320508075688772, ori_mr = 3.0 * 1.7320508075688772;
   int aff_ps = 32, ori_ps = 32;
+  // weights=FILE.npz in [AffNet] / [OriNet] / [zmqDescriptor]: the network runs in-process (mods_net_*), no daemon, no port
+  std::string aff_weights, ori_weights, zmq_weights;
 };
 
 int read_config(const std::string &config_fn, const std::string &iters_fn, int ver_type, Config *cfg) {
@@ -193,6 +195,9 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   if (ini.Has("OriNet", "port")) cfg->ori_port = ini.GetString("OriNet", "port", "");
   cfg->ori_mr = ini.GetDouble("OriNet", "mrSize", cfg->ori_mr);
   cfg->ori_ps = (int)ini.GetInteger("OriNet", "patchSize", cfg->ori_ps);
+  cfg->aff_weights = ini.GetString("AffNet", "weights", "");
+  cfg->ori_weights = ini.GetString("OriNet", "weights", "");
+  cfg->zmq_weights = ini.GetString("zmqDescriptor", "weights", "");
   // iterations file :457-492
   cfg->max_steps = (int)it.GetInteger("Iterations", "Steps", 4);
   cfg->min_matches = (int)it.GetInteger("Iterations", "minMatches", 15);
@@ -412,6 +417,46 @@ bool write_regions_npz(const std::string &fn, const std::vector<mods_imgrep *> &
   return true;
 }
 
+// A built-in network from the arrays `<prefix>.features.N.*` of a weights file written with np.savez (the names of the daemon's
+// --weights FILE.npz), in network order; every missing or misshapen array is an error that names it
+mods_net *load_net(int device, int kind, const std::string &prefix, std::string fn) {
+  while (!fn.empty() && (isspace((unsigned char)fn.back()) || fn.back() == ';')) fn.pop_back();
+  static std::map<std::string, std::map<std::string, modscli::NpyArray>> files;      // one file usually serves all three sections
+  if (!files.count(fn)) {
+    std::string err;
+    std::map<std::string, modscli::NpyArray> z;
+    if (!modscli::npz_read(fn, &z, &err)) { std::cerr << "mods: weights file: " << err << " (write it with numpy.savez, not savez_compressed)" << std::endl; return nullptr; }
+    files[fn] = std::move(z);
+  }
+  const std::map<std::string, modscli::NpyArray> &z = files[fn];
+  std::vector<std::string> names;
+  for (int l = 0; l < 6; l++) {
+    names.push_back("features." + std::to_string(3 * l) + ".weight");
+    names.push_back("features." + std::to_string(3 * l + 1) + ".running_mean");
+    names.push_back("features." + std::to_string(3 * l + 1) + ".running_var");
+  }
+  names.push_back("features.19.weight");
+  if (kind == MODS_NET_HARDNET) { names.push_back("features.20.running_mean"); names.push_back("features.20.running_var"); }
+  else names.push_back("features.19.bias");
+  std::vector<const float *> ptr;
+  std::vector<size_t> cnt;
+  std::string missing;
+  for (const std::string &nm : names) {
+    const auto it = z.find(prefix + "." + nm);
+    if (it == z.end()) { missing += (missing.empty() ? "" : ", ") + prefix + "." + nm; continue; }
+    if (it->second.descr != "<f4") { std::cerr << "mods: " << fn << ": array " << prefix << "." << nm << " is " << it->second.descr << ", float32 expected" << std::endl; return nullptr; }
+    ptr.push_back((const float *)it->second.data.data());
+    cnt.push_back(it->second.count());
+  }
+  if (!missing.empty()) { std::cerr << "mods: " << fn << " has no arrays " << missing << std::endl; return nullptr; }
+  mods_net *net = nullptr;
+  if (mods_net_create(device, kind, ptr.data(), cnt.data(), (int)ptr.size(), &net)) {
+    std::cerr << "mods: " << fn << " (" << prefix << ".*): " << mods_last_error() << std::endl;
+    return nullptr;
+  }
+  return net;
+}
+
 // PreLoadRegionsNPZ, imagerepresentation.cpp:1355-1503: xy, scales, responses, descs and either A, angles (degrees) or neither
 // (upright circles); det_kp = reproj_kp
 bool read_regions_npz(const std::string &fn, std::vector<mods_region> *out) {
@@ -609,19 +654,36 @@ int main(int argc, char **argv) {
   }
   double first_ratio = 0.8;
   for (const mods_ladder_step &st : cfg.steps) if (st.n_tilts >= 0 && st.fginn_ratio > 0) { first_ratio = st.fginn_ratio; break; }
-  if (cfg.use_zmq) {
+  // a section with weights= serves its slot in-process: 32 x 32 patches only, rounded to 8 bits as over the wire
+  mods_net *net_desc = nullptr, *net_aff = nullptr, *net_ori = nullptr;
+  auto builtin = [&](const char *section, const std::string &weights, int ps, int kind, const char *name, const char *prefix, mods_net **net) {
+    if (ps != 32) { std::cerr << "mods: [" << section << "] weights= runs the network in-process on 32x32 patches; patchSize=" << ps << " is not supported" << std::endl; return false; }
+    if (cfg.verbose) std::cerr << "[" << section << "]: " << name << " in-process, weights from " << weights << std::endl;
+    *net = load_net(device, kind, prefix, weights);
+    return *net != nullptr;
+  };
+  if (cfg.use_zmq && !cfg.zmq_weights.empty()) {
+    if (!builtin("zmqDescriptor", cfg.zmq_weights, cfg.zmq_ps, MODS_NET_HARDNET, "HardNet", "hardnet", &net_desc)) return 1;
+    if (mods_ctx_set_builtin_descriptor(ctx, net_desc, cfg.zmq_mr, 1)) return fail("built-in descriptor");
+  } else if (cfg.use_zmq) {
     while (!cfg.zmq_port.empty() && isspace((unsigned char)cfg.zmq_port.back())) cfg.zmq_port.pop_back();
     if (cfg.verbose) std::cerr << "Descriptors from the daemon at " << cfg.zmq_port << " (" << cfg.zmq_ps << "x" << cfg.zmq_ps << " patches)" << std::endl;
     if (mods_ctx_set_external_descriptor(ctx, &mods_zmq_descriptor_hook, (void *)cfg.zmq_port.c_str(), cfg.zmq_mr, cfg.zmq_ps)) return fail("external descriptor");
   }
   auto rtrim = [](std::string &t) { while (!t.empty() && isspace((unsigned char)t.back())) t.pop_back(); };
-  if (cfg.aff_zmq) {
+  if (cfg.aff_zmq && cfg.pair.det.doBaumberg) std::cerr << "Warning: [AffineAdaptation] useZMQ=1 with doBaumberg=1 in [HessianAffine]: the Baumberg frames are replaced" << std::endl;
+  if (cfg.aff_zmq && !cfg.aff_weights.empty()) {
+    if (!builtin("AffNet", cfg.aff_weights, cfg.aff_ps, MODS_NET_AFFNET, "AffNet", "affnet", &net_aff)) return 1;
+    if (mods_ctx_set_builtin_shape(ctx, net_aff, cfg.aff_mr, 1)) return fail("built-in shape");
+  } else if (cfg.aff_zmq) {
     rtrim(cfg.aff_port);
     if (cfg.verbose) std::cerr << "Affine shapes from the daemon at " << cfg.aff_port << std::endl;
-    if (cfg.pair.det.doBaumberg) std::cerr << "Warning: [AffineAdaptation] useZMQ=1 with doBaumberg=1 in [HessianAffine]: the Baumberg frames are replaced" << std::endl;
     if (mods_ctx_set_external_shape(ctx, &mods_zmq_descriptor_hook, (void *)cfg.aff_port.c_str(), cfg.aff_mr, cfg.aff_ps)) return fail("external shape");
   }
-  if (cfg.ori_zmq) {
+  if (cfg.ori_zmq && !cfg.ori_weights.empty()) {
+    if (!builtin("OriNet", cfg.ori_weights, cfg.ori_ps, MODS_NET_ORINET, "OriNet", "orinet", &net_ori)) return 1;
+    if (mods_ctx_set_builtin_orientation(ctx, net_ori, cfg.ori_mr, 1)) return fail("built-in orientation");
+  } else if (cfg.ori_zmq) {
     rtrim(cfg.ori_port);
     if (cfg.verbose) std::cerr << "Orientations from the daemon at " << cfg.ori_port << std::endl;
     if (mods_ctx_set_external_orientation(ctx, &mods_zmq_descriptor_hook, (void *)cfg.ori_port.c_str(), cfg.ori_mr, cfg.ori_ps)) return fail("external orientation");
@@ -756,5 +818,6 @@ int main(int argc, char **argv) {
   if (!multi) for (int d = 0; d < n_det; d++) { mods_imgrep_destroy(reps1[d]); mods_imgrep_destroy(reps2[d]); }
   mods_dev_free(d1); mods_dev_free(d2);
   mods_ctx_destroy(ctx);
+  mods_net_destroy(net_desc); mods_net_destroy(net_aff); mods_net_destroy(net_ori);
   return 0;
 }

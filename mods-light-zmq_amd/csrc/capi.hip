@@ -253,7 +253,7 @@ void mods_ctx_destroy(mods_ctx *c) {
   (void)hipFree(c->cand_count); (void)hipFree(c->keys_dev); (void)hipFree(c->sort_keys); (void)hipFree(c->sort_idx); (void)hipFree(c->rank_dev); (void)hipFree(c->nms_mask);
   (void)hipHostFree(c->host_counts); (void)hipHostFree(c->pin_arena);
   (void)hipFree(c->ori_dev); (void)hipFree(c->ori_multi_dev); (void)hipFree(c->regions_dev); (void)hipFree(c->regions_half_dev); (void)hipFree(c->region_count); (void)hipFree(c->inside_count); (void)hipFree(c->desc_tables_dev); (void)hipFree(c->blur_table_dev);
-  (void)hipFree(c->desc_err_dev); (void)hipFree(c->desc_scratch);
+  (void)hipFree(c->desc_err_dev); (void)hipFree(c->desc_scratch); (void)hipFree(c->net_out_dev);
   (void)hipFree(c->m_desc); (void)hipFree(c->m_c); (void)hipFree(c->m_xy); (void)hipFree(c->m_u64); (void)hipFree(c->m_int); (void)hipFree(c->m_mid);
   (void)hipFree(c->m_p2); (void)hipFree(c->dd_buf); (void)hipFree(c->m_tent2); (void)hipFree(c->m_tent); (void)hipFree(c->m_tent_batch); (void)hipHostFree(c->m_count); (void)hipFree(c->m_regs);
   mser_release(c);
@@ -437,7 +437,7 @@ static unsigned long long fnv1a(const void *p, size_t n, unsigned long long h) {
 // whose scale space does not fork (small images, small batches, mods_ctx_pyramid_streams(1)) stay eager.
 static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
                   const mods_describe_params *desc) {
-  const bool can = c->dd_graphs && c->timing_mask == 0 && !c->ext_fn && !c->shape_fn && !c->ori_fn && det->detectorType != MODS_DET_MSER;
+  const bool can = c->dd_graphs && c->timing_mask == 0 && !mods::has_hooks(c) && !mods::has_nets(c) && det->detectorType != MODS_DET_MSER;
   if (!can) { mods::dev_state_changed(c); return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc); }
   mods_ctx::DdKey key;
   key.img = img_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
@@ -533,6 +533,7 @@ int mods_detect_describe_dev(mods_ctx *c, const float *img_dev, int n_img, int w
 int mods_ctx_set_external_descriptor(mods_ctx *c, mods_descriptor_fn fn, void *user, double mrSize, int patchSize) {
   if (!c) return MODS_E_ARG;
   c->ext_fn = fn; c->ext_user = user; c->ext_mr = mrSize; c->ext_ps = patchSize;
+  c->ext_net = nullptr;                  // a slot holds a callback or a built-in network (nets.hip), never both
   return MODS_OK;
 }
 
@@ -540,6 +541,7 @@ int mods_ctx_set_external_shape(mods_ctx *c, mods_descriptor_fn fn, void *user, 
   if (!c) return MODS_E_ARG;
   if (fn && (patchSize < 8 || patchSize > 63)) { set_error("external shape: patch size %d unsupported", patchSize); return MODS_E_ARG; }
   c->shape_fn = fn; c->shape_user = user; c->shape_mr = mrSize; c->shape_ps = patchSize;
+  c->shape_net = nullptr;
   return MODS_OK;
 }
 
@@ -547,6 +549,7 @@ int mods_ctx_set_external_orientation(mods_ctx *c, mods_descriptor_fn fn, void *
   if (!c) return MODS_E_ARG;
   if (fn && (patchSize < 8 || patchSize > 63)) { set_error("external orientation: patch size %d unsupported", patchSize); return MODS_E_ARG; }
   c->ori_fn = fn; c->ori_user = user; c->ori_mr = mrSize; c->ori_ps = patchSize;
+  c->ori_net = nullptr;
   return MODS_OK;
 }
 // host copy of the patches the describe stage extracted for image slot img in its last call ([n][ps][ps] fp32)

@@ -183,6 +183,11 @@ struct mods_ctx {
   void *shape_user = nullptr, *ori_user = nullptr;
   double shape_mr = 0, ori_mr = 0;
   int shape_ps = 0, ori_ps = 0;
+  // the same three slots served in-process (nets.hip): a network reads the patch store in HBM, only its 3 / 2 / 128 values per
+  // patch go to the host.  A slot holds a callback or a network, never both; the networks are shared, not owned
+  mods_net *shape_net = nullptr, *ori_net = nullptr, *ext_net = nullptr;
+  int shape_q8 = 0, ori_q8 = 0, ext_q8 = 0;          // round the patches to 8 bits first, as the wire to a daemon does
+  float *net_out_dev = nullptr; size_t net_out_cap = 0;   // the networks' outputs of one image slot (floats), grown on demand
   size_t desc_scratch_elems = 0;
   std::vector<int> last_region_counts;
   // matching
@@ -299,6 +304,12 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par);
 int launch_dominant_angle_test(mods_ctx *ctx, const float *patch_dev, int ps, double th, float *out_dev);
 int launch_sift_patch_test(mods_ctx *ctx, const float *patch_dev, int ps, int root, double max_bin, uint8_t *out_dev);
+
+// nets.hip
+inline bool has_hooks(const mods_ctx *c) { return c->ext_fn || c->shape_fn || c->ori_fn; }          // host callbacks (one context)
+inline bool has_nets(const mods_ctx *c) { return c->ext_net || c->shape_net || c->ori_net; }        // built-in networks
+// n patches [n][32][32] of the patch store through `net` on ctx->stream; the net's dim values per patch arrive in out_host (waits)
+int net_run_to_host(mods_ctx *ctx, mods_net *net, const float *patches_dev, int n, int quantise_u8, float *out_host);
 
 
 }  // namespace mods

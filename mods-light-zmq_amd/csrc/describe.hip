@@ -521,7 +521,7 @@ static void build_sift_tab(int ps, SiftTab *t) {   // siftdesc.cpp:22-71, spatia
 }
 
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par) {
-  if (ctx->ext_fn && (ctx->ext_ps < 8 || ctx->ext_ps > 63)) { set_error("external descriptor: patch size %d unsupported", ctx->ext_ps); return MODS_E_ARG; }
+  if ((ctx->ext_fn || ctx->ext_net) && (ctx->ext_ps < 8 || ctx->ext_ps > 63)) { set_error("external descriptor: patch size %d unsupported", ctx->ext_ps); return MODS_E_ARG; }
   if (par->ori_patchSize < 8 || par->ori_patchSize > 48 || par->desc_patchSize < 9 || par->desc_patchSize > 63 ||
       !(par->desc_patchSize & 1)) { set_error("unsupported patch sizes (ori %d, desc %d)", par->ori_patchSize, par->desc_patchSize); return MODS_E_ARG; }
   if (!ctx->desc_tables_dev) {
@@ -572,11 +572,17 @@ static int external_describe(mods_ctx *ctx, int n_img, const DescConst &k) {
   for (int b = 0; b < n_img; b++) {
     const int n = std::min(counts[b], k.reg_cap);
     if (n <= 0) continue;
-    patches.resize((size_t)n * pp); out.assign((size_t)n * 128, 0.f); desc.resize((size_t)n * 128);
-    MODS_HIP_CHECK(mods::copy_wait(ctx->stream, patches.data(), ctx->desc_scratch + (size_t)b * k.reg_cap * pp, sizeof(float) * patches.size(), hipMemcpyDeviceToHost));
-    int dim = 0;
-    const int rc = ctx->ext_fn(ctx->ext_user, patches.data(), n, k.desc_ps, out.data(), out.size(), &dim);
-    if (rc || dim != 128) { set_error("external descriptor failed (rc %d, %d values per patch; 128 expected)", rc, dim); return MODS_E_ARG; }
+    out.assign((size_t)n * 128, 0.f); desc.resize((size_t)n * 128);
+    if (ctx->ext_net) {                    // built-in HardNet: the patches stay in HBM, 128 values per patch come back
+      const int rc = net_run_to_host(ctx, ctx->ext_net, ctx->desc_scratch + (size_t)b * k.reg_cap * pp, n, ctx->ext_q8, out.data());
+      if (rc) return rc;
+    } else {
+      patches.resize((size_t)n * pp);
+      MODS_HIP_CHECK(mods::copy_wait(ctx->stream, patches.data(), ctx->desc_scratch + (size_t)b * k.reg_cap * pp, sizeof(float) * patches.size(), hipMemcpyDeviceToHost));
+      int dim = 0;
+      const int rc = ctx->ext_fn(ctx->ext_user, patches.data(), n, k.desc_ps, out.data(), out.size(), &dim);
+      if (rc || dim != 128) { set_error("external descriptor failed (rc %d, %d values per patch; 128 expected)", rc, dim); return MODS_E_ARG; }
+    }
     for (size_t i = 0; i < desc.size(); i++) {
       const float v = out[i];
       desc[i] = !(v > 0.f) ? 0 : (v >= 255.f ? 255 : (uint8_t)(v + 0.5f));   // !(v > 0): also NaN replies -> 0
@@ -592,7 +598,8 @@ static int external_describe(mods_ctx *ctx, int n_img, const DescConst &k) {
 // networks live behind a callback (the ZMQ client); the patches come from the GPU extraction kernels, the per-keypoint
 // arithmetic around the callback (a few thousand keypoints, double precision, libm) runs on the host as in the reference.
 // ---------------------------------------------------------------------------------------
-// ExtractPatchesColumn patches (mr, ps) of host region lists, one list per image: staged through the region slots
+// ExtractPatchesColumn patches (mr, ps) of host region lists, one list per image: staged through the region slots.
+// patches == nullptr: they stay in the patch store (image b at desc_scratch + b * reg_cap * ps * ps) for a built-in network
 static int net_patches(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, double mr, int ps,
                        const std::vector<std::vector<mods_region>> &regs, const float *dmask, const SiftTab *tab,
                        std::vector<std::vector<float>> *patches) {
@@ -609,6 +616,7 @@ static int net_patches(mods_ctx *ctx, const float *img_dev, int n_img, DescConst
   k.desc_mr = mr; k.desc_ps = ps; k.patch_rule = 1; k.photo = 0;
   int rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, false);
   if (rc) return rc;
+  if (!patches) return MODS_OK;
   MODS_HIP_CHECK(mods::stream_wait(ctx->stream));
   patches->assign(n_img, std::vector<float>());
   const size_t pp = (size_t)ps * ps;
@@ -619,6 +627,8 @@ static int net_patches(mods_ctx *ctx, const float *img_dev, int n_img, DescConst
   }
   return MODS_OK;
 }
+
+constexpr int kNetPS = 32;     // the built-in networks' patch size (mods_ctx_set_builtin_*)
 
 static int fetch_keys(mods_ctx *ctx, int n_img, const int *key_count, std::vector<std::vector<mods_affkey>> *keys) {
   std::vector<int> counts(n_img);
@@ -652,7 +662,7 @@ static int external_shape(mods_ctx *ctx, const float *img_dev, int n_img, const 
   for (int b = 0; b < n_img; b++)
     for (size_t i = 0; i < keys[b].size(); i++) regs[b].push_back(region_of_key(keys[b][i], (int)i));
   std::vector<std::vector<float>> patches;
-  if ((rc = net_patches(ctx, img_dev, n_img, k, ctx->shape_mr, ctx->shape_ps, regs, dmask, tab, &patches))) return rc;
+  if ((rc = net_patches(ctx, img_dev, n_img, k, ctx->shape_mr, ctx->shape_ps, regs, dmask, tab, ctx->shape_net ? nullptr : &patches))) return rc;
   std::vector<int> counts(n_img, 0);
   std::vector<float> out;
   for (int b = 0; b < n_img; b++) {
@@ -660,9 +670,13 @@ static int external_shape(mods_ctx *ctx, const float *img_dev, int n_img, const 
     std::vector<mods_affkey> kept;
     if (n > 0) {
       out.assign((size_t)n * 3, 0.f);
-      int dim = 0;
-      const int frc = ctx->shape_fn(ctx->shape_user, patches[b].data(), n, ctx->shape_ps, out.data(), out.size(), &dim);
-      if (frc || dim != 3) { set_error("external shape function failed (rc %d, %d values per patch; 3 expected)", frc, dim); return MODS_E_ARG; }
+      if (ctx->shape_net) {
+        if ((rc = net_run_to_host(ctx, ctx->shape_net, ctx->desc_scratch + (size_t)b * k.reg_cap * kNetPS * kNetPS, n, ctx->shape_q8, out.data()))) return rc;
+      } else {
+        int dim = 0;
+        const int frc = ctx->shape_fn(ctx->shape_user, patches[b].data(), n, ctx->shape_ps, out.data(), out.size(), &dim);
+        if (frc || dim != 3) { set_error("external shape function failed (rc %d, %d values per patch; 3 expected)", frc, dim); return MODS_E_ARG; }
+      }
       for (int i = 0; i < n; i++) {
         mods_affkey kp = keys[b][i];
         const double a = out[3 * i], bb = 0, c = out[3 * i + 1], d = out[3 * i + 2];
@@ -713,7 +727,7 @@ static int external_orientation(mods_ctx *ctx, const float *img_dev, int n_img, 
     }
   for (int b = 0; b < n_img; b++) inside[b] = (int)regs[b].size();
   std::vector<std::vector<float>> patches;
-  if ((rc = net_patches(ctx, img_dev, n_img, k, ctx->ori_mr, ctx->ori_ps, regs, dmask, tab, &patches))) return rc;
+  if ((rc = net_patches(ctx, img_dev, n_img, k, ctx->ori_mr, ctx->ori_ps, regs, dmask, tab, ctx->ori_net ? nullptr : &patches))) return rc;
   std::vector<int> counts(n_img, 0);
   std::vector<float> out;
   for (int b = 0; b < n_img; b++) {
@@ -721,9 +735,13 @@ static int external_orientation(mods_ctx *ctx, const float *img_dev, int n_img, 
     std::vector<mods_region> kept;
     if (n > 0) {
       out.assign((size_t)n * 2, 0.f);
-      int dim = 0;
-      const int frc = ctx->ori_fn(ctx->ori_user, patches[b].data(), n, ctx->ori_ps, out.data(), out.size(), &dim);
-      if (frc || dim != 2) { set_error("external orientation function failed (rc %d, %d values per patch; 2 expected)", frc, dim); return MODS_E_ARG; }
+      if (ctx->ori_net) {
+        if ((rc = net_run_to_host(ctx, ctx->ori_net, ctx->desc_scratch + (size_t)b * k.reg_cap * kNetPS * kNetPS, n, ctx->ori_q8, out.data()))) return rc;
+      } else {
+        int dim = 0;
+        const int frc = ctx->ori_fn(ctx->ori_user, patches[b].data(), n, ctx->ori_ps, out.data(), out.size(), &dim);
+        if (frc || dim != 2) { set_error("external orientation function failed (rc %d, %d values per patch; 2 expected)", frc, dim); return MODS_E_ARG; }
+      }
       for (int i = 0; i < n; i++) {
         mods_region r = regs[b][i];
         const double angle = atan2f(out[2 * i], out[2 * i + 1]);   // atan2(float, float): the float overload
@@ -804,7 +822,7 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
   k.desc_mr = par->desc_mrSize; k.desc_ps = par->desc_patchSize; k.photo = par->photoNorm; k.root = par->rootSift;
   k.max_bin = par->maxBinValue;
   k.patch_rule = par->fastExtraction ? 2 : 0;
-  const bool external = ctx->ext_fn != nullptr;
+  const bool external = ctx->ext_fn != nullptr || ctx->ext_net != nullptr;
   if (external && par->fastExtraction) { set_error("FastPatchExtraction with an external descriptor is not supported"); return MODS_E_ARG; }
   if (external) { k.desc_mr = ctx->ext_mr; k.desc_ps = ctx->ext_ps; k.photo = 0; k.patch_rule = 1; }
   int *key_count = ctx->cand_count + 2 * ctx->batch;
@@ -812,8 +830,8 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
   const SiftTab *tab = (const SiftTab *)(ctx->desc_tables_dev + kTabSift);
   // doExternalAffineAdaptation is set in the HessianAffine branch of the detector dispatch only (imagerepresentation.cpp:733-737):
   // the regions of DoG / HarrisAffine / MSER views keep their own frames
-  if (ctx->shape_fn && ctx->par.detectorType == MODS_DET_HESSIAN && (rc = external_shape(ctx, img_dev, n_img, k, key_count, dmask, tab))) return rc;
-  if (ctx->ori_fn) {
+  if ((ctx->shape_fn || ctx->shape_net) && ctx->par.detectorType == MODS_DET_HESSIAN && (rc = external_shape(ctx, img_dev, n_img, k, key_count, dmask, tab))) return rc;
+  if (ctx->ori_fn || ctx->ori_net) {
     if ((rc = external_orientation(ctx, img_dev, n_img, k, key_count, dmask, tab))) return rc;
   } else {
     StageScope ts(ctx, MODS_STAGE_ORIENT);

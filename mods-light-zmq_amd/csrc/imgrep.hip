@@ -318,7 +318,8 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
                          const mods_hessaff_params *dets, std::vector<ViewJob> &jobs) {
   static const int env_workers = getenv("MODS_LADDER_WORKERS") ? atoi(getenv("MODS_LADDER_WORKERS")) : 4;
   int n_workers = std::max(1, std::min(env_workers, 8));
-  if (c->ext_fn || c->shape_fn || c->ori_fn) n_workers = 1;      // the daemons' hooks belong to one context
+  if (mods::has_hooks(c)) n_workers = 1;                         // the daemons' hooks belong to one context (built-in networks
+                                                                 // are shared: the helpers get them below and the ladder keeps its workers)
   if (jobs.empty()) return MODS_OK;
   // Work units: a view of image 1 and the same view of image 2 go through ONE chain of launches when the images have one size
   // (both images of a pair share their view schedule) and the contexts hold two images; otherwise one job per unit.
@@ -369,7 +370,12 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
       c->helpers[k - 1] = h;
     }
     mods_ctx *wk = k == 0 ? c : c->helpers[k - 1];
-    if (k > 0) wk->timing_mask = c->timing_mask;
+    if (k > 0) {
+      wk->timing_mask = c->timing_mask;
+      wk->shape_net = c->shape_net; wk->shape_q8 = c->shape_q8; wk->shape_mr = c->shape_mr; wk->shape_ps = c->shape_ps;
+      wk->ori_net = c->ori_net; wk->ori_q8 = c->ori_q8; wk->ori_mr = c->ori_mr; wk->ori_ps = c->ori_ps;
+      wk->ext_net = c->ext_net; wk->ext_q8 = c->ext_q8; wk->ext_mr = c->ext_mr; wk->ext_ps = c->ext_ps;
+    }
     mods_ctx::StageArena &A = c->helper_stage[k];
     size_t used = 0;
     auto park = [&](int ji, int slot) {                         // regions of context slot `slot` -> this worker's arena
