@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -95,6 +96,63 @@ struct StageTimer {
 __host__ __device__ inline size_t tent_u6_off(size_t n) { return (n * sizeof(mods_tentative) + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t tent_laf_off(size_t n) { return tent_u6_off(n) + n * 6 * sizeof(double); }
 __host__ __device__ inline size_t tent_bytes(size_t n) { return tent_laf_off(n) + n * 14 * sizeof(double); }
+
+namespace mods {
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The packed form of n tentatives (mods_ctx::m_tent) split into / joined from three arrays.  These two and the device code that
+// writes and reads the packed form (match.hip: the emit kernel, dedup.hip) are all that knows the layout.  unpack: any of the
+// three destinations may be null
+inline void tent_unpack(const char *packed, size_t n, mods_tentative *tent, double *u6, double *laf) {
+  if (tent) memcpy(tent, packed, sizeof(mods_tentative) * n);
+  if (u6) memcpy(u6, packed + tent_u6_off(n), sizeof(double) * 6 * n);
+  if (laf) memcpy(laf, packed + tent_laf_off(n), sizeof(double) * 14 * n);
+}
+inline void tent_pack(char *packed, size_t n, const mods_tentative *tent, const double *u6, const double *laf) {
+  memcpy(packed, tent, sizeof(mods_tentative) * n);
+  memcpy(packed + tent_u6_off(n), u6, sizeof(double) * 6 * n);
+  memcpy(packed + tent_laf_off(n), laf, sizeof(double) * 14 * n);
+}
+
+// A tentative list on the host: tent[n], the correspondences u6[n][6] and the frames laf[n][14], always of one length
+struct TentList {
+  std::vector<mods_tentative> tent;
+  std::vector<double> u6, laf;
+  size_t size() const { return tent.size(); }
+  bool empty() const { return tent.empty(); }
+  void clear() { tent.clear(); u6.clear(); laf.clear(); }
+  void resize(size_t n) { tent.resize(n); u6.resize(n * 6); laf.resize(n * 14); }
+  void truncate(size_t n) { if (n < size()) resize(n); }
+  void append(const TentList &o) {
+    tent.insert(tent.end(), o.tent.begin(), o.tent.end());
+    u6.insert(u6.end(), o.u6.begin(), o.u6.end());
+    laf.insert(laf.end(), o.laf.begin(), o.laf.end());
+  }
+  void unpack_from(const char *packed, size_t n) { resize(n); tent_unpack(packed, n, tent.data(), u6.data(), laf.data()); }
+  void pack_into(char *packed) const { tent_pack(packed, size(), tent.data(), u6.data(), laf.data()); }
+  // the verified correspondences a verification left in the first rows, as (x1 y1 x2 y2) per match
+  void copy_matches(int n, double *matches_out, int max_matches) const {
+    if (!matches_out) return;
+    for (int m = 0; m < n && m < max_matches && (size_t)m < size(); m++) {
+      const double *p = &u6[(size_t)m * 6];
+      matches_out[4 * m] = p[0]; matches_out[4 * m + 1] = p[1]; matches_out[4 * m + 2] = p[3]; matches_out[4 * m + 3] = p[4];
+    }
+  }
+};
+
+// mods_ctx::m_count, the pinned counter block: three runs of kCountSlots ints - list lengths the emit kernel writes, lengths the
+// device duplicate filter kept, and that filter's status (0 = filtered).  Entry 0 of a run belongs to the last single search
+// (kLastSearch), entry 1 + i to pair i of a batch: a batch holds at most kCountSlots - 1 pairs
+constexpr int kCountSlots = 64;
+constexpr int kCountInts = 3 * kCountSlots;
+constexpr int kLastSearch = -1;
+constexpr int count_slot(int pair = kLastSearch) { return 1 + pair; }
+constexpr int kept_slot(int pair = kLastSearch) { return kCountSlots + 1 + pair; }
+constexpr int status_slot(int pair = kLastSearch) { return 2 * kCountSlots + 1 + pair; }
+inline int read_slot(const int *counts, int slot) { return ((const volatile int *)counts)[slot]; }   // a device wrote it: after a stream wait
+
+}  // namespace mods
 
 struct mods_ctx {
   int device = 0;
@@ -204,15 +262,13 @@ struct mods_ctx {
   // m_tent holds the n tentatives of the last search PACKED: mods_tentative[n] | (16-byte aligned) u6[n][6] = the correspondences
   // (x1 y1 1 x2 y2 1) | laf[n][14] = the frames (x y a11 a12 a21 a22 s) of both regions - one device-to-host copy of
   // tent_bytes(n) bytes brings all three (tent_u6_off / tent_laf_off give the parts)
-  int *m_count = nullptr;            // PINNED HOST memory (192 ints): [0] tentatives of the last search, [1..63] of pair i of a batch (emit kernel);
-                                     // [64 + i] / [128 + i] kept correspondences / status of the device duplicate filter (i = 0: the last search)
+  int *m_count = nullptr;            // PINNED HOST memory (kCountInts ints), indexed by count_slot / kept_slot / status_slot
   mods_tentative *m_tent_out = nullptr; int *m_count_out = nullptr;   // set by a batch of pairs: where match_run leaves the packed list / its length
   char *m_tent_batch = nullptr; size_t m_tent_batch_cap = 0;          // the packed lists of a batch, one segment per pair
   mods_region *m_regs = nullptr;     // [2][max_cand] staging for host-side lists
   void *dd_buf = nullptr; int dd_jobs = 0;   // duplicate filter on the device (dedup.hip): per list of a batch sorted coordinates, ranks, near lists
   mods_tentative *m_tent2 = nullptr; // the filtered packed list of the last search (single-pair path)
-  std::vector<mods_tentative> h_tent;  // host copies for the sequential stages
-  std::vector<double> h_u6, h_laf;
+  mods::TentList h_list;             // host copy for the sequential stages
   std::vector<unsigned char> h_mask;
   void *mser = nullptr;              // MserState (mser.hip): buffers of the MSER detector, allocated on first use
   // the step loop spreads the views of a step over a few more contexts of the same GPU (imgrep.hip: run_view_jobs)
@@ -292,6 +348,7 @@ constexpr int DUP_MAX_JOBS = 64;
 struct DupJob { const char *src; char *dst; const int *n_src; int *n_dst; int *status; };
 int dup_filter_dev(mods_ctx *c, const DupJob *jobs, int n_jobs, int grid_n, double r, int mode);
 int dup_filter_reserve(mods_ctx *c, int n_jobs);
+static_assert(DUP_MAX_JOBS <= kCountSlots, "every job of the duplicate filter has its slots in m_count");
 int launch_fast_sqrt_selftest(mods_ctx *ctx, unsigned long long *out5_host);   // describe.hip
 int launch_blur_table(mods_ctx *ctx, int ps);   // sift.hip
 bool ransac_profile_on();     // MODS_RANSAC_PROF: per-call breakdown of the verification on stderr (ransac.hip)
@@ -311,8 +368,22 @@ inline bool has_nets(const mods_ctx *c) { return c->ext_net || c->shape_net || c
 // n patches [n][32][32] of the patch store through `net` on ctx->stream; the net's dim values per patch arrive in out_host (waits)
 int net_run_to_host(mods_ctx *ctx, mods_net *net, const float *patches_dev, int n, int quantise_u8, float *out_host);
 
+// pair.hip: the two halves of a pair.  The GPU half detects, describes and matches (a batch: the images of all pairs as one batch)
+// and leaves every pair's tentatives in its list; the host-driven half filters duplicates and verifies the list in place
+int pair_gpu_stage(mods_ctx *c, const float *img_dev, int w, int h, int stride, const mods_pair_params *par, mods_pair_result *res,
+                   TentList *list);
+int pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds, int n_pairs, int w, int h, const mods_pair_params *par,
+                    mods_pair_result *const *res, TentList *const *lists);
+int pair_verify_stage(int device, const mods_pair_params *par, mods_pair_result *res, TentList *list, double *matches_out,
+                      int max_matches, int w, int h);
 
 }  // namespace mods
 
+// entry points of the library that include/mods_hip.h does not list
+extern "C" {
 // capi.hip: the packed output of the last search in one device-to-host copy, split into the caller's arrays (synchronises the stream)
-extern "C" int mods_match_copy_out(mods_ctx *c, int n, mods_tentative *tent, double *u6, double *laf);
+int mods_match_copy_out(mods_ctx *c, int n, mods_tentative *tent, double *u6, double *laf);
+int mods_match_fetch_internal(mods_ctx *c, mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out);   // capi.hip
+int mods_ransac_warmup(int device, int len);                                                  // ransac.hip
+int mods_ctx_warmup(mods_ctx *c, int n_img, int w, int h, const mods_pair_params *par);       // pair.hip
+}

@@ -36,22 +36,11 @@ __global__ void __launch_bounds__(256) shift_ids_kernel(mods_region *reg, int n,
   if (i < n) { reg[i].id += shift; reg[i].parent += shift; }
 }
 
-static double now_ms2() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace mods
 
 using namespace mods;
 
 extern "C" {
-
-int mods_loransac_h(const double *u6, const double *laf, int n, const mods_ransac_params *par, unsigned char *mask, double *H_out,
-                    int *n_inliers, int *stats3);
-int mods_loransac_f(const double *u6, const double *laf, int n, const mods_ransac_params *par, unsigned char *mask, double *F_out,
-                    int *n_inliers, int *stats3);
-int mods_duplicate_filter(mods_tentative *tent, double *u6, double *laf, int n, double r, int mode, int *n_out);
-int mods_ransac_set_device(int device);
-int mods_unoriented_count(mods_ctx *c, int img);
-int mods_match_fetch_internal(mods_ctx *c, mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out);   // capi.hip
 
 int mods_host_alloc(size_t bytes, void **out) { if (!out) return MODS_E_ARG; MODS_HIP_CHECK(hipHostMalloc(out, bytes ? bytes : 4, hipHostMallocDefault)); return MODS_OK; }
 int mods_host_free(void *p) { MODS_HIP_CHECK(hipHostFree(p)); return MODS_OK; }
@@ -217,17 +206,9 @@ int mods_match_reps_any(mods_ctx *c, const mods_imgrep *q, int q_begin, int q_en
 // img1_dev / img2_dev: dense fp32 images in HBM (the two images may differ in size).  Every step adds the step's new views of both images to the two region
 // banks, matches bank 1 against bank 2, filters duplicates, verifies, and stops once the verified
 // matches reach min_matches.
-static void copy_verified(mods_ctx *c, const mods_ladder_result *res, double *matches_out, int max_matches) {
-  if (!matches_out) return;
-  for (int m = 0; m < res->n_inliers && m < max_matches; m++) {   // mods_verify_tentatives left the verified rows first
-    const double *p = &c->h_u6[(size_t)m * 6];
-    matches_out[4 * m] = p[0]; matches_out[4 * m + 1] = p[1]; matches_out[4 * m + 2] = p[3]; matches_out[4 * m + 3] = p[4];
-  }
-}
 
 // One FGINN search of bank q against bank t into a host list (MatchFlannFGINN of one (detector, descriptor) pair,
 // correspondencebank.cpp:288-340)
-struct TentList { std::vector<mods_tentative> t; std::vector<double> u6, laf; void clear() { t.clear(); u6.clear(); laf.clear(); } };
 // distance > 0: MatchFLANNDistance (Hamming, threshold `distance`) instead of the FGINN search
 static int match_into(mods_ctx *c, mods_imgrep *q, mods_imgrep *t, double ratio, const mods_pair_params *par, TentList *out, double distance = 0) {
   int rc, m = 0;
@@ -237,34 +218,30 @@ static int match_into(mods_ctx *c, mods_imgrep *q, mods_imgrep *t, double ratio,
   else rc = match_run(c, q->reg, q->n, t->reg, t->n, ratio, par->contradDist, par->nn);
   if (rc) return rc;
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
-  m = *(volatile int *)c->m_count;
+  m = read_slot(c->m_count, count_slot());
   if (m > c->max_cand) { set_error("tentative list overflow"); return MODS_E_CAPACITY; }
-  out->t.resize(m); out->u6.resize((size_t)m * 6); out->laf.resize((size_t)m * 14);
-  return mods_match_copy_out(c, m, out->t.data(), out->u6.data(), out->laf.data());
+  out->resize(m);
+  return mods_match_copy_out(c, m, out->tent.data(), out->u6.data(), out->laf.data());
 }
 
 // CorrespondenceBank::GetCorresponcesVector("All", "All") (correspondencebank.cpp:114-148): the bank is a std::map keyed by
 // descriptor name, then by detector name, and the joint list walks it in key order - "HalfRootSIFT" before "RootSIFT",
 // detectors in the (name-sorted) order the caller listed them.  lists[desc][det], desc 0 = RootSIFT, 1 = HalfRootSIFT.
 static void gather_tentatives(mods_ctx *c, const std::vector<TentList> lists[2]) {
-  c->h_tent.clear(); c->h_u6.clear(); c->h_laf.clear();
+  c->h_list.clear();
   for (int desc = 1; desc >= 0; desc--)
-    for (const TentList &l : lists[desc]) {
-      c->h_tent.insert(c->h_tent.end(), l.t.begin(), l.t.end());
-      c->h_u6.insert(c->h_u6.end(), l.u6.begin(), l.u6.end());
-      c->h_laf.insert(c->h_laf.end(), l.laf.begin(), l.laf.end());
-    }
+    for (const TentList &l : lists[desc]) c->h_list.append(l);
 }
 
 // DuplicateFiltering + LORANSACFiltering (ORSAFiltering for useF = 2) of the gathered list (mods.cpp:278-383); w, h: the size
 // ORSA normalises by, ((w1 + w2) / 2, (h1 + h2) / 2) in the step loop (mods.cpp:347-350), 0 where the caller has none
 static int verify_gathered(mods_ctx *c, const mods_pair_params *par, mods_ladder_result *res, int w, int h) {
-  const int n = (int)c->h_tent.size();
+  const int n = (int)c->h_list.size();
   res->n_tentatives = n;
   int stats[3] = {0, 0, 0};
   double ms_dup = 0, ms_ran = 0;
   int gt3[3] = {0, 0, 0};
-  const int rc = mods_verify_tentatives_wh(c->device, par, c->h_tent.data(), c->h_u6.data(), c->h_laf.data(), n, w, h, &res->n_unique,
+  const int rc = mods_verify_tentatives_wh(c->device, par, c->h_list.tent.data(), c->h_list.u6.data(), c->h_list.laf.data(), n, w, h, &res->n_unique,
                                            &res->n_inliers, res->H, stats, gt3, &ms_dup, &ms_ran);
   if (rc) return rc;
   res->ms_duplicates += ms_dup; res->ms_ransac += ms_ran;
@@ -286,13 +263,13 @@ static int stop_count(const mods_pair_params *par, const mods_ladder_result *res
 static int match_verify_banks(mods_ctx *c, mods_imgrep *rep1, mods_imgrep *rep2, double fginn_ratio, const mods_pair_params *par,
                               mods_ladder_result *res, mods_imgrep *rep1h = nullptr, mods_imgrep *rep2h = nullptr, double fginn_ratio_half = 0) {
   int rc;
-  const double t1 = now_ms2();
+  const double t1 = now_ms();
   std::vector<TentList> lists[2];
   lists[0].resize(1); lists[1].resize(1);
   if (fginn_ratio > 0 && (rc = match_into(c, rep1, rep2, fginn_ratio, par, &lists[0][0]))) return rc;
   if (fginn_ratio_half > 0 && (rc = match_into(c, rep1h, rep2h, fginn_ratio_half, par, &lists[1][0]))) return rc;
   gather_tentatives(c, lists);
-  res->ms_match += now_ms2() - t1;
+  res->ms_match += now_ms() - t1;
   return verify_gathered(c, par, res, 0, 0);   // banks only: no image size (useF = 2 is refused)
 }
 
@@ -492,7 +469,7 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
   for (int step = 0; step < n_steps && curr_matches < min_matches; step++) {
     std::vector<int> new_views(n_det, 0);
     std::vector<ViewJob> jobs;
-    const double t0 = now_ms2();
+    const double t0 = now_ms();
     for (int d = 0; d < n_det; d++) {
       const mods_ladder_step &st = steps[(size_t)step * n_det + d];
       if (st.n_tilts < 0 || st.n_scales < 0) continue;          // the detector has no section in this step
@@ -529,7 +506,7 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
     }
     res->n_described[0] = res->n_described[1] = 0;
     for (int d = 0; d < n_det; d++) { res->n_described[0] += reps1[d]->n; res->n_described[1] += reps2[d]->n; }
-    const double t1 = now_ms2();
+    const double t1 = now_ms();
     res->ms_detect_describe += t1 - t0;
     // MatchImgReps, correspondencebank.cpp:286-340: a detector is matched in a step that brought new views of it; each of its
     // descriptor lists is cleared and searched again over everything accumulated.  Lists that are not touched keep their
@@ -584,12 +561,12 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
       }
     }
     gather_tentatives(c, lists);
-    res->ms_match += now_ms2() - t1;
+    res->ms_match += now_ms() - t1;
     if ((rc = verify_gathered(c, par, res, (w1 + w2) / 2, (h1 + h2) / 2))) return rc;
     curr_matches = stop_count(par, res);
     res->steps_done = step + 1;
   }
-  copy_verified(c, res, matches_out, max_matches);
+  c->h_list.copy_matches(res->n_inliers, matches_out, max_matches);   // the verification left the verified rows first
   return MODS_OK;
 }
 
@@ -619,7 +596,7 @@ int mods_match_verify_reps(mods_ctx *c, mods_imgrep *rep1, mods_imgrep *rep2, do
   const int rc = match_verify_banks(c, rep1, rep2, fginn_ratio, par, res);
   if (rc) return rc;
   res->steps_done = 1;
-  copy_verified(c, res, matches_out, max_matches);
+  c->h_list.copy_matches(res->n_inliers, matches_out, max_matches);   // the verification left the verified rows first
   return MODS_OK;
 }
 

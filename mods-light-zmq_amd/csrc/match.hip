@@ -972,7 +972,7 @@ int match_ensure_buffers(mods_ctx *ctx, int n_sets) {
   if (!ctx->m_tent) MODS_HIP_CHECK(hipMalloc(&ctx->m_tent, tent_bytes(n) + 64));
   // the tentative count lives in pinned host memory: the emit kernel's single store lands there, the host reads it after a
   // stream synchronisation - no 4-byte copy launch per search
-  if (!ctx->m_count) MODS_HIP_CHECK(hipHostMalloc(&ctx->m_count, 192 * sizeof(int)));   // [0]: the last search; [i]: pair i of a batch (m_count_out)
+  if (!ctx->m_count) MODS_HIP_CHECK(hipHostMalloc(&ctx->m_count, mods::kCountInts * sizeof(int)));   // (slots: common.hpp)
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_desc, 0, S * st.s_desc, ctx->stream));
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_c, 0, S * st.s_c * sizeof(int), ctx->stream));
   ctx->m_sets = n_sets;
@@ -1072,7 +1072,7 @@ int match_run(mods_ctx *ctx, const mods_region *q_dev, int n_q, const mods_regio
               double contradDist, int nn) {
   int rc = match_ensure_buffers(ctx);
   if (rc) return rc;
-  // where the packed list and its length go: the context's own buffer / counter, or what a batch of pairs set (capi.hip: match_pairs)
+  // where the packed list and its length go: the context's own buffer / counter, or what a batch of pairs set (pair.hip: pairs_gpu_stage)
   mods_tentative *tent_out = ctx->m_tent_out ? ctx->m_tent_out : ctx->m_tent;
   int *count_out = ctx->m_count_out ? ctx->m_count_out : ctx->m_count;
   return match_run_group(ctx, 1, &q_dev, &n_q, &t_dev, &n_t, &tent_out, &count_out, ratio, contradDist, nn);

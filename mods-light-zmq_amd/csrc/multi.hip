@@ -22,14 +22,13 @@
 #include "common.hpp"
 #include <rccl/rccl.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <memory>
 #include <string>
 #include <thread>
 
-extern "C" int mods_ctx_create_ex(int device, int max_w, int max_h, int batch, int flags, mods_ctx **out);
 using mods::set_error;
+using mods::TentList;
 
 struct mods_multi {
   int n = 0;
@@ -48,10 +47,6 @@ struct mods_multi {
   size_t img_px = 0;                  // pixels the image buffer of a device holds (both images together)
   int side = 0;                       // side of the contexts' square canvas (>= the diagonal of the images given at creation)
 };
-
-extern "C" int mods_match_reps_any(mods_ctx *c, const mods_imgrep *q, int q_begin, int q_end, const mods_imgrep *t, double ratio, double contradDist,
-                                   int nn, double distance, mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out);
-extern "C" int mods_regions_half_copy_dev(mods_ctx *c, int img, mods_region *dst_dev, int n);
 
 namespace {
 
@@ -74,7 +69,6 @@ void assign_views(const std::vector<double> &areas, int n_dev, std::vector<std::
 }
 
 struct Job { int det, im; mods_view_par v; double init_sigma; int do_blur; int half_ori, want_half; };
-struct TentList { std::vector<mods_tentative> t; std::vector<double> u6, laf; void clear() { t.clear(); u6.clear(); laf.clear(); } };
 
 int bank(mods_multi *m, std::vector<std::vector<mods_imgrep *>> &v, int d, int det) {
   if ((int)v[d].size() <= det) v[d].resize(det + 1, nullptr);
@@ -101,21 +95,17 @@ int match_sharded(mods_multi *m, const std::vector<mods_imgrep *> &q, const std:
       const int q0 = (int)((long long)nq * d / D), q1 = (int)((long long)nq * (d + 1) / D);
       if (q1 <= q0) return;
       const int cap = q1 - q0;
-      part[d].t.resize(cap); part[d].u6.resize((size_t)cap * 6); part[d].laf.resize((size_t)cap * 14);
+      part[d].resize(cap);
       int n = 0;
-      const int rc = mods_match_reps_any(m->ctx[d], q[d], q0, q1, t[d], ratio, par->contradDist, par->nn, distance, part[d].t.data(),
+      const int rc = mods_match_reps_any(m->ctx[d], q[d], q0, q1, t[d], ratio, par->contradDist, par->nn, distance, part[d].tent.data(),
                                          part[d].u6.data(), part[d].laf.data(), cap, &n);
       if (rc) { rcs[d] = rc; errs[d] = mods_last_error(); return; }
-      part[d].t.resize(n); part[d].u6.resize((size_t)n * 6); part[d].laf.resize((size_t)n * 14);
+      part[d].truncate(n);
     });
   for (auto &x : th) x.join();
   for (int d = 0; d < D; d++)
     if (rcs[d]) { set_error("device %d: %s", m->dev[d], errs[d].c_str()); return rcs[d]; }
-  for (int d = 0; d < D; d++) {
-    out->t.insert(out->t.end(), part[d].t.begin(), part[d].t.end());
-    out->u6.insert(out->u6.end(), part[d].u6.begin(), part[d].u6.end());
-    out->laf.insert(out->laf.end(), part[d].laf.begin(), part[d].laf.end());
-  }
+  for (int d = 0; d < D; d++) out->append(part[d]);
   return MODS_OK;
 }
 
@@ -247,9 +237,7 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
   lists[0].resize(n_slots); lists[1].resize(n_slots);
   auto slot_of = [&](int d) { return groups && d >= group_pos ? d + 1 : d; };
   int curr_matches = 0;
-  std::vector<mods_tentative> tent;
-  std::vector<double> u6, laf;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  TentList joint;
   for (int step = 0; step < n_steps && curr_matches < min_matches; step++) {
     // ---- the step's view jobs in canonical order: detector, image, view (the order mods_match_ladder_groups_dev appends in)
     std::vector<Job> jobs;
@@ -277,7 +265,7 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
         if (pd[det].half && ((rc = bank(m, m->h1, d, det)) || (rc = bank(m, m->h2, d, det)))) return rc;
     std::vector<std::vector<int>> mine;
     assign_views(areas, D, &mine);
-    const double t0 = now();
+    const double t0 = mods::now_ms();
     // ---- every device: synthesise / detect / describe its views; a job's regions are packed RootSIFT first, then (when the
     // step asks for HalfRootSIFT lists) its HalfRootSIFT twins
     std::vector<int> job_count(jobs.size(), 0), job_det(jobs.size(), 0), job_unor(jobs.size(), 0);
@@ -360,7 +348,7 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
     }
     res->n_described[0] = res->n_described[1] = 0;
     for (int det = 0; det < n_det; det++) { res->n_described[0] += mods_imgrep_count(m->r1[0][det]); res->n_described[1] += mods_imgrep_count(m->r2[0][det]); }
-    const double t1 = now();
+    const double t1 = mods::now_ms();
     res->ms_detect_describe += t1 - t0;
     // ---- MatchImgReps (correspondencebank.cpp:245-340), the rules of mods_match_ladder_groups_dev, every search sharded by
     // query rows
@@ -418,22 +406,18 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
       }
     }
     // the joint list in the bank's key order: HalfRootSIFT lists before RootSIFT lists, detectors in slot order
-    tent.clear(); u6.clear(); laf.clear();
+    joint.clear();
     for (int desc = 1; desc >= 0; desc--)
-      for (const TentList &l : lists[desc]) {
-        tent.insert(tent.end(), l.t.begin(), l.t.end());
-        u6.insert(u6.end(), l.u6.begin(), l.u6.end());
-        laf.insert(laf.end(), l.laf.begin(), l.laf.end());
-      }
-    const double t2 = now();
+      for (const TentList &l : lists[desc]) joint.append(l);
+    const double t2 = mods::now_ms();
     res->ms_match += t2 - t1;
-    res->n_tentatives = (int)tent.size();
+    res->n_tentatives = (int)joint.size();
     // ---- device 0's host: duplicate filter + verification
     int stats[3] = {0, 0, 0};
     double ms_dup = 0, ms_ran = 0;
     int gt3[3] = {0, 0, 0};
-    rc = mods_verify_tentatives_wh(m->dev[0], par, tent.data(), u6.data(), laf.data(), (int)tent.size(), (w1 + w2) / 2, (h1 + h2) / 2,
-                                   &res->n_unique, &res->n_inliers, res->H, stats, gt3, &ms_dup, &ms_ran);
+    rc = mods_verify_tentatives_wh(m->dev[0], par, joint.tent.data(), joint.u6.data(), joint.laf.data(), (int)joint.size(), (w1 + w2) / 2,
+                                   (h1 + h2) / 2, &res->n_unique, &res->n_inliers, res->H, stats, gt3, &ms_dup, &ms_ran);
     if (rc) return rc;
     res->ms_duplicates += ms_dup; res->ms_ransac += ms_ran;
     res->ransac_samples = stats[0]; res->ransac_lo = stats[1]; res->ransac_rejects = stats[2];
@@ -443,11 +427,7 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
                    : (par->ransac.ransacForStopping ? res->gt_ransac_inliers : (par->dup_before_ransac ? res->gt_true : res->n_inliers));
     res->steps_done = step + 1;
   }
-  if (matches_out)
-    for (int i = 0; i < res->n_inliers && i < max_matches; i++) {
-      const double *p = &u6[(size_t)i * 6];
-      matches_out[4 * i] = p[0]; matches_out[4 * i + 1] = p[1]; matches_out[4 * i + 2] = p[3]; matches_out[4 * i + 3] = p[4];
-    }
+  joint.copy_matches(res->n_inliers, matches_out, max_matches);
   return MODS_OK;
 }
 

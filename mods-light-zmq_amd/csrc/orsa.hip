@@ -187,7 +187,6 @@ static OrsaGpu *orsa_gpu() {
 }
 
 static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e && *e ? atoi(e) : dflt; }
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // ---- scoring back ends -----------------------------------------------------------------------------------------------------
 

@@ -20,17 +20,6 @@
 #include <set>
 #include <tuple>
 
-extern "C" int mods_ctx_create_ex(int device, int max_w, int max_h, int batch, int flags, mods_ctx **out);
-extern "C" int mods_pair_gpu_stage(mods_ctx *c, const float *img_dev, int w, int h, int stride, const mods_pair_params *par,
-                                   mods_pair_result *res, std::vector<mods_tentative> *tent, std::vector<double> *u6,
-                                   std::vector<double> *laf);
-extern "C" int mods_pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds, int n_pairs, int w, int h, const mods_pair_params *par,
-                                    mods_pair_result **res, std::vector<mods_tentative> **tent, std::vector<double> **u6,
-                                    std::vector<double> **laf);
-extern "C" int mods_pair_verify_stage(int device, const mods_pair_params *par, mods_pair_result *res, std::vector<mods_tentative> *tent,
-                                      std::vector<double> *u6, std::vector<double> *laf, double *matches_out, int max_matches,
-                                      int w, int h);
-
 namespace mods {
 
 struct Job {
@@ -38,8 +27,7 @@ struct Job {
   const void *img = nullptr;
   int kind = 0;                   // 0 fp32 in HBM, 1 fp32 on the host, 2 8-bit grey on the host
   mods_pair_result res;
-  std::vector<mods_tentative> tent;
-  std::vector<double> u6, laf;
+  TentList list;
   int rc = MODS_OK;
   std::string err;
   bool done = false;
@@ -70,9 +58,6 @@ struct mods_pipeline {
 static long long thread_cpu_ns() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (long long)ts.tv_sec * 1000000000ll + ts.tv_nsec; }
 
 using namespace mods;
-
-extern "C" int mods_ransac_warmup(int device, int len);
-extern "C" int mods_ctx_warmup(mods_ctx *c, int n_img, int w, int h, const mods_pair_params *par);
 
 static void worker_ready(mods_pipeline *p, int rc) {
   {
@@ -115,11 +100,10 @@ static void gpu_worker(mods_pipeline *p, mods_ctx *ctx) {
     std::vector<const void *> imgs(n);
     std::vector<int> kinds(n);
     std::vector<mods_pair_result *> res(n);
-    std::vector<std::vector<mods_tentative> *> tent(n);
-    std::vector<std::vector<double> *> u6(n), laf(n);
-    for (int i = 0; i < n; i++) { imgs[i] = js[i]->img; kinds[i] = js[i]->kind; res[i] = &js[i]->res; tent[i] = &js[i]->tent; u6[i] = &js[i]->u6; laf[i] = &js[i]->laf; }
+    std::vector<TentList *> lists(n);
+    for (int i = 0; i < n; i++) { imgs[i] = js[i]->img; kinds[i] = js[i]->kind; res[i] = &js[i]->res; lists[i] = &js[i]->list; }
     const long long c0 = thread_cpu_ns();
-    const int rc = mods_pairs_gpu_stage(ctx, imgs.data(), kinds.data(), n, p->w, p->h, &p->par, res.data(), tent.data(), u6.data(), laf.data());
+    const int rc = pairs_gpu_stage(ctx, imgs.data(), kinds.data(), n, p->w, p->h, &p->par, res.data(), lists.data());
     p->cpu_gpu_ns.fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed);
     const std::string err = rc ? mods_last_error() : "";
     {
@@ -145,7 +129,7 @@ static void verify_worker(mods_pipeline *p) {
     }
     if (j->rc == MODS_OK) {
       const long long c0 = thread_cpu_ns();
-      j->rc = mods_pair_verify_stage(p->device, &p->par, &j->res, &j->tent, &j->u6, &j->laf, nullptr, 0, p->w, p->h);
+      j->rc = pair_verify_stage(p->device, &p->par, &j->res, &j->list, nullptr, 0, p->w, p->h);
       p->cpu_verify_ns.fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed);
       if (j->rc) j->err = mods_last_error();
     }
@@ -164,9 +148,6 @@ static void verify_worker(mods_pipeline *p) {
 // workers' contexts below - so the watch is gone: docs/history/r05_removed_paths.patch.)
 
 extern "C" {
-
-int mods_pipeline_create_ex(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
-                            int pairs_per_batch, mods_pipeline **out);
 
 int mods_pipeline_create(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
                          mods_pipeline **out) {
@@ -315,11 +296,7 @@ int mods_pipeline_next_matches(mods_pipeline *p, mods_pair_result *res, long *ta
   if (tag) *tag = j->tag;
   if (j->rc) set_error("%s", j->err.c_str());
   // the verify stage leaves the verified correspondences in the first n_inliers rows of the job's list
-  if (!j->rc && matches_out)
-    for (int m = 0; m < j->res.n_inliers && m < max_matches && (size_t)m * 6 + 5 < j->u6.size(); m++) {
-      const double *q = &j->u6[(size_t)m * 6];
-      matches_out[4 * m] = q[0]; matches_out[4 * m + 1] = q[1]; matches_out[4 * m + 2] = q[3]; matches_out[4 * m + 3] = q[4];
-    }
+  if (!j->rc) j->list.copy_matches(j->res.n_inliers, matches_out, max_matches);
   return j->rc;
 }
 
