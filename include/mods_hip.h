@@ -150,6 +150,13 @@ int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
    mods_ctx_graph_replays: calls served by a replay so far. */
 int mods_ctx_graphs(mods_ctx *ctx, int on);
 long mods_ctx_graph_replays(const mods_ctx *ctx);
+/* detect + describe calls of the context so far whose orientation and description had the batch's 8-bit images to sample from
+   (mods_detect_describe_dev_u8 with packed rows; the pair pipeline's batches of 8-bit pairs, warm-up included) */
+long mods_ctx_u8_source_calls(const mods_ctx *ctx);
+/* which kernels sample from the 8-bit images in such calls: bit 0 orient_kernel, 1 extract_small_kernel, 2 big_fused_kernel,
+   3 big_sample_kernel; mask < 0 (the default): the library's measured choice (extract_small and big_fused).  Every choice gives the
+   same regions; the tests use it to run the forms the default leaves out. */
+int mods_ctx_u8_kernels(mods_ctx *ctx, int mask);
 /* Streams the Hessian scale space of a large batch is built on: 2 (default) = the octaves from the third on, and their non-maximum
    suppression, run on a side stream next to the large octaves' last level and NMS; 1 = everything on the context's stream (what
    per-launch timing wants).  The planes and the candidates are the same either way. */
@@ -224,6 +231,13 @@ int mods_orient_describe(mods_ctx *ctx, const float *img, int w, int h, int stri
 int mods_detect_describe_dev(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, int stride,
                              const mods_hessaff_params *det, const mods_describe_params *desc,
                              int *n_detected_host, int *n_regions_host);
+/* the same for a batch that is 8-bit grey in HBM ([n_img][h][stride] bytes, the form images have on disk): converted exactly to fp32
+ * inside the context for the scale space and the detector, while orientation and description sample the 8-bit images themselves
+ * (which kernels do: DESIGN.md section 4, "Sampling from the 8-bit twin") - the same regions to the bit.
+ * img_u8_dev must stay unchanged until the call returns. */
+int mods_detect_describe_dev_u8(mods_ctx *ctx, const unsigned char *img_u8_dev, int n_img, int w, int h, int stride,
+                                const mods_hessaff_params *det, const mods_describe_params *desc,
+                                int *n_detected_host, int *n_regions_host);
 /* External descriptors (reference: the "ZMQ" descriptor, DescribeWithZmq, imagerepresentation.cpp:21-103, 992-1006).  While
  * a function is set, the describe stage extracts ExtractPatchesColumn's patches (patchSize x patchSize at mrSize, fp32, no
  * photometric normalisation) and hands them to it; the function returns 128 values per patch (0..255, integer valued, as
@@ -718,6 +732,7 @@ int mods_pipeline_capacity(const mods_pipeline *p);    /* pairs that may be in f
 /* HIP-event timing of the workers' contexts (sums over them); enable/read while nothing is in flight */
 int mods_pipeline_timing_enable(mods_pipeline *p, int stage_mask);
 int mods_pipeline_timing_read(mods_pipeline *p, int stage, double *total_ms, int *launches, double *bytes);
+long mods_pipeline_u8_source_calls(mods_pipeline *p);   /* sum of mods_ctx_u8_source_calls over the GPU workers' contexts */
 long mods_pipeline_graph_replays(mods_pipeline *p);   /* batches whose detect + describe chain was a graph replay (mods_ctx_graphs) */
 /* CPU seconds the GPU workers' / the verify workers' own threads have spent inside their stages since the last reset (thread clocks;
    the RANSAC task pool's helper threads are not in them).  What a pair costs the host: needed to size ranks per node. */

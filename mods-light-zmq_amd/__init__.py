@@ -392,6 +392,22 @@ class Context:
         _check(lib().mods_detect_describe_dev(self.h, C.c_void_p(dev_ptr), n_img, w, h, w, C.byref(det), C.byref(desc), nd, nr))
         return list(nd), list(nr)
 
+    def u8_source_calls(self):
+        lib().mods_ctx_u8_source_calls.restype = C.c_long
+        return int(lib().mods_ctx_u8_source_calls(self.h))
+
+    def set_u8_kernels(self, mask):
+        """bit 0 orient, 1 extract_small, 2 big_fused, 3 big_sample sample from the 8-bit images in detect_describe_dev_u8; -1: default"""
+        _check(lib().mods_ctx_u8_kernels(self.h, int(mask)))
+
+    def detect_describe_dev_u8(self, dev_ptr, n_img, w, h, det=None, desc=None):
+        """detect_describe_dev for a batch of 8-bit grey images [n_img][h][w] in HBM: the same regions, sampled from the 8-bit images."""
+        det = det or HessAffParams.default()
+        desc = desc or DescribeParams.default()
+        nd, nr = (C.c_int * n_img)(), (C.c_int * n_img)()
+        _check(lib().mods_detect_describe_dev_u8(self.h, C.c_void_p(dev_ptr), n_img, w, h, w, C.byref(det), C.byref(desc), nd, nr))
+        return list(nd), list(nr)
+
     def regions_fetch(self, img, max_out=1 << 18):
         n = C.c_int()
         _check(lib().mods_regions_fetch(self.h, img, None, 0, C.byref(n)))
@@ -1149,6 +1165,11 @@ class Pipeline:
     def graph_replays(self):
         lib().mods_pipeline_graph_replays.restype = C.c_long
         return int(lib().mods_pipeline_graph_replays(self.h))
+
+    def u8_source_calls(self):
+        """batches (warm-up included) that were described from their staged 8-bit images"""
+        lib().mods_pipeline_u8_source_calls.restype = C.c_long
+        return int(lib().mods_pipeline_u8_source_calls(self.h))
 
     def cpu_seconds(self, reset=False):
         """(GPU workers, verify workers): CPU seconds their threads spent inside their stages since the last reset"""

@@ -440,7 +440,7 @@ static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, in
   const bool can = c->dd_graphs && c->timing_mask == 0 && !mods::has_hooks(c) && !mods::has_nets(c) && det->detectorType != MODS_DET_MSER;
   if (!can) { mods::dev_state_changed(c); return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc); }
   mods_ctx::DdKey key;
-  key.img = img_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
+  key.img = img_dev; key.img_u8 = c->img_u8_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
   key.par_hash = fnv1a(desc, sizeof(*desc), fnv1a(det, sizeof(*det), 1469598103934665603ull)) ^ (unsigned long long)c->pyr_streams;
   key.epoch = c->dev_state_epoch;
   // A recording is made, and replayed, only right behind a call with the SAME arguments: tables that live on the device and are
@@ -500,14 +500,17 @@ int mods_ctx_graphs(mods_ctx *c, int on) {
   return MODS_OK;
 }
 long mods_ctx_graph_replays(const mods_ctx *c) { return c ? c->dd_replays : 0; }
+long mods_ctx_u8_source_calls(const mods_ctx *c) { return c ? c->u8_source_calls : 0; }
+int mods_ctx_u8_kernels(mods_ctx *c, int mask) {
+  if (!c || mask > 15) { set_error("u8_kernels: bad argument"); return MODS_E_ARG; }
+  c->u8_kernels = mask < 0 ? -1 : mask;
+  mods::dev_state_changed(c);            // (a recorded detect + describe graph holds the other form's launches)
+  return MODS_OK;
+}
 
-int mods_detect_describe_dev(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride,
-                             const mods_hessaff_params *det, const mods_describe_params *desc, int *n_detected_host,
-                             int *n_regions_host) {
-  if (!c || !img_dev || !det || !desc) { set_error("detect_describe: null argument"); return MODS_E_ARG; }
-  if (w <= 0 || h <= 0 || (size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("detect_describe: image larger than the context"); return MODS_E_ARG; }
-  if (stride < w) { set_error("detect_describe: stride %d < width %d", stride, w); return MODS_E_ARG; }
-  MODS_HIP_CHECK(hipSetDevice(c->device));
+// the call behind both detect + describe entry points; c->img_u8_dev: the 8-bit twin of img_dev for this call, or nullptr
+static int dd_call(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
+                   const mods_describe_params *desc, int *n_detected_host, int *n_regions_host) {
   int rc;
   if ((rc = dd_run(c, img_dev, n_img, w, h, stride, det, desc))) return rc;
   int *hc = c->host_counts;
@@ -526,6 +529,39 @@ int mods_detect_describe_dev(mods_ctx *c, const float *img_dev, int n_img, int w
     return MODS_E_CAPACITY;
   }
   return MODS_OK;
+}
+
+int mods_detect_describe_dev(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride,
+                             const mods_hessaff_params *det, const mods_describe_params *desc, int *n_detected_host,
+                             int *n_regions_host) {
+  if (!c || !img_dev || !det || !desc) { set_error("detect_describe: null argument"); return MODS_E_ARG; }
+  if (w <= 0 || h <= 0 || (size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("detect_describe: image larger than the context"); return MODS_E_ARG; }
+  if (n_img < 1 || n_img > c->batch) { set_error("detect_describe: %d images, context batch %d", n_img, c->batch); return MODS_E_ARG; }
+  if (stride < w) { set_error("detect_describe: stride %d < width %d", stride, w); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  c->img_u8_dev = nullptr;
+  return dd_call(c, img_dev, n_img, w, h, stride, det, desc, n_detected_host, n_regions_host);
+}
+
+// 8-bit grey in HBM: converted (exactly) into input_dev, from which the scale space is built and the keypoints are detected as in
+// mods_detect_describe_dev; orientation and description sample from the 8-bit images themselves in the kernels whose switch is on
+// (describe_common.hpp) - (float)u8 at the load gives the fp32 copy's values, so the regions are the same to the bit.
+// Rows that are not packed (stride != w) and the MSER detector take the fp32 copy throughout.
+int mods_detect_describe_dev_u8(mods_ctx *c, const unsigned char *img_u8_dev, int n_img, int w, int h, int stride,
+                                const mods_hessaff_params *det, const mods_describe_params *desc, int *n_detected_host,
+                                int *n_regions_host) {
+  if (!c || !img_u8_dev || !det || !desc) { set_error("detect_describe_u8: null argument"); return MODS_E_ARG; }
+  if (w <= 0 || h <= 0 || (size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("detect_describe_u8: image larger than the context"); return MODS_E_ARG; }
+  if (n_img < 1 || n_img > c->batch) { set_error("detect_describe_u8: %d images, context batch %d", n_img, c->batch); return MODS_E_ARG; }
+  if (stride < w) { set_error("detect_describe_u8: stride %d < width %d", stride, w); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = mods::u8_to_f32_launch(c, img_u8_dev, n_img, w, h, stride, c->input_dev))) return rc;
+  c->img_u8_dev = (stride == w && det->detectorType != MODS_DET_MSER) ? img_u8_dev : nullptr;
+  if (c->img_u8_dev) c->u8_source_calls++;
+  rc = dd_call(c, c->input_dev, n_img, w, h, w, det, desc, n_detected_host, n_regions_host);
+  c->img_u8_dev = nullptr;
+  return rc;
 }
 
 // Route the description of every following call through `fn` (NULL: back to the built-in RootSIFT).  The patches are

@@ -205,6 +205,11 @@ struct mods_ctx {
   int *key_count = nullptr;          // [batch]
   int *host_counts = nullptr;        // pinned
   unsigned char *u8_stage_dev = nullptr;   // [batch][max_h][max_w] staging of 8-bit host images (pair pipeline), lazily allocated
+  // the 8-bit twin [n_img][h][w] of the fp32 images of the detect + describe call in progress (mods_detect_describe_dev_u8), read by
+  // describe_run_view; nullptr outside such a call
+  const unsigned char *img_u8_dev = nullptr;
+  int u8_kernels = -1;                   // which kernels sample from the twin: -1 = the build's choice (describe_common.hpp), else a mask
+  long u8_source_calls = 0;              // detect + describe calls that had such a twin (mods_ctx_u8_source_calls)
   // CLAHE (clahe.hip): LUT scratch [n_img][tiles_y * tiles_x][256] (clahe_reserve); clahe_on: the pair pipeline's 8-bit batches are
   // equalised with clahe_par on their way to fp32 (mods_pipeline_create_clahe)
   unsigned char *clahe_lut = nullptr; size_t clahe_lut_cap = 0;
@@ -282,8 +287,9 @@ struct mods_ctx {
   bool dd_graphs = false;
   // `epoch` = dev_state_epoch when the call was made: every host-side change of device tables or pools bumps that counter
   // (mods::dev_state_changed / dev_pool_reallocated), so a call behind such a change is never taken for a repeat of the one before it
-  struct DdKey { const float *img = nullptr; int n_img = 0, w = 0, h = 0, stride = 0; unsigned long long par_hash = 0, epoch = ~0ull;
-                 bool operator==(const DdKey &o) const { return img == o.img && n_img == o.n_img && w == o.w && h == o.h && stride == o.stride && par_hash == o.par_hash && epoch == o.epoch; } };
+  struct DdKey { const float *img = nullptr; const unsigned char *img_u8 = nullptr;     // img_u8: the call's 8-bit sampling source, or nullptr
+                 int n_img = 0, w = 0, h = 0, stride = 0; unsigned long long par_hash = 0, epoch = ~0ull;
+                 bool operator==(const DdKey &o) const { return img == o.img && img_u8 == o.img_u8 && n_img == o.n_img && w == o.w && h == o.h && stride == o.stride && par_hash == o.par_hash && epoch == o.epoch; } };
   unsigned long long dev_state_epoch = 0;
   std::vector<std::pair<DdKey, hipGraphExec_t>> dd_cache;   // recorded calls (a worker sees a few batch sizes), oldest first
   bool dd_stale = false;                                    // a pool the recordings point into was reallocated: they are dropped
@@ -356,6 +362,7 @@ int ransac_profile_mode();    // 0 off, 1 wall time, 2 the calling thread's CPU 
 
 // describe.hip
 int describe_run(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par);
+int u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst);     // pair.hip
 int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev);
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par);

@@ -180,7 +180,8 @@ __device__ bool dominant_angle_wave(float *s_patch, const float *__restrict__ vo
 #ifndef ORIENT_WAVES
 #define ORIENT_WAVES 4
 #endif
-__global__ __launch_bounds__(64, ORIENT_WAVES) void orient_kernel(const float *__restrict__ img_all, DescConst k,
+template <class PX>
+__global__ __launch_bounds__(64, ORIENT_WAVES) void orient_kernel(const PX *__restrict__ img_all, DescConst k,
                                                     const mods_affkey *__restrict__ keys_all,
                                                     const int *__restrict__ key_count, const float *__restrict__ orimask,
                                                     OriOut *__restrict__ ori_all, OriOut *__restrict__ ori_multi) {
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(64, ORIENT_WAVES) void orient_kernel(const float *_
   float *s_hist = (float *)(s_bin + ori_key_bytes(ps) * nv);
   const int lane = threadIdx.x;
   const int b = blockIdx.y;
-  const float *img = img_all + (size_t)k.w * k.h * b;
+  const PX *img = img_all + (size_t)k.w * k.h * b;
   const mods_affkey *keys = keys_all + (size_t)b * k.max_cand;
   OriOut *ori = ori_all + (size_t)b * k.max_cand;
   int n = key_count[b];
@@ -823,6 +824,10 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
   k.max_bin = par->maxBinValue;
   k.patch_rule = par->fastExtraction ? 2 : 0;
   const bool external = ctx->ext_fn != nullptr || ctx->ext_net != nullptr;
+  // the call's 8-bit twin of img_dev (mods_detect_describe_dev_u8): the built-in orientation and description of an identity view
+  // sample from it; views and the external / network paths have fp32 only
+  const bool hooks = external || ctx->shape_fn || ctx->shape_net || ctx->ori_fn || ctx->ori_net;
+  const unsigned char *img_u8 = (!H && !hooks) ? ctx->img_u8_dev : nullptr;
   if (external && par->fastExtraction) { set_error("FastPatchExtraction with an external descriptor is not supported"); return MODS_E_ARG; }
   if (external) { k.desc_mr = ctx->ext_mr; k.desc_ps = ctx->ext_ps; k.photo = 0; k.patch_rule = 1; }
   int *key_count = ctx->cand_count + 2 * ctx->batch;
@@ -846,8 +851,12 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
         ctx->ori_multi_bytes = need;
       }
     }
-    hipLaunchKernelGGL(orient_kernel, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_dev, k, ctx->keys_dev, key_count,
-                       orimask, (OriOut *)ctx->ori_dev, (OriOut *)ctx->ori_multi_dev);
+    if (img_u8 && kernel_from_u8(ctx, U8K_ORIENT))
+      hipLaunchKernelGGL(orient_kernel<unsigned char>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_u8, k, ctx->keys_dev, key_count,
+                         orimask, (OriOut *)ctx->ori_dev, (OriOut *)ctx->ori_multi_dev);
+    else
+      hipLaunchKernelGGL(orient_kernel<float>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_dev, k, ctx->keys_dev, key_count,
+                         orimask, (OriOut *)ctx->ori_dev, (OriOut *)ctx->ori_multi_dev);
     if (k.ori_cap > 1)
       hipLaunchKernelGGL(compact_regions_multi_kernel, dim3(1, n_img), dim3(1024), 0, ctx->stream, k, ctx->keys_dev, key_count,
                          (const OriOut *)ctx->ori_dev, (const OriOut *)ctx->ori_multi_dev, ctx->regions_dev, ctx->region_count, ctx->inside_count);
@@ -856,7 +865,7 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
                          (const OriOut *)ctx->ori_dev, ctx->regions_dev, ctx->region_count, ctx->inside_count);
     MODS_HIP_CHECK(hipGetLastError());
   }
-  rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external);
+  rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8);
   if (rc) return rc;
   ctx->have_half = false;
   if (par->halfDesc && !external) {

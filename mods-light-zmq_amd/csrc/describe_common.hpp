@@ -39,9 +39,32 @@ struct SiftTab {           // precomputeBinsAndWeights, siftdesc.cpp:22-71 (host
   float w0[64], w1[64];    // stored as double in the reference but float valued
 };
 
-// sift.hip
+// The kernels that gather from the input image (orient_kernel, extract_small_kernel, big_fused_kernel, big_sample_kernel) exist for
+// fp32 and for 8-bit pixels.  A call that has the batch as 8-bit grey in HBM as well (mods_detect_describe_dev_u8) samples from that
+// copy in the kernels whose switch is 1: the same values from a quarter of the bytes.  Each kernel keeps the form that was faster at
+// the benchmark's 32-image batch ("Sampling from the 8-bit twin"; profiles/u8_sampling_*); times per batch:
+#ifndef ORIENT_FROM_U8
+#define ORIENT_FROM_U8 0          // 1.853 against 1.861 ms, run-to-run deviation 0.067: no gain, stays on fp32
+#endif
+#ifndef EXTRACT_SMALL_FROM_U8
+#define EXTRACT_SMALL_FROM_U8 1   // 3 x 0.985 against 3 x 1.036 ms
+#endif
+#ifndef BIG_FUSED_FROM_U8
+#define BIG_FUSED_FROM_U8 1       // 2.67 against 2.88 ms
+#endif
+#ifndef BIG_SAMPLE_FROM_U8
+#define BIG_SAMPLE_FROM_U8 0      // no region of the benchmark's images reaches this kernel (P2 > 1024): not measured, stays on fp32
+#endif
+// the same choice as a mask, and the one a context was given for its calls instead (mods_ctx_u8_kernels: the tests run the forms that
+// the defaults leave out)
+enum { U8K_ORIENT = 1, U8K_EXTRACT_SMALL = 2, U8K_BIG_FUSED = 4, U8K_BIG_SAMPLE = 8 };
+constexpr int kU8KernelsDefault = (ORIENT_FROM_U8 ? U8K_ORIENT : 0) | (EXTRACT_SMALL_FROM_U8 ? U8K_EXTRACT_SMALL : 0) |
+                                  (BIG_FUSED_FROM_U8 ? U8K_BIG_FUSED : 0) | (BIG_SAMPLE_FROM_U8 ? U8K_BIG_SAMPLE : 0);
+inline bool kernel_from_u8(const mods_ctx *ctx, int kernel) { return ((ctx->u8_kernels < 0 ? kU8KernelsDefault : ctx->u8_kernels) & kernel) != 0; }
+
+// sift.hip.  img_u8: the same images [n_img][h][w] as 8-bit grey, or nullptr
 int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab,
-                            bool run_sift = true);
+                            bool run_sift = true, const unsigned char *img_u8 = nullptr);
 // HalfRootSIFT twins of the described regions: copies regions_dev to regions_half_dev and overwrites the descriptors from the
 // patch store left by launch_extract_and_sift (block-per-region SIFT kernel)
 int launch_half_sift(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, const SiftTab *tab);

@@ -79,11 +79,21 @@ __device__ __forceinline__ float fast_sqrtf_any(float x) {
 // two horizontally adjacent pixels by one 8-byte load (only 4-byte aligned): a gather costs the memory pipeline per lane
 // and per instruction, so the four pixels of a bilinear tap are fetched with two loads
 struct __attribute__((packed, aligned(4))) PixPair { float a, b; };
+// the same pair of an 8-bit image (the input as it came from the host, before its exact conversion to fp32) by one 2-byte load at
+// any byte alignment (odd widths make odd row strides), converted at the load: (float)u8 is exact, so a tap gives the bits the
+// fp32 copy gives, from a quarter of the bytes behind L1 and L2
+struct __attribute__((packed, aligned(1))) PixPairU8 { unsigned char a, b; };
+__device__ __forceinline__ void pix_pair(const float *__restrict__ p, float &a, float &b) { const PixPair q = *(const PixPair *)p; a = q.a; b = q.b; }
+__device__ __forceinline__ void pix_pair(const unsigned char *__restrict__ p, float &a, float &b) {
+  const PixPairU8 q = *(const PixPairU8 *)p;
+  a = (float)q.a; b = (float)q.b;
+}
 
 // The four pixels of one bilinear tap, loaded without combining them (lets a caller issue the loads
 // of several taps before the first use).  valid = false: the tap is 0 (checked branch, outside).
 struct TapLoads { float r00, r01, r10, r11, wx, wy; bool valid; };
-__device__ __forceinline__ TapLoads tap_load(const float *__restrict__ im, int w, int h, float WX, float WY, bool touch) {
+template <class PX>
+__device__ __forceinline__ TapLoads tap_load(const PX *__restrict__ im, int w, int h, float WX, float WY, bool touch) {
   TapLoads t;
   int x, y;
   if (!touch) { x = (int)WX; y = (int)WY; t.valid = true; }
@@ -91,9 +101,8 @@ __device__ __forceinline__ TapLoads tap_load(const float *__restrict__ im, int w
   t.wx = WX - (float)x;
   t.wy = WY - (float)y;
   if (t.valid) {
-    const float *Row0 = im + (size_t)y * w + x;
-    const PixPair p0 = *(const PixPair *)Row0, p1 = *(const PixPair *)(Row0 + w);
-    t.r00 = p0.a; t.r01 = p0.b; t.r10 = p1.a; t.r11 = p1.b;
+    const PX *Row0 = im + (size_t)y * w + x;
+    pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + w, t.r10, t.r11);
   } else { t.r00 = t.r01 = t.r10 = t.r11 = 0.f; }
   return t;
 }
@@ -102,16 +111,16 @@ __device__ __forceinline__ TapLoads tap_load(const float *__restrict__ im, int w
 // every tap's loads before it starts the next one (s_waitcnt vmcnt(0) in front of each conditional block: 25-35 thousand cycles
 // per Baumberg iteration went into 12 serial round trips).  floorf == the unchecked branch's (int) cast there: coordinates of
 // an untouched window are >= 1.
-__device__ __forceinline__ TapLoads tap_load_bf(const float *__restrict__ im, int w, int h, float WX, float WY, bool touch) {
+template <class PX>
+__device__ __forceinline__ TapLoads tap_load_bf(const PX *__restrict__ im, int w, int h, float WX, float WY, bool touch) {
   TapLoads t;
   const int x = (int)floorf(WX), y = (int)floorf(WY);
   t.valid = !touch || (WX >= 0 && WY >= 0 && x < w - 1 && y < h - 1);
   t.wx = WX - (float)x;
   t.wy = WY - (float)y;
   const int xc = min(max(x, 0), w - 2), yc = min(max(y, 0), h - 2);
-  const float *Row0 = im + (unsigned)(__mul24(yc, w) + xc);
-  const PixPair p0 = *(const PixPair *)Row0, p1 = *(const PixPair *)(Row0 + w);
-  t.r00 = p0.a; t.r01 = p0.b; t.r10 = p1.a; t.r11 = p1.b;
+  const PX *Row0 = im + (unsigned)(__mul24(yc, w) + xc);
+  pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + w, t.r10, t.r11);
   return t;
 }
 __device__ __forceinline__ float tap_combine(const TapLoads &t) {
@@ -124,19 +133,19 @@ __device__ __forceinline__ float tap_combine(const TapLoads &t) {
 // no border test, no clamp).  That covers the window's own samples only: a lane of a partly filled tile whose sample lies beyond
 // the window's edge (`inwin` false; its value is never stored) reads pixel 0 instead.  A third of the VALU work of the checked form
 // (tap_load_bf: two floors, four clamps, four compares - all half-rate instructions on gfx950 - go away).
-__device__ __forceinline__ TapLoads tap_load_inside(const float *__restrict__ im, int w, float WX, float WY, bool inwin) {
+template <class PX>
+__device__ __forceinline__ TapLoads tap_load_inside(const PX *__restrict__ im, int w, float WX, float WY, bool inwin) {
   TapLoads t;
   const int x = (int)WX, y = (int)WY;
   t.valid = true;
   t.wx = WX - (float)x;
   t.wy = WY - (float)y;
-  const float *Row0 = im + (inwin ? (unsigned)(__mul24(y, w) + x) : 0u);
-  const PixPair p0 = *(const PixPair *)Row0, p1 = *(const PixPair *)(Row0 + w);
-  t.r00 = p0.a; t.r01 = p0.b; t.r10 = p1.a; t.r11 = p1.b;
+  const PX *Row0 = im + (inwin ? (unsigned)(__mul24(y, w) + x) : 0u);
+  pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + w, t.r10, t.r11);
   return t;
 }
-template <bool TOUCH>
-__device__ __forceinline__ TapLoads tap_load_t(const float *__restrict__ im, int w, int h, float WX, float WY, bool inwin) {
+template <bool TOUCH, class PX>
+__device__ __forceinline__ TapLoads tap_load_t(const PX *__restrict__ im, int w, int h, float WX, float WY, bool inwin) {
   if (TOUCH) return tap_load_bf(im, w, h, WX, WY, true);
   return tap_load_inside(im, w, WX, WY, inwin);
 }
@@ -155,8 +164,9 @@ template <bool TOUCH> __device__ __forceinline__ float tap_combine_t(const TapLo
 // store(row, col, value) is called for every sample of the window.
 // The rows [row_begin, row_end) of the window are sampled (all columns).  TOUCH = whether the window touches the image border
 // (interpolateCheckBorders): the same for every lane, so the two forms of the tap are two instantiations behind one scalar branch.
-template <bool WIDE, bool TOUCH, class Store>
-__device__ __forceinline__ void sample_tiles_rows_t(const float *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
+// PX = float or unsigned char: the pixel type of the image (pix_pair).
+template <bool WIDE, bool TOUCH, class PX, class Store>
+__device__ __forceinline__ void sample_tiles_rows_t(const PX *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
                                                     float a21, float a22, int n, int row_begin, int row_end, int wv, int nw, Store store) {
   // tile = TC columns x TR rows of neighbouring samples (round 6 measured 4 x 16 tiles - half the column steps between a lane's taps,
   // twice the image rows per gather: no change in any kernel, profiles/r06_describe_experiments.log)
@@ -223,16 +233,16 @@ __device__ __forceinline__ void sample_tiles_rows_t(const float *__restrict__ im
     for (int q = nw * TR; q > 0; q--) { rx += a12; ry += a22; }
   }
 }
-template <bool WIDE, class Store>
-__device__ __forceinline__ void sample_tiles_rows(const float *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
+template <bool WIDE, class PX, class Store>
+__device__ __forceinline__ void sample_tiles_rows(const PX *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
                                                   float a21, float a22, int n, int row_begin, int row_end, int wv, int nw, Store store) {
   // (every lane evaluates the same expression: the first lane's value makes the branch a scalar one)
   const bool touch = __builtin_amdgcn_readfirstlane((int)check_borders(w, h, fx, fy, a11, a12, a21, a22, n, n)) != 0;
   if (touch) sample_tiles_rows_t<WIDE, true>(img, w, h, fx, fy, a11, a12, a21, a22, n, row_begin, row_end, wv, nw, store);
   else sample_tiles_rows_t<WIDE, false>(img, w, h, fx, fy, a11, a12, a21, a22, n, row_begin, row_end, wv, nw, store);
 }
-template <class Store>
-__device__ __forceinline__ void sample_tiles(const float *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
+template <class PX, class Store>
+__device__ __forceinline__ void sample_tiles(const PX *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
                                              float a21, float a22, int n, int wv, int nw, Store store) {
   sample_tiles_rows<false>(img, w, h, fx, fy, a11, a12, a21, a22, n, 0, n, wv, nw, store);
 }

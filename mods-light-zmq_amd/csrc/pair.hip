@@ -28,11 +28,31 @@ static DupJob single_pair_dup_job(mods_ctx *c) {
 constexpr size_t kPinArena = (size_t)24 << 20;   // pinned staging of a batch's tentative lists
 
 // 8-bit grey -> float (the ImageRepresentation constructor's convertTo(CV_32F), imagerepresentation.cpp:293-302): exact
-extern "C" __global__ __launch_bounds__(256) void u8_to_f32_kernel(const unsigned char *__restrict__ src, float *__restrict__ dst, size_t n4) {
+// n4 groups of four pixels (src 4-byte, dst 16-byte aligned), then the pixels 4 n4 .. n - 1 one by one
+extern "C" __global__ __launch_bounds__(256) void u8_to_f32_kernel(const unsigned char *__restrict__ src, float *__restrict__ dst, size_t n4,
+                                                                   size_t n) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const uchar4 v = ((const uchar4 *)src)[i];
     ((float4 *)dst)[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
   }
+  for (size_t i = 4 * n4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = (float)src[i];
+}
+// the same for rows of w pixels `stride` bytes apart, packed on the way
+extern "C" __global__ __launch_bounds__(256) void u8_rows_to_f32_kernel(const unsigned char *__restrict__ src, size_t stride, size_t w, size_t rows,
+                                                                        float *__restrict__ dst) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < rows * w; i += (size_t)gridDim.x * 256) dst[i] = (float)src[(i / w) * stride + i % w];
+}
+// images [n_img][h][stride] of 8-bit grey in HBM -> fp32 [n_img][h][w]; any size, any alignment of src
+int mods::u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst) {
+  const size_t n = (size_t)n_img * w * h;
+  if (stride != w)
+    hipLaunchKernelGGL(u8_rows_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, (size_t)stride, (size_t)w, (size_t)n_img * h, dst);
+  else {
+    const bool vec = (((uintptr_t)src & 3) | ((uintptr_t)dst & 15)) == 0;
+    hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, dst, vec ? n / 4 : (size_t)0, n);
+  }
+  MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
 }
 
 // ---- the GPU half ------------------------------------------------------------------------------------------
@@ -94,6 +114,10 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
   // CLAHE pipeline (mods_pipeline_create_clahe): the 8-bit pairs are staged side by side and equalised in one LUT + one apply launch
   // over the batch's 2 n_pairs images, the apply launch writing fp32 into input_dev in the place of u8_to_f32_kernel
   const bool clahe = c->clahe_on;
+  // a batch of 8-bit pairs only (and no CLAHE, whose fp32 output is no 8-bit image): the staged 8-bit batch [n_img][h][w] is converted
+  // in one launch and stays the sampling source of orientation and description (mods_detect_describe_dev_u8)
+  bool all_u8 = !clahe && kinds != nullptr;
+  for (int i = 0; all_u8 && i < n_pairs; i++) all_u8 = kinds[i] == 2;
   for (int i = 0; i < n_pairs; i++) {
     memset(res[i], 0, sizeof(*res[i]));
     for (int q = 0; q < 9; q++) res[i]->H[q] = -1;
@@ -102,12 +126,12 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     if (kind == 2) {
       if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
       unsigned char *st = c->u8_stage_dev + plane2 * i;
-      if (!clahe && ((plane2 & 3) || ((uintptr_t)st & 3))) { set_error("match_pairs: 8-bit input needs w*h*2 divisible by 4"); return MODS_E_ARG; }
+      if (!clahe && !all_u8 && ((plane2 & 3) || ((uintptr_t)st & 3))) { set_error("match_pairs: 8-bit input needs w*h*2 divisible by 4"); return MODS_E_ARG; }
       // (reading page-locked host images from the conversion kernel itself - no staging copy - was measured: 610 against 636
       // pairs/s, the kernel's waves sit on PCIe reads; the copy engine path stays)
       MODS_HIP_CHECK(hipMemcpyAsync(st, img[i], plane2, hipMemcpyHostToDevice, c->stream));
       const unsigned char *src = st;
-      if (!clahe) hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, c->input_dev + plane2 * i, plane2 / 4);
+      if (!clahe && !all_u8) hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, c->input_dev + plane2 * i, plane2 / 4, plane2);
     } else {
       MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev + plane2 * i, img[i], sizeof(float) * plane2,
                                     kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
@@ -119,7 +143,9 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
   // (queued ahead of the detect stage's scope: no MODS_STAGE_* bracket includes these two launches, rocprofv3 shows their time)
   if (clahe && (rc = clahe_launch(c, c->u8_stage_dev, n_img, w, h, w, &c->clahe_par, c->input_dev, w, 1))) return rc;
   const double t0 = now_ms();
-  if ((rc = mods_detect_describe_dev(c, c->input_dev, n_img, w, h, w, &par->det, &par->desc, nd.data(), nr.data()))) return rc;
+  if (all_u8) rc = mods_detect_describe_dev_u8(c, c->u8_stage_dev, n_img, w, h, w, &par->det, &par->desc, nd.data(), nr.data());
+  else rc = mods_detect_describe_dev(c, c->input_dev, n_img, w, h, w, &par->det, &par->desc, nd.data(), nr.data());
+  if (rc) return rc;
   const double t1 = now_ms();
   // The tentative lists of the batch go to the host through a pinned arena: the packed list of a pair (tentatives |
   // correspondences | frames) is ONE transfer queued behind its match kernels, the stream is synchronised once per pair for the COUNT only (4 bytes) and once
@@ -282,6 +308,17 @@ int mods_ctx_warmup(mods_ctx *c, int n_img, int w, int h, const mods_pair_params
   std::vector<int> nd(n_img), nr(n_img);
   int rc = mods_detect_describe_dev(c, c->input_dev, n_img, w, h, w, &par->det, &par->desc, nd.data(), nr.data());
   if (rc) return rc;
+  // the same batch as 8-bit grey through the 8-bit entry point: a pipeline's 8-bit batches sample from the staged images, and the
+  // first use of those kernels must not load their code objects inside the running pipeline.  (Its regions differ from the fp32
+  // lattice's - the lattice is rounded - which does not matter to what follows.)  A CLAHE context never takes that path.
+  if (!c->clahe_on) {
+    std::vector<unsigned char> img8(plane);
+    for (size_t i = 0; i < plane; i++) img8[i] = (unsigned char)std::min(255.f, std::max(0.f, img[i] + 0.5f));
+    MODS_HIP_CHECK(mods::copy_wait(c->stream, c->u8_stage_dev, img8.data(), plane, hipMemcpyHostToDevice));
+    for (int i = 1; i < n_img; i++)
+      MODS_HIP_CHECK(hipMemcpyAsync(c->u8_stage_dev + plane * i, c->u8_stage_dev, plane, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = mods_detect_describe_dev_u8(c, c->u8_stage_dev, n_img, w, h, w, &par->det, &par->desc, nd.data(), nr.data()))) return rc;
+  }
   const int last = n_img - 1;
   if ((rc = match_ensure_buffers(c, std::min(16, std::max(1, n_img / 2))))) return rc;     // the searches of a batch's pairs run as one group
   if ((rc = match_run(c, c->regions_dev, nr[0], c->regions_dev + (size_t)last * c->max_cand, nr[last], par->fginn_ratio, par->contradDist, par->nn))) return rc;

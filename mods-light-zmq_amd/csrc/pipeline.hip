@@ -183,6 +183,11 @@ long mods_pipeline_graph_replays(mods_pipeline *p) {
   if (p) for (auto *c : p->ctxs) n += mods_ctx_graph_replays(c);
   return n;
 }
+long mods_pipeline_u8_source_calls(mods_pipeline *p) {
+  long n = 0;
+  if (p) for (auto *c : p->ctxs) n += mods_ctx_u8_source_calls(c);
+  return n;
+}
 
 // CPU seconds the GPU workers / the verify workers have spent inside their stages since the last reset (reset != 0 clears them)
 int mods_pipeline_cpu_seconds(mods_pipeline *p, double *gpu_workers_s, double *verify_workers_s, int reset) {

@@ -344,7 +344,8 @@ __device__ __forceinline__ void resample_full(const float *B, int P2, int ts, in
 // extract, LDS tier: direct branch and P2 <= SMALL_CAP.  grid = (N, n_img), block = 256.
 // dynamic LDS: S cap*odd4(cap) (transposed window, then the blurred window) | T cap*cap4 (row pass) | seq 2ps | cidx 2ps | taps 32 | red 2 doubles
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, ES_MINB) void extract_small_kernel(const float *__restrict__ img_all, DescConst k,
+template <class PX>
+__global__ __launch_bounds__(256, ES_MINB) void extract_small_kernel(const PX *__restrict__ img_all, DescConst k,
                                                             const mods_region *__restrict__ reg_all, const int *__restrict__ items,
                                                             const int *__restrict__ n_items_dev, int items_cap,
                                                             float *__restrict__ patches, const float *__restrict__ blur_table) {
@@ -367,7 +368,7 @@ __global__ __launch_bounds__(256, ES_MINB) void extract_small_kernel(const float
 #endif
   for (int it = blockIdx.x; it < n; it += gridDim.x) {
     const int code = items[it], b = code >> 17, ri = code & 0x1ffff;
-    const float *img = img_all + (size_t)k.w * k.h * b;
+    const PX *img = img_all + (size_t)k.w * k.h * b;
     const RegionGeom g = region_geom(reg_all[(size_t)b * k.max_reg + ri], k.desc_mr, ps, k.patch_rule);
     float *out = patches + ((size_t)b * k.reg_cap + ri) * pp;
     __syncthreads();
@@ -592,7 +593,8 @@ __global__ __launch_bounds__(256) void big_setup_kernel(DescConst k, const BigLi
 // samples a 4 x 4 block of the grid, i.e. a compact block of the image with few cache lines per gather.  The running coordinates of interpolate() (helpers.cpp:551-626) are a sequential fp32
 // recurrence: a lane replays the row steps up to its row and then advances its own copy four column steps per sample -
 // the same additions in the same order as the reference.
-__global__ __launch_bounds__(256) void big_sample_kernel(const float *__restrict__ img_all, DescConst k, const BigLists *__restrict__ bl,
+template <class PX>
+__global__ __launch_bounds__(256) void big_sample_kernel(const PX *__restrict__ img_all, DescConst k, const BigLists *__restrict__ bl,
                                                          const BigRegion *__restrict__ regions, const int2 *__restrict__ sitems,
                                                          int max_items, const mods_region *__restrict__ reg_all,
                                                          float *__restrict__ pool, const int *__restrict__ err_flag) {
@@ -603,7 +605,7 @@ __global__ __launch_bounds__(256) void big_sample_kernel(const float *__restrict
     const int2 item = sitems[it];
     const BigRegion br = regions[item.x];
     const RegionGeom g = region_geom(reg_all[(size_t)br.img * k.max_reg + br.ri], k.desc_mr, k.desc_ps, k.patch_rule);
-    const float *img = img_all + (size_t)k.w * k.h * br.img;
+    const PX *img = img_all + (size_t)k.w * k.h * br.img;
     const int P2 = br.P2, P2r = br.P2r, half = P2 / 2, w = k.w, h = k.h;
     const int row = item.y + 4 * (lane >> 4) + (lane & 3), s = (lane >> 2) & 3;
     if (row >= P2) continue;
@@ -616,7 +618,7 @@ __global__ __launch_bounds__(256) void big_sample_kernel(const float *__restrict
     for (int q = 0; q < s; q++) { WX += g.f11; WY += g.f21; }
     float *dst = pool + br.slab + big_hdr_floats(br.n_tap, k.desc_ps) + (size_t)s * P2r + row;
     for (int c = s; c < P2; c += 32, dst += (size_t)32 * P2r) {
-      PixPair t0[8], t1[8];
+      float a0[8], b0[8], a1[8], b1[8];       // the tap's pixel pairs of row y and row y + 1
       float wx[8], wy[8];
       bool ok[8];
 #pragma unroll
@@ -629,9 +631,9 @@ __global__ __launch_bounds__(256) void big_sample_kernel(const float *__restrict
           wx[u] = WX - (float)x;
           wy[u] = WY - (float)y;
           if (ok[u]) {
-            const float *Row0 = img + (size_t)y * w + x;
-            t0[u] = *(const PixPair *)Row0;
-            t1[u] = *(const PixPair *)(Row0 + w);
+            const PX *Row0 = img + (size_t)y * w + x;
+            pix_pair(Row0, a0[u], b0[u]);
+            pix_pair(Row0 + w, a1[u], b1[u]);
           }
           WX += g.f11; WY += g.f21; WX += g.f11; WY += g.f21; WX += g.f11; WY += g.f21; WX += g.f11; WY += g.f21;
         }
@@ -641,8 +643,8 @@ __global__ __launch_bounds__(256) void big_sample_kernel(const float *__restrict
         if (c + 4 * u < P2) {
           float v = 0.f;
           if (ok[u]) {
-            const float I1 = wx[u] * (t0[u].b - t0[u].a) + t0[u].a;
-            v = wy[u] * (wx[u] * (t1[u].b - t1[u].a) + t1[u].a - I1) + I1;
+            const float I1 = wx[u] * (b0[u] - a0[u]) + a0[u];
+            v = wy[u] * (wx[u] * (b1[u] - a1[u]) + a1[u] - I1) + I1;
           }
           dst[(size_t)4 * u * P2r] = v;
         }
@@ -752,7 +754,8 @@ __global__ __launch_bounds__(256) void big_rowpass_kernel(DescConst k, const Big
 //   phase 1  thread (row = tid % R, phase = tid / R) walks the coordinate recurrence of its row and samples the columns
 //            phase, phase + nph, ... (nph = 256 / R column steps between two of its samples)
 //   phase 2  as big_rowpass_kernel, float4 = 4 rows from LDS; wave w takes the pair groups w, w + 4, ...
-__global__ __launch_bounds__(256) void big_fused_kernel(const float *__restrict__ img_all, DescConst k, const BigLists *__restrict__ bl,
+template <class PX>
+__global__ __launch_bounds__(256) void big_fused_kernel(const PX *__restrict__ img_all, DescConst k, const BigLists *__restrict__ bl,
                                                         const BigRegion *__restrict__ regions, const int2 *__restrict__ fitems,
                                                         int max_items, const mods_region *__restrict__ reg_all,
                                                         float *__restrict__ pool, const int *__restrict__ err_flag) {
@@ -777,7 +780,7 @@ __global__ __launch_bounds__(256) void big_fused_kernel(const float *__restrict_
     const int2 item = fitems[it];
     const BigRegion br = regions[item.x];
     const RegionGeom g = region_geom(reg_all[(size_t)br.img * k.max_reg + br.ri], k.desc_mr, ps, k.patch_rule);
-    const float *img = img_all + (size_t)k.w * k.h * br.img;
+    const PX *img = img_all + (size_t)k.w * k.h * br.img;
     const int P2 = br.P2, w = k.w, h = k.h;
     const int R = big_fuse_rows(P2), r0 = item.y;
     __syncthreads();   // the previous item's row pass is done with the tile
@@ -1540,7 +1543,8 @@ __global__ __launch_bounds__(256) void sift_patch_test_kernel(const float *__res
 }
 
 // ---------------------------------------------------------------------------------------
-int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool run_sift) {
+int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool run_sift,
+                            const unsigned char *img_u8) {
   StageScope ts(ctx, MODS_STAGE_DESCRIBE);
   const int ps = k.desc_ps, ps2 = 2 * ps, pp = ps * ps;
   // HBM layout of the description scratch: patch store [n_img][reg_cap][ps*ps] | big-tier bookkeeping | slab pool
@@ -1589,17 +1593,30 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
       kt.p2_lo = tiers[t]; kt.p2_hi = tiers[t + 1];
       const size_t capS = kt.p2_hi > 4 ? kt.p2_hi : 4;
       const size_t ldsS = sizeof(float) * (capS * odd4((int)capS) + capS * ((capS + 3) & ~(size_t)3) + 2 * ps2 + 32) + 32;
-      hipLaunchKernelGGL(extract_small_kernel, dim3(4096), dim3(256), ldsS, ctx->stream, img_dev, kt, ctx->regions_dev,
-                         small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
-                         (const float *)ctx->blur_table_dev);
+      if (img_u8 && kernel_from_u8(ctx, U8K_EXTRACT_SMALL))
+        hipLaunchKernelGGL(extract_small_kernel<unsigned char>, dim3(4096), dim3(256), ldsS, ctx->stream, img_u8, kt, ctx->regions_dev,
+                           small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
+                           (const float *)ctx->blur_table_dev);
+      else
+        hipLaunchKernelGGL(extract_small_kernel<float>, dim3(4096), dim3(256), ldsS, ctx->stream, img_dev, kt, ctx->regions_dev,
+                           small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
+                           (const float *)ctx->blur_table_dev);
     }
   }
   const size_t ldsH = sizeof(float) * (k.tap_cap + 4 * ps2) + 32;
   hipLaunchKernelGGL(big_setup_kernel, dim3(1024), dim3(256), ldsH, ctx->stream, k, bl, bregs, max_big, pool, ctx->desc_err_dev);
-  hipLaunchKernelGGL(big_fused_kernel, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_dev, k, bl, bregs, fitems, max_items,
-                     ctx->regions_dev, pool, ctx->desc_err_dev);
-  hipLaunchKernelGGL(big_sample_kernel, dim3(4096), dim3(256), 0, ctx->stream, img_dev, k, bl, bregs, sitems, max_items,
-                     ctx->regions_dev, pool, ctx->desc_err_dev);
+  if (img_u8 && kernel_from_u8(ctx, U8K_BIG_FUSED))
+    hipLaunchKernelGGL(big_fused_kernel<unsigned char>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_u8, k, bl, bregs, fitems,
+                       max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
+  else
+    hipLaunchKernelGGL(big_fused_kernel<float>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_dev, k, bl, bregs, fitems,
+                       max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
+  if (img_u8 && kernel_from_u8(ctx, U8K_BIG_SAMPLE))
+    hipLaunchKernelGGL(big_sample_kernel<unsigned char>, dim3(4096), dim3(256), 0, ctx->stream, img_u8, k, bl, bregs, sitems, max_items,
+                       ctx->regions_dev, pool, ctx->desc_err_dev);
+  else
+    hipLaunchKernelGGL(big_sample_kernel<float>, dim3(4096), dim3(256), 0, ctx->stream, img_dev, k, bl, bregs, sitems, max_items,
+                       ctx->regions_dev, pool, ctx->desc_err_dev);
   hipLaunchKernelGGL(big_rowpass_kernel, dim3(4096), dim3(256), 0, ctx->stream, k, bl, bregs, ritems, max_items, pool,
                      ctx->desc_err_dev);
   hipLaunchKernelGGL(big_colres_kernel, dim3(4096), dim3(256), 0, ctx->stream, k, bl, bregs, max_big, pool, patches, ctx->desc_err_dev);
