@@ -151,7 +151,8 @@ int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 int mods_ctx_graphs(mods_ctx *ctx, int on);
 long mods_ctx_graph_replays(const mods_ctx *ctx);
 /* detect + describe calls of the context so far whose orientation and description had the batch's 8-bit images to sample from
-   (mods_detect_describe_dev_u8 with packed rows; the pair pipeline's batches of 8-bit pairs, warm-up included) */
+   (mods_detect_describe_dev_u8 with packed rows; mods_orient_describe_u8; the pair pipeline's batches of 8-bit pairs, warm-up
+   included) */
 long mods_ctx_u8_source_calls(const mods_ctx *ctx);
 /* which kernels sample from the 8-bit images in such calls: bit 0 orient_kernel, 1 extract_small_kernel, 2 big_fused_kernel,
    3 big_sample_kernel; mask < 0 (the default): the library's measured choice (extract_small and big_fused).  Every choice gives the
@@ -225,6 +226,14 @@ typedef struct mods_describe_params {
  * regions in input order (dropped ones removed). */
 int mods_orient_describe(mods_ctx *ctx, const float *img, int w, int h, int stride, const mods_affkey *keys,
                          int n_keys, const mods_describe_params *par, mods_region *out, int max_out, int *n_out);
+
+/* the same for an 8-bit grey host image (`stride` in bytes): converted exactly to fp32 inside the context, while orientation and
+ * description sample the 8-bit image itself in the kernels mods_ctx_u8_kernels selects - the same regions to the bit.  Counts in
+ * mods_ctx_u8_source_calls.  MODS_E_ARG, before any device call: a null pointer, stride < w, an image larger than the context,
+ * more keypoints than the context's candidate capacity (for which mods_orient_describe, the fp32 twin, answers MODS_E_CAPACITY
+ * after it has selected the device: here every refusal is an argument error and comes first). */
+int mods_orient_describe_u8(mods_ctx *ctx, const unsigned char *img_u8, int w, int h, int stride, const mods_affkey *keys,
+                            int n_keys, const mods_describe_params *par, mods_region *out, int max_out, int *n_out);
 
 /* detect + orient + describe for a batch of device-resident images; regions stay in HBM for the
  * matcher (mods_regions_fetch copies them out).  n_regions_host[i] = regions of image i. */

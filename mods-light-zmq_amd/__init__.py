@@ -378,6 +378,24 @@ class Context:
                                           len(k), C.byref(params), out.ctypes.data_as(C.c_void_p), max_out, C.byref(n)))
         return out[:n.value].copy()
 
+    def orient_describe_u8(self, img_u8, keys, params=None, max_out=None):
+        """orient_describe for an 8-bit grey image [h][w] (any row stride: a view with padded rows is passed as it is): the same
+        regions, sampled from the 8-bit image in the kernels set_u8_kernels selects."""
+        params = params or DescribeParams.default()
+        a = np.asarray(img_u8)
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("orient_describe_u8 takes a 2-d uint8 array")
+        if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+            a = np.ascontiguousarray(a)
+        k = np.ascontiguousarray(keys)
+        max_out = max_out or len(k) + 1
+        out = np.zeros(max_out, REGION_DTYPE)
+        n = C.c_int()
+        _check(lib().mods_orient_describe_u8(self.h, C.c_void_p(a.ctypes.data), a.shape[1], a.shape[0], a.strides[0],
+                                             k.ctypes.data_as(C.c_void_p), len(k), C.byref(params), out.ctypes.data_as(C.c_void_p),
+                                             max_out, C.byref(n)))
+        return out[:n.value].copy()
+
     def regions_fetch_half(self, img=0, max_out=1 << 18):
         """HalfRootSIFT twins of the regions of image slot img (desc[:64]; describe with DescribeParams.halfDesc = 1)."""
         out = np.zeros(max_out, REGION_DTYPE)
@@ -400,12 +418,14 @@ class Context:
         """bit 0 orient, 1 extract_small, 2 big_fused, 3 big_sample sample from the 8-bit images in detect_describe_dev_u8; -1: default"""
         _check(lib().mods_ctx_u8_kernels(self.h, int(mask)))
 
-    def detect_describe_dev_u8(self, dev_ptr, n_img, w, h, det=None, desc=None):
-        """detect_describe_dev for a batch of 8-bit grey images [n_img][h][w] in HBM: the same regions, sampled from the 8-bit images."""
+    def detect_describe_dev_u8(self, dev_ptr, n_img, w, h, det=None, desc=None, stride=None):
+        """detect_describe_dev for a batch of 8-bit grey images [n_img][h][stride] in HBM (stride in bytes, default w): the same regions,
+        sampled from the 8-bit images where the rows are packed, from their fp32 copy otherwise."""
         det = det or HessAffParams.default()
         desc = desc or DescribeParams.default()
         nd, nr = (C.c_int * n_img)(), (C.c_int * n_img)()
-        _check(lib().mods_detect_describe_dev_u8(self.h, C.c_void_p(dev_ptr), n_img, w, h, w, C.byref(det), C.byref(desc), nd, nr))
+        _check(lib().mods_detect_describe_dev_u8(self.h, C.c_void_p(dev_ptr), n_img, w, h, w if stride is None else int(stride),
+                                                 C.byref(det), C.byref(desc), nd, nr))
         return list(nd), list(nr)
 
     def regions_fetch(self, img, max_out=1 << 18):

@@ -685,6 +685,36 @@ int mods_orient_describe(mods_ctx *c, const float *img, int w, int h, int stride
   return check_desc_err(c);
 }
 
+// mods_orient_describe for an 8-bit grey host image: staged packed in u8_stage_dev, converted (exactly) into input_dev, and the 8-bit
+// copy is the call's sampling source in the kernels whose switch is on (mods_ctx_u8_kernels) - the given keypoints reach every size
+// class of those kernels, which the detector's own keypoints on an affordable image do not.  Everything that does not need the
+// context is checked first, so that a bad call is refused without a device.
+int mods_orient_describe_u8(mods_ctx *c, const unsigned char *img_u8, int w, int h, int stride, const mods_affkey *keys, int n_keys,
+                            const mods_describe_params *par, mods_region *out, int max_out, int *n_out) {
+  if (!img_u8 || !par || !n_out || (n_keys > 0 && !keys)) { set_error("orient_describe_u8: null argument"); return MODS_E_ARG; }
+  if (w < 1 || h < 1) { set_error("orient_describe_u8: image size %d x %d", w, h); return MODS_E_ARG; }
+  if (stride < w) { set_error("orient_describe_u8: stride %d < width %d", stride, w); return MODS_E_ARG; }
+  if (n_keys < 0) { set_error("orient_describe_u8: %d keypoints", n_keys); return MODS_E_ARG; }
+  if (!c) { set_error("orient_describe_u8: null context"); return MODS_E_ARG; }
+  if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("orient_describe_u8: image %d x %d larger than the context", w, h); return MODS_E_ARG; }
+  if (n_keys > c->max_cand) { set_error("orient_describe_u8: too many keypoints for the context: %d > %d", n_keys, c->max_cand); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = mods::u8_stage_ensure(c))) return rc;
+  MODS_HIP_CHECK(hipMemcpy2DAsync(c->u8_stage_dev, w, img_u8, stride, w, h, hipMemcpyHostToDevice, c->stream));
+  MODS_HIP_CHECK(hipMemcpyAsync(c->keys_dev, keys, sizeof(mods_affkey) * n_keys, hipMemcpyHostToDevice, c->stream));
+  MODS_HIP_CHECK(hipMemcpyAsync(c->cand_count + 2 * c->batch, &n_keys, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  MODS_HIP_CHECK(mods::stream_wait(c->stream));   // n_keys is a stack variable
+  if ((rc = mods::u8_to_f32_launch(c, c->u8_stage_dev, 1, w, h, w, c->input_dev))) return rc;
+  c->img_u8_dev = c->u8_stage_dev;
+  c->u8_source_calls++;
+  rc = describe_run(c, c->input_dev, 1, w, h, par);
+  c->img_u8_dev = nullptr;
+  if (rc) return rc;
+  if ((rc = mods_regions_fetch(c, 0, out, max_out, n_out))) return rc;
+  return check_desc_err(c);
+}
+
 int mods_dominant_angle(mods_ctx *c, const float *patch, int ps, double th, float *angle, int *found) {
   mods_describe_params dp = {5.1962, ps, 1, th, 5.1962, c->desc_ps ? c->desc_ps : 41, 1, 1, 0.2};
   MODS_HIP_CHECK(hipSetDevice(c->device));

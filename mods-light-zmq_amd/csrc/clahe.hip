@@ -273,7 +273,7 @@ int mods_clahe(mods_ctx *c, const unsigned char *src_host, int w, int h, const m
   int rc = clahe_check(c, src_host, dst_host, 1, w, h, w, w, par, "mods_clahe");
   if (rc) return rc;
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
+  if ((rc = mods::u8_stage_ensure(c))) return rc;
   if ((rc = clahe_reserve(c, 1, par))) return rc;
   const size_t bytes = (size_t)w * h;
   MODS_HIP_CHECK(mods::copy_wait(c->stream, c->u8_stage_dev, src_host, bytes, hipMemcpyHostToDevice));

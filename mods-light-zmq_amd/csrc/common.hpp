@@ -363,6 +363,7 @@ int ransac_profile_mode();    // 0 off, 1 wall time, 2 the calling thread's CPU 
 // describe.hip
 int describe_run(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par);
 int u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst);     // pair.hip
+int u8_stage_ensure(mods_ctx *c);          // pair.hip: c->u8_stage_dev allocated (a full batch of the context's largest images)
 int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev);
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par);

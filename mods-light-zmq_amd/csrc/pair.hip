@@ -42,6 +42,11 @@ extern "C" __global__ __launch_bounds__(256) void u8_rows_to_f32_kernel(const un
                                                                         float *__restrict__ dst) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < rows * w; i += (size_t)gridDim.x * 256) dst[i] = (float)src[(i / w) * stride + i % w];
 }
+// the context's staging area for 8-bit host images, allocated at its first use
+int mods::u8_stage_ensure(mods_ctx *c) {
+  if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
+  return MODS_OK;
+}
 // images [n_img][h][stride] of 8-bit grey in HBM -> fp32 [n_img][h][w]; any size, any alignment of src
 int mods::u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst) {
   const size_t n = (size_t)n_img * w * h;
@@ -124,7 +129,7 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     const int kind = kinds ? kinds[i] : 0;
     if (clahe && kind != 2) { set_error("match_pairs: a CLAHE pipeline takes 8-bit images only"); return MODS_E_ARG; }
     if (kind == 2) {
-      if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
+      if (int rc_stage = mods::u8_stage_ensure(c)) return rc_stage;
       unsigned char *st = c->u8_stage_dev + plane2 * i;
       if (!clahe && !all_u8 && ((plane2 & 3) || ((uintptr_t)st & 3))) { set_error("match_pairs: 8-bit input needs w*h*2 divisible by 4"); return MODS_E_ARG; }
       // (reading page-locked host images from the conversion kernel itself - no staging copy - was measured: 610 against 636
@@ -291,7 +296,7 @@ int mods_ctx_warmup(mods_ctx *c, int n_img, int w, int h, const mods_pair_params
   if (!c || !par || n_img < 1 || n_img > c->batch) { set_error("warmup: bad argument"); return MODS_E_ARG; }
   if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("warmup: image larger than the context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
+  if (int rc_stage = mods::u8_stage_ensure(c)) return rc_stage;
   if (!c->pin_arena) { MODS_HIP_CHECK(hipHostMalloc(&c->pin_arena, kPinArena)); c->pin_arena_cap = kPinArena; }
   std::vector<float> img((size_t)w * h);
   // blobs every 14 px on top of blobs every 90 px: some ten thousand regions of both patch tiers on a 2-megapixel image; on larger

@@ -102,6 +102,26 @@ def test_verification_without_a_device_is_an_error_not_an_abort(pkg):
             fn(u, None)
 
 
+BUF = C.c_void_p(0x1000)        # never dereferenced: every call below is refused before anything is read
+
+
+@pytest.mark.parametrize("kw,msg", [
+    (dict(img=None), b"null argument"), (dict(par=None), b"null argument"), (dict(n_out=None), b"null argument"),
+    (dict(keys=None), b"null argument"), (dict(w=0), b"image size 0 x 48"), (dict(h=-3), b"image size 64 x -3"),
+    (dict(stride=63), b"stride 63 < width 64"), (dict(n_keys=-1), b"-1 keypoints"), (dict(), b"null context"),
+    (dict(keys=None, n_keys=0), b"null context")])      # (no keys at all need no key array)
+def test_orient_describe_u8_argument_errors(pkg, kw, msg):
+    """mods_orient_describe_u8 refuses a bad call with MODS_E_ARG and a message before any device call - here without a device and
+    without a context (the two checks against the context's size: tests/test_gpu_describe_u8_keys.py)."""
+    lib = pkg.lib()
+    a = dict(img=BUF, w=64, h=48, stride=64, keys=BUF, n_keys=5, par=BUF, n_out=BUF)
+    a.update(kw)
+    rc = lib.mods_orient_describe_u8(None, a["img"], a["w"], a["h"], a["stride"], a["keys"], a["n_keys"], a["par"], BUF, 8, a["n_out"])
+    assert rc == -2
+    err = lib.mods_last_error()
+    assert err.startswith(b"orient_describe_u8: ") and msg in err, err
+
+
 def test_struct_layouts(pkg):
     assert pkg.REGION_DTYPE.itemsize == 208 and pkg.AFFKEY_DTYPE.itemsize == 88 and pkg.TENT_DTYPE.itemsize == 40
     assert orc.REGION_DTYPE == pkg.REGION_DTYPE and orc.TENT_DTYPE == pkg.TENT_DTYPE

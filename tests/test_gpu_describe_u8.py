@@ -46,8 +46,8 @@ def test_u8_entry_point_equals_fp32(pkg, kernels):
     row counts of big_fused_kernel), windows that touch the image border (the checked tap) and windows that do not (the unchecked
     one).  kernels = -1: the library's choice (extract_small_kernel and big_fused_kernel on the 8-bit images); 15: all four, which
     runs the 8-bit form of orient_kernel as well.  big_sample_kernel takes regions with P2 > 1024 only, which images of this size
-    cannot hold (the largest window here is 291 pixels wide): its 8-bit form - the same pix_pair load under the same template - is
-    launched with an empty work list and has never sampled a pixel on a GPU."""
+    cannot hold (the largest window here is 291 pixels wide): here it is launched with an empty work list; given keypoints reach
+    it, in both forms, in tests/test_gpu_describe_u8_keys.py."""
     import torch
     w, h = 481, 363
     a, b, _ = synth.pair(w, h, seed=7)
