@@ -521,6 +521,14 @@ unsigned mods_test_rfth(unsigned seed, const double *u, const unsigned char *hin
  * Returns the number of stable thresholds. */
 int mods_test_mser_grow(const unsigned char *img8, int w, int h, int min_size, double max_area, double min_margin, int invert,
                         int *out5, int max_out, int *tree_out);
+/* self-test hook of the owning buffer type (csrc/buffer.hpp; no device needed): runs it over a memory policy that counts and fails on a
+ * chosen allocation.  report (n >= 16): [0] calls made by a reserve below the capacity, [1] frees and [2] allocations of one growth,
+ * [3] 1 when a failed growth left get() == nullptr, [4] its capacity(), [5] frees during it, [6] allocations of the reserve that
+ * follows, [7] 1 when moves, swap and detach behaved, [8] buffers of a group left non-empty by a failed group reservation (summed
+ * over the failing position), [9] 1 when a group reservation succeeded with [10] buffers at their size, [11] frees of a pointer
+ * that was not live, [12] allocations alive after every buffer was destroyed, [13] allocations made, [14] frees made, [15] the
+ * group's size.  Returns the number of entries filled. */
+int mods_test_buffer_growth(int *report, int n);
 /* Host threads the degenerate branch of DEGENSAC spreads its independent pieces over (csrc/ransac_pool.hpp): MODS_RANSAC_THREADS, by
  * default the cores this process may use, at most 8; 1 = the one-thread loops.  Results do not depend on it. */
 int mods_ransac_host_threads(void);

@@ -6,6 +6,7 @@
 #include "f_laf.hpp"
 #include "../../include/mods_degensac.h"
 #include <cstdarg>
+#include <memory>
 #include <algorithm>
 #include <cmath>
 #include <mutex>
@@ -203,7 +204,7 @@ static int ctx_create_impl(int device, int max_w, int max_h, int batch, unsigned
     return MODS_E_NODEVICE;
   }
   MODS_HIP_CHECK(hipSetDevice(device));
-  mods_ctx *c = new mods_ctx();
+  std::unique_ptr<mods_ctx> c(new mods_ctx());   // a failed creation releases what it made
   c->device = device; c->max_w = max_w; c->max_h = max_h; c->batch = batch;
   { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->n_cu = cus; }
   MODS_HIP_CHECK(hipStreamCreateWithFlags(&c->stream, stream_flags));
@@ -212,26 +213,25 @@ static int ctx_create_impl(int device, int max_w, int max_h, int batch, unsigned
   mc = std::max<size_t>(mc, 1u << 16);
   mc = std::min<size_t>(mc, 1u << 22);
   c->max_cand = (int)mc;
-  MODS_HIP_CHECK(hipMalloc(&c->pyr_dev, sizeof(PyramidDev)));
-  MODS_HIP_CHECK(hipMalloc(&c->input_dev, px * batch * sizeof(float)));
-  MODS_HIP_CHECK(hipMalloc(&c->tmp_dev, px * batch * sizeof(float)));
-  MODS_HIP_CHECK(hipMalloc(&c->gauss_taps_dev, 16 * 64 * sizeof(float)));
-  MODS_HIP_CHECK(hipMalloc(&c->smm_mask_dev, 32 * 32 * sizeof(float)));
-  MODS_HIP_CHECK(hipMalloc(&c->cand, sizeof(CandDev) * mc * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->cand_count, sizeof(int) * 3 * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->keys_dev, sizeof(mods_affkey) * mc * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->sort_keys, sizeof(unsigned long long) * mc * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->sort_idx, sizeof(int) * 2 * mc * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->rank_dev, sizeof(int) * mc * batch));
-  c->nms_mask_words = (px / 64 + (size_t)max_h + 64) * kMaxLevels * batch;
-  MODS_HIP_CHECK(hipMalloc(&c->nms_mask, sizeof(unsigned long long) * c->nms_mask_words));
-  MODS_HIP_CHECK(hipHostMalloc(&c->host_counts, sizeof(int) * (5 * batch + 4)));   // cand / acc / key / region / inside counts, error flag
-  MODS_HIP_CHECK(hipMalloc(&c->ori_dev, 48 * mc * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->regions_dev, sizeof(mods_region) * mc * batch));
-  MODS_HIP_CHECK(hipMalloc(&c->region_count, sizeof(int) * 3 * batch));   // regions, then 2 tier counts per image
-  MODS_HIP_CHECK(hipMalloc(&c->inside_count, sizeof(int) * batch));
+  MODS_HIP_CHECK(c->pyr_dev.reserve(1));
+  MODS_HIP_CHECK(c->input_dev.reserve(px * batch));
+  MODS_HIP_CHECK(c->tmp_dev.reserve(px * batch));
+  MODS_HIP_CHECK(c->gauss_taps_dev.reserve(16 * 64));
+  MODS_HIP_CHECK(c->smm_mask_dev.reserve(32 * 32));
+  MODS_HIP_CHECK(c->cand.reserve(mc * batch));
+  MODS_HIP_CHECK(c->cand_count.reserve(3 * (size_t)batch));
+  MODS_HIP_CHECK(c->keys_dev.reserve(mc * batch));
+  MODS_HIP_CHECK(c->sort_keys.reserve(mc * batch));
+  MODS_HIP_CHECK(c->sort_idx.reserve(2 * mc * batch));
+  MODS_HIP_CHECK(c->rank_dev.reserve(mc * batch));
+  MODS_HIP_CHECK(c->nms_mask.reserve((px / 64 + (size_t)max_h + 64) * kMaxLevels * batch));
+  MODS_HIP_CHECK(c->host_counts.reserve(5 * (size_t)batch + 4));   // cand / acc / key / region / inside counts, error flag
+  MODS_HIP_CHECK(c->ori_dev.reserve(48 * mc * batch));
+  MODS_HIP_CHECK(c->regions_dev.reserve(mc * batch));
+  MODS_HIP_CHECK(c->region_count.reserve(3 * (size_t)batch));   // regions, then 2 tier counts per image
+  MODS_HIP_CHECK(c->inside_count.reserve((size_t)batch));
   MODS_HIP_CHECK(mods::fill_wait(c->stream, c->inside_count, 0, sizeof(int) * batch));
-  *out = c;
+  *out = c.release();
   return MODS_OK;
 }
 
@@ -240,31 +240,30 @@ static void dd_graph_drop(mods_ctx *c) {
   c->dd_cache.clear();
 }
 
+}  // extern "C"
+
+// what is not memory; the buffers (members, MserState, helper_stage) free themselves after this
+mods_ctx::~mods_ctx() {
+  for (auto &t : timers) {
+    for (auto &p : t.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    for (auto &e : t.pool) (void)hipEventDestroy(e);
+  }
+  mser_release(this);
+  for (mods_ctx *h : helpers) if (h) mods_ctx_destroy(h);
+  (void)hipSetDevice(device);
+  dd_graph_drop(this);
+  if (stream2) (void)hipStreamDestroy(stream2);
+  if (ev_fork) (void)hipEventDestroy(ev_fork);
+  if (ev_join) (void)hipEventDestroy(ev_join);
+  if (stream) (void)hipStreamDestroy(stream);
+}
+
+extern "C" {
+
 void mods_ctx_destroy(mods_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)mods::stream_wait(c->stream);
-  for (auto &t : c->timers) {
-    for (auto &p : t.pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    for (auto &e : t.pool) (void)hipEventDestroy(e);
-  }
-  (void)hipFree(c->pyr_dev); (void)hipFree(c->plane_pool); (void)hipFree(c->omap_pool); (void)hipFree(c->input_dev); (void)hipFree(c->u8_stage_dev); (void)hipFree(c->clahe_lut);
-  (void)hipFree(c->tmp_dev); (void)hipFree(c->alt_taps_dev); (void)hipFree(c->alt_planes); (void)hipFree(c->view_dev); (void)hipFree(c->gauss_taps_dev); (void)hipFree(c->smm_mask_dev); if (c->baum_stats_dev) (void)hipFree(c->baum_stats_dev); (void)hipFree(c->cand);
-  (void)hipFree(c->cand_count); (void)hipFree(c->keys_dev); (void)hipFree(c->sort_keys); (void)hipFree(c->sort_idx); (void)hipFree(c->rank_dev); (void)hipFree(c->nms_mask);
-  (void)hipHostFree(c->host_counts); (void)hipHostFree(c->pin_arena);
-  (void)hipFree(c->ori_dev); (void)hipFree(c->ori_multi_dev); (void)hipFree(c->regions_dev); (void)hipFree(c->regions_half_dev); (void)hipFree(c->region_count); (void)hipFree(c->inside_count); (void)hipFree(c->desc_tables_dev); (void)hipFree(c->blur_table_dev);
-  (void)hipFree(c->desc_err_dev); (void)hipFree(c->desc_scratch); (void)hipFree(c->net_out_dev);
-  (void)hipFree(c->m_desc); (void)hipFree(c->m_c); (void)hipFree(c->m_xy); (void)hipFree(c->m_u64); (void)hipFree(c->m_int); (void)hipFree(c->m_mid);
-  (void)hipFree(c->m_p2); (void)hipFree(c->dd_buf); (void)hipFree(c->m_tent2); (void)hipFree(c->m_tent); (void)hipFree(c->m_tent_batch); (void)hipHostFree(c->m_count); (void)hipFree(c->m_regs);
-  mser_release(c);
-  for (mods_ctx *h : c->helpers) if (h) mods_ctx_destroy(h);
-  for (auto &a : c->helper_stage) (void)hipFree(a.buf);
-  (void)hipSetDevice(c->device);
-  dd_graph_drop(c);
-  if (c->stream2) (void)hipStreamDestroy(c->stream2);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -611,12 +610,13 @@ int mods_baumberg_stats_enable(mods_ctx *c, int on) {
   if (!c) return MODS_E_ARG;
   MODS_HIP_CHECK(hipSetDevice(c->device));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
-  if (c->baum_stats_dev) { (void)hipFree(c->baum_stats_dev); c->baum_stats_dev = nullptr; }
-  if (on) {
-    MODS_HIP_CHECK(hipMalloc(&c->baum_stats_dev, sizeof(unsigned long long) * 2 * 64 * (size_t)c->batch));
-    MODS_HIP_CHECK(hipMemset(c->baum_stats_dev, 0, sizeof(unsigned long long) * 2 * 64 * (size_t)c->batch));
-  }
+  c->baum_stats_dev.release();
   mods::dev_pool_reallocated(c);         // (a recorded detect + describe graph holds the old pointer)
+  if (on) {
+    const size_t n = 2 * 64 * (size_t)c->batch;
+    MODS_HIP_CHECK(c->baum_stats_dev.reserve(n));
+    MODS_HIP_CHECK(mods::fill_wait(c->stream, c->baum_stats_dev, 0, sizeof(unsigned long long) * n));
+  }
   return MODS_OK;
 }
 int mods_baumberg_stats(mods_ctx *c, int img, unsigned long long *keypoints, unsigned long long *iterations) {
@@ -624,7 +624,7 @@ int mods_baumberg_stats(mods_ctx *c, int img, unsigned long long *keypoints, uns
   MODS_HIP_CHECK(hipSetDevice(c->device));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   unsigned long long v[2 * 64], kp = 0, it = 0;   // 64 slots per image (the kernel spreads its adds)
-  MODS_HIP_CHECK(hipMemcpy(v, c->baum_stats_dev + 2 * 64 * (size_t)img, sizeof(v), hipMemcpyDeviceToHost));
+  MODS_HIP_CHECK(mods::copy_wait(c->stream, v, c->baum_stats_dev + 2 * 64 * (size_t)img, sizeof(v), hipMemcpyDeviceToHost));
   for (int q = 0; q < 64; q++) { kp += v[2 * q]; it += v[2 * q + 1]; }
   if (keypoints) *keypoints = kp;
   if (iterations) *iterations = it;
@@ -742,7 +742,7 @@ int mods_sift_patch(mods_ctx *c, const float *patch, int ps, int rootsift, doubl
   int rc = describe_configure(c, &dp);
   if (rc) return rc;
   MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev, patch, sizeof(float) * ps * ps, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_sift_patch_test(c, c->input_dev, ps, rootsift, maxBinValue, (uint8_t *)c->tmp_dev))) return rc;
+  if ((rc = launch_sift_patch_test(c, c->input_dev, ps, rootsift, maxBinValue, (uint8_t *)c->tmp_dev.get()))) return rc;
   MODS_HIP_CHECK(hipMemcpyAsync(out128, c->tmp_dev, 128, hipMemcpyDeviceToHost, c->stream));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   return MODS_OK;
@@ -1113,3 +1113,97 @@ int mods_resize_half(mods_ctx *c, const float *src, int w, int h, float *dst, in
 }
 
 }  // extern "C"
+
+namespace {
+// memory policy of mods_test_buffer_growth: counts, fails on a chosen call, and knows which pointers are live
+struct FakeMem {
+  static inline int allocs = 0, frees = 0, bad_frees = 0, fail_at = -1;   // fail_at: the allocation (counted from 0) that fails
+  static inline std::vector<void *> live;
+  static void reset() { allocs = frees = bad_frees = 0; fail_at = -1; }
+  static hipError_t alloc(void **p, size_t bytes) {
+    if (allocs++ == fail_at) { *p = nullptr; return hipErrorOutOfMemory; }
+    *p = malloc(bytes ? bytes : 1);
+    live.push_back(*p);
+    return hipSuccess;
+  }
+  static hipError_t free(void *p) {
+    frees++;
+    auto it = std::find(live.begin(), live.end(), p);
+    if (it == live.end()) { bad_frees++; return hipErrorInvalidValue; }   // freed twice, or never allocated
+    live.erase(it);
+    ::free(p);
+    return hipSuccess;
+  }
+};
+}  // namespace
+
+extern "C" int mods_test_buffer_growth(int *report, int n) {
+  using B = mods::Buf<double, FakeMem>;
+  constexpr int kReport = 16, kGroup = 4;
+  if (!report || n < kReport) return MODS_E_ARG;
+  for (int i = 0; i < kReport; i++) report[i] = -1;
+  FakeMem::reset();
+  int successful = 0;   // allocations that returned memory
+  {
+    B a;
+    bool ok = a.reserve(100, 150) == hipSuccess && a.capacity() == 150;
+    successful++;
+    int a0 = FakeMem::allocs, f0 = FakeMem::frees;
+    bool moved = false;
+    ok = ok && a.reserve(120, 180, &moved) == hipSuccess && !moved && a.capacity() == 150;
+    report[0] = (FakeMem::allocs - a0) + (FakeMem::frees - f0);                 // a reserve below the capacity: 0 calls
+    ok = ok && a.reserve(151, 300, &moved) == hipSuccess && moved && a.capacity() == 300;
+    successful++;
+    report[1] = FakeMem::frees - f0; report[2] = FakeMem::allocs - a0;          // a growth: 1 free, 1 allocation
+    a0 = FakeMem::allocs; f0 = FakeMem::frees;
+    FakeMem::fail_at = FakeMem::allocs;
+    report[3] = a.reserve(301, 600) != hipSuccess && a.get() == nullptr;        // a failed growth: empty
+    report[4] = (int)a.capacity();
+    report[5] = FakeMem::frees - f0;                                            // ... and the old allocation freed once
+    FakeMem::fail_at = -1;
+    a0 = FakeMem::allocs;
+    ok = ok && a.reserve(10, 10) == hipSuccess && a.get() && a.capacity() == 10;
+    successful++;
+    report[6] = FakeMem::allocs - a0;                                           // the reserve after it allocates again: 1
+    // moves, swap, detach
+    B b(std::move(a));
+    ok = ok && !a.get() && a.capacity() == 0 && b.capacity() == 10;
+    B c; ok = ok && c.reserve(5, 5) == hipSuccess; successful++;
+    c = std::move(b);                                                           // onto a non-empty buffer: its allocation is freed
+    ok = ok && c.capacity() == 10 && !b.get();
+    B d; ok = ok && d.reserve(7, 7) == hipSuccess; successful++;
+    c.swap(d);
+    ok = ok && c.capacity() == 7 && d.capacity() == 10;
+    double *raw = d.detach();
+    ok = ok && raw && !d.get() && d.capacity() == 0;
+    B e; ok = ok && e.reserve(3, 3) == hipSuccess; successful++;
+    (void)FakeMem::free(raw);                                                   // the detached allocation is the caller's
+    FakeMem::fail_at = FakeMem::allocs;
+    ok = ok && e.reserve(4, 4) != hipSuccess && !e.get();
+    FakeMem::fail_at = -1;
+    report[7] = ok;
+    // the group rule: allocation j of kGroup fails -> all empty; without a failure all hold their elements
+    B g[kGroup];
+    int left = 0;
+    for (int j = 0; j < kGroup; j++) {
+      for (int q = 0; q < kGroup; q++) if (g[q].reserve(2, 2) == hipSuccess) successful++;   // a non-empty group to start from
+      const int before = FakeMem::allocs;
+      FakeMem::fail_at = FakeMem::allocs + j;
+      if (mods::reserve_group(g[0], 8 + j, g[1], 16 + j, g[2], 24 + j, g[3], 32 + j) == hipSuccess) left += 100;
+      successful += FakeMem::allocs - before - 1;
+      FakeMem::fail_at = -1;
+      for (const B &x : g) left += x.get() != nullptr || x.capacity() != 0;
+    }
+    report[8] = left;                                                           // 0
+    const int before = FakeMem::allocs;
+    report[9] = mods::reserve_group(g[0], 8, g[1], 16, g[2], 24, g[3], 32) == hipSuccess;
+    successful += FakeMem::allocs - before;
+    report[10] = (g[0].capacity() == 8) + (g[1].capacity() == 16) + (g[2].capacity() == 24) + (g[3].capacity() == 32);   // kGroup
+  }
+  report[11] = FakeMem::bad_frees;                                              // 0: nothing freed twice
+  report[12] = (int)FakeMem::live.size();                                       // 0: everything freed by now
+  report[13] = successful;
+  report[14] = FakeMem::frees;                                                  // == report[13]: each allocation freed exactly once
+  report[15] = kGroup;
+  return kReport;
+}

@@ -215,12 +215,9 @@ int clahe_check(mods_ctx *c, const void *src, const void *dst, int n_img, int w,
 // LUT scratch of n_img images on the given grid (a hipMalloc: called outside the pipeline's running path)
 int clahe_reserve(mods_ctx *c, int n_img, const mods_clahe_params *par) {
   const size_t need = (size_t)n_img * par->tiles_x * par->tiles_y * 256;
-  if (need <= c->clahe_lut_cap) return MODS_OK;
+  if (need <= c->clahe_lut.capacity()) return MODS_OK;
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  if (c->clahe_lut) { MODS_HIP_CHECK(mods::stream_wait(c->stream)); MODS_HIP_CHECK(hipFree(c->clahe_lut)); }
-  c->clahe_lut = nullptr; c->clahe_lut_cap = 0;
-  MODS_HIP_CHECK(hipMalloc(&c->clahe_lut, need));
-  c->clahe_lut_cap = need;
+  MODS_HIP_CHECK(mods::reserve_scratch(c, c->clahe_lut, need, need));
   return MODS_OK;
 }
 
@@ -228,7 +225,7 @@ int clahe_reserve(mods_ctx *c, int n_img, const mods_clahe_params *par) {
 int clahe_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int src_stride, const mods_clahe_params *par,
                  void *dst, int dst_stride, int dst_f32) {
   const ClaheGeom g = clahe_geom(w, h, par);
-  if ((size_t)n_img * g.tiles_x * g.tiles_y * 256 > c->clahe_lut_cap) { set_error("clahe: LUT scratch not reserved"); return MODS_E_ARG; }
+  if ((size_t)n_img * g.tiles_x * g.tiles_y * 256 > c->clahe_lut.capacity()) { set_error("clahe: LUT scratch not reserved"); return MODS_E_ARG; }
   const size_t src_img = (size_t)h * src_stride, dst_img = (size_t)h * dst_stride;
   hipLaunchKernelGGL(clahe_lut_kernel, dim3(g.tiles_x * g.tiles_y, n_img), dim3(kLutThreads), 0, c->stream, src, w, h, src_stride,
                      src_img, g, c->clahe_lut);

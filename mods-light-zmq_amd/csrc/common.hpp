@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/mods_hip.h"
+#include "buffer.hpp"
 
 namespace mods {
 
@@ -152,9 +153,13 @@ constexpr int kept_slot(int pair = kLastSearch) { return kCountSlots + 1 + pair;
 constexpr int status_slot(int pair = kLastSearch) { return 2 * kCountSlots + 1 + pair; }
 inline int read_slot(const int *counts, int slot) { return ((const volatile int *)counts)[slot]; }   // a device wrote it: after a stream wait
 
+struct MserState;   // mser.hip
+
 }  // namespace mods
 
 struct mods_ctx {
+  mods_ctx() = default;
+  ~mods_ctx();                       // capi.hip: what is not memory (events, graph execs, helpers, streams); every buffer below frees itself
   int device = 0;
   int n_cu = 256;                    // compute units of the device (sizes the persistent grids)
   int max_w = 0, max_h = 0, batch = 1;
@@ -169,42 +174,38 @@ struct mods_ctx {
   int pyr_streams = 2;                    // mods_ctx_pyramid_streams: 1 keeps the whole scale space on ctx->stream
   // scale space
   mods::PyramidDev pyr;              // host copy of the descriptor table
-  mods::PyramidDev *pyr_dev = nullptr;
+  mods::Buf<mods::PyramidDev> pyr_dev;
   mods::PyramidDev pyr_dev_image;    // what pyr_dev holds (pyramid_configure uploads the table only when it changed)
   bool pyr_dev_valid = false;
-  float *plane_pool = nullptr;       // all blur/response planes
-  size_t plane_pool_elems = 0;
-  unsigned int *omap_pool = nullptr;
-  size_t omap_pool_elems = 0;
+  mods::Buf<float> plane_pool;       // all blur/response planes
+  mods::Buf<unsigned int> omap_pool;
   bool omap_dirty = true;            // the pool holds cells that are not 0xFFFFFFFF (detect_run fills it before use)
-  float *input_dev = nullptr;        // staging for host-pointer entry points
-  float *tmp_dev = nullptr;
+  mods::Buf<float> input_dev;        // staging for host-pointer entry points
+  mods::Buf<float> tmp_dev;
   // DoG / Harris responses (pyramid.cpp:165-194, 256-278): per-level tap tables of the response's own blur and scratch planes
-  float *alt_taps_dev = nullptr;           // [kMaxLevels][kAltTapStride]
+  mods::Buf<float> alt_taps_dev;           // [kMaxLevels][kAltTapStride]
   int alt_ntap[mods::kMaxLevels] = {0};
   float alt_sigma[mods::kMaxLevels] = {0};  // sigma the tables were built for
-  float *alt_planes = nullptr; size_t alt_plane_elems = 0;   // 4 planes of the first octave's size
-  float *view_dev = nullptr;         // pixels of the current synthesised view (allocated on first use)
-  float *gauss_taps_dev = nullptr;   // [16 slots][64] Gaussian taps
+  mods::Buf<float> alt_planes;       // 4 planes of the first octave's size
+  mods::Buf<float> view_dev;         // pixels of the current synthesised view (allocated on first use)
+  mods::Buf<float> gauss_taps_dev;   // [16 slots][64] Gaussian taps
   float taps_sigma[16] = {0};        // sigma currently held by each slot (0 = empty)
   float taps_host[16][2 * mods::kMaxBlurRadius + 1] = {{0}};
   int taps_host_n[16] = {0};
-  float *smm_mask_dev = nullptr;     // computeGaussMask(smmWindowSize)
-  unsigned long long *baum_stats_dev = nullptr;   // per image slot: {keypoints that entered the Baumberg iteration, iterations run} (mods_baumberg_stats)
+  mods::Buf<float> smm_mask_dev;     // computeGaussMask(smmWindowSize)
+  mods::Buf<unsigned long long> baum_stats_dev;   // per image slot: {keypoints that entered the Baumberg iteration, iterations run} (mods_baumberg_stats)
   int smm_mask_size = 0;
   // candidates
   int max_cand = 0;                  // per image
-  mods::CandDev *cand = nullptr;     // [batch][max_cand]
-  int *cand_count = nullptr;         // [batch] raw NMS hits
-  mods_affkey *keys_dev = nullptr;   // [batch][max_cand] sorted output
-  unsigned long long *sort_keys = nullptr;
-  int *sort_idx = nullptr;
-  int *rank_dev = nullptr;           // [batch][max_cand]
-  unsigned long long *nms_mask = nullptr;   // ballot words of one octave's NMS
-  size_t nms_mask_words = 0;
-  int *key_count = nullptr;          // [batch]
-  int *host_counts = nullptr;        // pinned
-  unsigned char *u8_stage_dev = nullptr;   // [batch][max_h][max_w] staging of 8-bit host images (pair pipeline), lazily allocated
+  mods::Buf<mods::CandDev> cand;     // [batch][max_cand]
+  mods::Buf<int> cand_count;         // [3][batch] raw NMS hits, accepted, keys
+  mods::Buf<mods_affkey> keys_dev;   // [batch][max_cand] sorted output
+  mods::Buf<unsigned long long> sort_keys;
+  mods::Buf<int> sort_idx;
+  mods::Buf<int> rank_dev;           // [batch][max_cand]
+  mods::Buf<unsigned long long> nms_mask;   // ballot words of one octave's NMS
+  mods::PinnedBuf<int> host_counts;
+  mods::Buf<unsigned char> u8_stage_dev;   // [batch][max_h][max_w] staging of 8-bit host images (pair pipeline), lazily allocated
   // the 8-bit twin [n_img][h][w] of the fp32 images of the detect + describe call in progress (mods_detect_describe_dev_u8), read by
   // describe_run_view; nullptr outside such a call
   const unsigned char *img_u8_dev = nullptr;
@@ -212,30 +213,29 @@ struct mods_ctx {
   long u8_source_calls = 0;              // detect + describe calls that had such a twin (mods_ctx_u8_source_calls)
   // CLAHE (clahe.hip): LUT scratch [n_img][tiles_y * tiles_x][256] (clahe_reserve); clahe_on: the pair pipeline's 8-bit batches are
   // equalised with clahe_par on their way to fp32 (mods_pipeline_create_clahe)
-  unsigned char *clahe_lut = nullptr; size_t clahe_lut_cap = 0;
+  mods::Buf<unsigned char> clahe_lut;
   bool clahe_on = false;
   mods_clahe_params clahe_par = {0.0, 0, 0};
-  char *pin_arena = nullptr;         // pinned host staging of a batch's tentative lists (pair pipeline), lazily allocated
-  size_t pin_arena_cap = 0;
+  mods::PinnedBuf<char> pin_arena;   // pinned host staging of a batch's tentative lists (pair pipeline), lazily allocated
   mods_hessaff_params par;
   int reg_number_eff = -1;           // par.regionsNumber after the tilt / zoom scaling of DetectAffineKeypoints (scale-space-detector.cpp:20-21)
   int last_w = 0, last_h = 0, last_n_img = 0;
   const float *last_img_dev = nullptr; int last_stride = 0;   // the batch the pyramid was built from (sampleFromImage)
   // orientation + description
-  float *desc_tables_dev = nullptr;  // [orimask 64x64][desc mask 64x64][orientation vote mask 64x64][SiftTab], offsets kTab*
-  int *desc_err_dev = nullptr;
+  mods::Buf<float> desc_tables_dev;  // [orimask 64x64][desc mask 64x64][orientation vote mask 64x64][SiftTab], offsets kTab*
+  mods::Buf<int> desc_err_dev;
   int desc_ori_ps = 0, desc_ps = 0;
-  void *ori_dev = nullptr;           // [batch][max_cand] OriOut
-  void *ori_multi_dev = nullptr; size_t ori_multi_bytes = 0;   // [batch][max_cand][ori_cap] OriOut (maxAngles > 1), allocated on first use
-  mods_region *regions_dev = nullptr;  // [batch][max_cand]
-  mods_region *regions_half_dev = nullptr;   // HalfRootSIFT twins (allocated on first use)
+  mods::Buf<char> ori_dev;           // [batch][max_cand] OriOut (describe.hip), in bytes
+  mods::Buf<char> ori_multi_dev;     // [batch][max_cand][ori_cap] OriOut (maxAngles > 1), allocated on first use
+  mods::Buf<mods_region> regions_dev;  // [batch][max_cand]
+  mods::Buf<mods_region> regions_half_dev;   // HalfRootSIFT twins (allocated on first use)
   bool have_half = false;
-  int *region_count = nullptr;       // [batch]
-  int *inside_count = nullptr;       // [batch] keypoints that pass the centre test (the reference's unoriented list)
+  mods::Buf<int> region_count;       // [batch]
+  mods::Buf<int> inside_count;       // [batch] keypoints that pass the centre test (the reference's unoriented list)
   std::vector<int> last_inside_counts;
-  float *desc_scratch = nullptr;
+  mods::Buf<float> desc_scratch;
   int blur_table_ps = 0;
-  float *blur_table_dev = nullptr;   // per-P2 taps / resampling sequence / source indices of the LDS extraction tier (sift.hip: blur_table_kernel)
+  mods::Buf<float> blur_table_dev;   // per-P2 taps / resampling sequence / source indices of the LDS extraction tier (sift.hip: blur_table_kernel)
   // external descriptor (e.g. a ZMQ daemon): when set, patches go to this function instead of the SIFT kernel
   mods_descriptor_fn ext_fn = nullptr;
   void *ext_user = nullptr;
@@ -250,37 +250,35 @@ struct mods_ctx {
   // patch go to the host.  A slot holds a callback or a network, never both; the networks are shared, not owned
   mods_net *shape_net = nullptr, *ori_net = nullptr, *ext_net = nullptr;
   int shape_q8 = 0, ori_q8 = 0, ext_q8 = 0;          // round the patches to 8 bits first, as the wire to a daemon does
-  float *net_out_dev = nullptr; size_t net_out_cap = 0;   // the networks' outputs of one image slot (floats), grown on demand
-  size_t desc_scratch_elems = 0;
+  mods::Buf<float> net_out_dev;      // the networks' outputs of one image slot (floats), grown on demand
   std::vector<int> last_region_counts;
   // matching
-  int8_t *m_desc = nullptr;          // [2][pad][128] int8 descriptors (query list, train list)
-  int *m_c = nullptr;                // [2][pad] precombined norms
-  void *m_xy = nullptr;              // [2][pad] double2 centres
-  unsigned long long *m_u64 = nullptr;
-  int *m_int = nullptr;
-  void *m_mid = nullptr;
-  void *m_p2 = nullptr;              // pass-1 top-2 keys per train split, pass-2 query subset (see match.hip)
+  mods::Buf<int8_t> m_desc;          // [2][pad][128] int8 descriptors (query list, train list)
+  mods::Buf<int> m_c;                // [2][pad] precombined norms
+  mods::Buf<double2> m_xy;           // [2][pad] centres
+  mods::Buf<unsigned long long> m_u64;
+  mods::Buf<int> m_int;
+  mods::Buf<char> m_mid;             // QueryMid records (match.hip), in bytes
+  mods::Buf<char> m_p2;              // pass-1 top-2 keys per train split, pass-2 query subset (see match.hip)
   size_t m_best2_cap = 0;            // entries (pairs of keys) in the top-2 table
   int m_sets = 0;                    // searches the matcher's scratch buffers hold side by side (match_ensure_buffers)
-  mods_tentative *m_tent = nullptr;
+  mods::Buf<char> m_tent;
   // m_tent holds the n tentatives of the last search PACKED: mods_tentative[n] | (16-byte aligned) u6[n][6] = the correspondences
   // (x1 y1 1 x2 y2 1) | laf[n][14] = the frames (x y a11 a12 a21 a22 s) of both regions - one device-to-host copy of
   // tent_bytes(n) bytes brings all three (tent_u6_off / tent_laf_off give the parts)
-  int *m_count = nullptr;            // PINNED HOST memory (kCountInts ints), indexed by count_slot / kept_slot / status_slot
+  mods::PinnedBuf<int> m_count;      // PINNED HOST memory (kCountInts ints), indexed by count_slot / kept_slot / status_slot
   mods_tentative *m_tent_out = nullptr; int *m_count_out = nullptr;   // set by a batch of pairs: where match_run leaves the packed list / its length
-  char *m_tent_batch = nullptr; size_t m_tent_batch_cap = 0;          // the packed lists of a batch, one segment per pair
-  mods_region *m_regs = nullptr;     // [2][max_cand] staging for host-side lists
-  void *dd_buf = nullptr; int dd_jobs = 0;   // duplicate filter on the device (dedup.hip): per list of a batch sorted coordinates, ranks, near lists
-  mods_tentative *m_tent2 = nullptr; // the filtered packed list of the last search (single-pair path)
+  mods::Buf<char> m_tent_batch;      // the packed lists of a batch, one segment per pair
+  mods::Buf<mods_region> m_regs;     // [2][max_cand] staging for host-side lists
+  mods::Buf<char> dd_buf; int dd_jobs = 0;   // duplicate filter on the device (dedup.hip): per list of a batch sorted coordinates, ranks, near lists
+  mods::Buf<char> m_tent2;           // the filtered packed list of the last search (single-pair path)
   mods::TentList h_list;             // host copy for the sequential stages
   std::vector<unsigned char> h_mask;
-  void *mser = nullptr;              // MserState (mser.hip): buffers of the MSER detector, allocated on first use
+  mods::MserState *mser = nullptr;   // MserState (mser.hip): buffers of the MSER detector, allocated on first use
   // the step loop spreads the views of a step over a few more contexts of the same GPU (imgrep.hip: run_view_jobs)
   std::vector<mods_ctx *> helpers;
   std::atomic<bool> helpers_failed{false};   // a helper context could not be made (memory): reported once, not retried
-  struct StageArena { mods_region *buf = nullptr; size_t cap = 0; };
-  std::vector<StageArena> helper_stage;
+  std::vector<mods::Buf<mods_region>> helper_stage;   // view staging, one arena per helper (imgrep.hip)
   // timing
   int timing_mask = 0;
   // mods_ctx_graphs: the launches of a detect + describe call replayed as one hipGraph (capi.hip: mods_detect_describe_dev)
@@ -309,6 +307,22 @@ constexpr int kTabOriMask = 0, kTabDescMask = 4096, kTabVoteMask = 8192, kTabSif
 // untouched: every upload, setter and (re)allocation that changes them from the host goes through one of these two
 inline void dev_state_changed(mods_ctx *c) { c->dev_state_epoch++; }                          // tables / parameters refreshed from the host
 inline void dev_pool_reallocated(mods_ctx *c) { c->dev_state_epoch++; c->dd_stale = true; }   // a pool moved: recordings are dropped
+
+// How a buffer of a context grows (buffer.hpp knows no streams): launches on ctx->stream may still use the allocation that a growth
+// frees, so the stream is waited for first - only when something is freed, never in steady state.  `alloc_elems` is the caller's
+// growth policy.  The capacity is set by the buffer, never by the caller
+template <class B> inline hipError_t reserve_scratch(mods_ctx *c, B &b, size_t need, size_t alloc_elems, bool *moved = nullptr) {
+  if (need <= b.capacity()) return hipSuccess;
+  if (b.get()) { const hipError_t e = stream_wait(c->stream); if (e != hipSuccess) return e; }
+  return b.reserve(need, alloc_elems, moved);
+}
+// ... and one that recorded graphs point into: they are dropped when it moved
+template <class B> inline hipError_t reserve_pool(mods_ctx *c, B &b, size_t need, size_t alloc_elems) {
+  bool moved = false;
+  const hipError_t e = reserve_scratch(c, b, need, alloc_elems, &moved);
+  if (moved) dev_pool_reallocated(c);
+  return e;
+}
 struct StageScope {                  // brackets launches of one stage with events when enabled
   mods_ctx *ctx; int stage; hipEvent_t e0 = nullptr, e1 = nullptr; bool on;
   StageScope(mods_ctx *c, int s, double bytes = 0);

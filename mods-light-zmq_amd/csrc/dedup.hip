@@ -207,9 +207,10 @@ static size_t dup_job_stride(const mods_ctx *c) {
 int dup_filter_reserve(mods_ctx *c, int n_jobs) {
   if (n_jobs < 1 || n_jobs > DUP_MAX_JOBS) { set_error("duplicate filter: %d lists", n_jobs); return MODS_E_ARG; }
   if (c->dd_jobs >= n_jobs) return MODS_OK;
-  if (c->dd_buf) { MODS_HIP_CHECK(mods::stream_wait(c->stream)); MODS_HIP_CHECK(hipFree(c->dd_buf)); c->dd_buf = nullptr; c->dd_jobs = 0; }
-  MODS_HIP_CHECK(hipMalloc(&c->dd_buf, (dup_job_stride(c) + 2 * (size_t)c->max_cand * sizeof(int)) * n_jobs));
-  c->dd_jobs = n_jobs;
+  const size_t bytes = (dup_job_stride(c) + 2 * (size_t)c->max_cand * sizeof(int)) * n_jobs;
+  const hipError_t e = mods::reserve_scratch(c, c->dd_buf, bytes, bytes);
+  c->dd_jobs = e == hipSuccess ? n_jobs : 0;
+  MODS_HIP_CHECK(e);
   return MODS_OK;
 }
 
@@ -220,8 +221,8 @@ int dup_filter_dev(mods_ctx *c, const DupJob *jobs, int n_jobs, int grid_n, doub
   const size_t ctr_job = 2 * n * sizeof(int);
   DupBatch b;
   b.n_jobs = n_jobs; b.max_n = c->max_cand; b.mode = mode; b.r_sq = r * r;   // the packed layout of a source list is that of min(*n_src, max_cand) entries (match_emit_kernel)
-  b.scratch = (char *)c->dd_buf; b.stride = stride;
-  b.counters = (int *)((char *)c->dd_buf + stride * c->dd_jobs);
+  b.scratch = c->dd_buf; b.stride = stride;
+  b.counters = (int *)(c->dd_buf + stride * c->dd_jobs);
   for (int i = 0; i < n_jobs; i++) b.job[i] = jobs[i];
   if (grid_n > c->max_cand || grid_n < 1) grid_n = c->max_cand;
   static DynLdsOnce once;

@@ -468,7 +468,7 @@ __global__ __launch_bounds__(256) void fast_sqrt_selftest_kernel(unsigned long l
   atomicAdd(out + 0, bad_dom); atomicAdd(out + 1, bad_tiny); atomicAdd(out + 2, bad_any); atomicAdd(out + 3, seen); atomicAdd(out + 4, bad_neg);
 }
 int launch_fast_sqrt_selftest(mods_ctx *ctx, unsigned long long *out5_host) {
-  unsigned long long *dev = (unsigned long long *)ctx->tmp_dev;
+  unsigned long long *dev = (unsigned long long *)ctx->tmp_dev.get();
   MODS_HIP_CHECK(hipMemsetAsync(dev, 0, 5 * sizeof(unsigned long long), ctx->stream));
   hipLaunchKernelGGL(fast_sqrt_selftest_kernel, dim3(4096), dim3(256), 0, ctx->stream, dev);
   MODS_HIP_CHECK(hipGetLastError());
@@ -526,8 +526,7 @@ int describe_configure(mods_ctx *ctx, const mods_describe_params *par) {
   if (par->ori_patchSize < 8 || par->ori_patchSize > 48 || par->desc_patchSize < 9 || par->desc_patchSize > 63 ||
       !(par->desc_patchSize & 1)) { set_error("unsupported patch sizes (ori %d, desc %d)", par->ori_patchSize, par->desc_patchSize); return MODS_E_ARG; }
   if (!ctx->desc_tables_dev) {
-    MODS_HIP_CHECK(hipMalloc(&ctx->desc_tables_dev, sizeof(float) * kTabSift + sizeof(SiftTab)));
-    MODS_HIP_CHECK(hipMalloc(&ctx->desc_err_dev, sizeof(int)));
+    MODS_HIP_CHECK(mods::reserve_group(ctx->desc_tables_dev, kTabSift + (sizeof(SiftTab) + sizeof(float) - 1) / sizeof(float), ctx->desc_err_dev, 1));
     MODS_HIP_CHECK(hipMemsetAsync(ctx->desc_err_dev, 0, sizeof(int), ctx->stream));
   }
   if (ctx->desc_ori_ps != par->ori_patchSize || ctx->desc_ps != par->desc_patchSize) {
@@ -844,25 +843,20 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
     hipLaunchKernelGGL(ori_bin_table_kernel, dim3(8), dim3(256), 0, ctx->stream);
     if (k.ori_cap > 1) {     // room for ori_cap oriented copies per keypoint
       const size_t need = sizeof(OriOut) * (size_t)k.ori_cap * ctx->max_cand * ctx->batch;
-      if (need > ctx->ori_multi_bytes) {
-        if (ctx->ori_multi_dev) MODS_HIP_CHECK(hipFree(ctx->ori_multi_dev));
-        ctx->ori_multi_dev = nullptr; ctx->ori_multi_bytes = 0;
-        mods::dev_pool_reallocated(ctx); MODS_HIP_CHECK(hipMalloc(&ctx->ori_multi_dev, need));
-        ctx->ori_multi_bytes = need;
-      }
+      MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->ori_multi_dev, need, need));
     }
     if (img_u8 && kernel_from_u8(ctx, U8K_ORIENT))
       hipLaunchKernelGGL(orient_kernel<unsigned char>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_u8, k, ctx->keys_dev, key_count,
-                         orimask, (OriOut *)ctx->ori_dev, (OriOut *)ctx->ori_multi_dev);
+                         orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
     else
       hipLaunchKernelGGL(orient_kernel<float>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_dev, k, ctx->keys_dev, key_count,
-                         orimask, (OriOut *)ctx->ori_dev, (OriOut *)ctx->ori_multi_dev);
+                         orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
     if (k.ori_cap > 1)
       hipLaunchKernelGGL(compact_regions_multi_kernel, dim3(1, n_img), dim3(1024), 0, ctx->stream, k, ctx->keys_dev, key_count,
-                         (const OriOut *)ctx->ori_dev, (const OriOut *)ctx->ori_multi_dev, ctx->regions_dev, ctx->region_count, ctx->inside_count);
+                         (const OriOut *)ctx->ori_dev.get(), (const OriOut *)ctx->ori_multi_dev.get(), ctx->regions_dev, ctx->region_count, ctx->inside_count);
     else
       hipLaunchKernelGGL(compact_regions_kernel, dim3((ctx->max_cand + 1023) / 1024, n_img), dim3(1024), 0, ctx->stream, k, ctx->keys_dev, key_count,
-                         (const OriOut *)ctx->ori_dev, ctx->regions_dev, ctx->region_count, ctx->inside_count);
+                         (const OriOut *)ctx->ori_dev.get(), ctx->regions_dev, ctx->region_count, ctx->inside_count);
     MODS_HIP_CHECK(hipGetLastError());
   }
   rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8);

@@ -1142,7 +1142,7 @@ static int detect_run_stages(mods_ctx *ctx) {
   hipStream_t fill_stream = ctx->pyr_side ? ctx->stream2 : ctx->stream;
   MODS_HIP_CHECK(hipMemsetAsync(ctx->cand_count, 0, sizeof(int) * 3 * ctx->batch, fill_stream));   // cand/acc/key counts
   if (ctx->omap_dirty) {     // first use of the pool, or a call that did not reach omap_reset_kernel: fill it once
-    MODS_HIP_CHECK(hipMemsetAsync(ctx->omap_pool, 0xFF, ctx->omap_pool_elems * sizeof(unsigned int), fill_stream));
+    MODS_HIP_CHECK(hipMemsetAsync(ctx->omap_pool, 0xFF, ctx->omap_pool.capacity() * sizeof(unsigned int), fill_stream));
   }
   ctx->omap_dirty = true;    // until this call has put the cells it claims back
   int *acc_count = ctx->cand_count + ctx->batch;
@@ -1175,7 +1175,7 @@ static int detect_run_stages(mods_ctx *ctx) {
       comp_pl.n++;
       mask_words += (size_t)n_img * total;
     }
-    if (mask_words > ctx->nms_mask_words) { set_error("nms mask buffer too small"); return MODS_E_CAPACITY; }
+    if (mask_words > ctx->nms_mask.capacity()) { set_error("nms mask buffer too small"); return MODS_E_CAPACITY; }
     unsigned long long *mask = (unsigned long long *)ctx->nms_mask;
     if (wide_pl.n && narrow_pl.n && narrow_pl.blk_begin[narrow_pl.n] <= 64 && wide_pl.n + narrow_pl.n <= kMaxOctaves) {
       for (int e = 0; e < narrow_pl.n; e++) {      // the tail octaves (30 x 17 pixels ...): not worth a launch of their own

@@ -15,6 +15,7 @@
 // so the matcher reads them in place and, for the multi-GPU path, the all-gather moves one dense buffer.
 #include "common.hpp"
 #include <atomic>
+#include <memory>
 #include <string>
 #include <thread>
 #include <algorithm>
@@ -24,7 +25,7 @@
 struct mods_imgrep {
   int device = 0;
   hipStream_t stream = nullptr;     // the owning context's stream
-  mods_region *reg = nullptr;
+  mods::Buf<mods_region> reg;
   int cap = 0, n = 0;
 };
 
@@ -102,22 +103,22 @@ int mods_view_schedule(const double *scale_set, int n_scales, const double *tilt
 int mods_imgrep_create(mods_ctx *c, int capacity, mods_imgrep **out) {
   if (!c || !out || capacity <= 0) { set_error("imgrep_create: bad arguments"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  mods_imgrep *r = new mods_imgrep();
-  r->device = c->device; r->stream = c->stream; r->cap = capacity;
-  MODS_HIP_CHECK(hipMalloc(&r->reg, sizeof(mods_region) * (size_t)capacity));
-  *out = r;
+  std::unique_ptr<mods_imgrep> r(new mods_imgrep());
+  r->device = c->device; r->stream = c->stream;
+  MODS_HIP_CHECK(r->reg.reserve((size_t)capacity));
+  r->cap = capacity;
+  *out = r.release();
   return MODS_OK;
 }
 void mods_imgrep_destroy(mods_imgrep *r) {
   if (!r) return;
   (void)hipSetDevice(r->device);
   (void)mods::stream_wait(r->stream);
-  (void)hipFree(r->reg);
   delete r;
 }
 int mods_imgrep_clear(mods_imgrep *r) { if (!r) return MODS_E_ARG; r->n = 0; return MODS_OK; }
 int mods_imgrep_count(const mods_imgrep *r) { return r ? r->n : 0; }
-const mods_region *mods_imgrep_regions_dev(const mods_imgrep *r) { return r ? r->reg : nullptr; }
+const mods_region *mods_imgrep_regions_dev(const mods_imgrep *r) { return r ? r->reg.get() : nullptr; }
 
 // AddRegions: the regions the context holds for image slot `img` (after mods_detect_describe[_view]_dev)
 static int imgrep_append_from(mods_imgrep *r, mods_ctx *c, int img, const mods_region *base) {
@@ -353,30 +354,28 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
       wk->ori_net = c->ori_net; wk->ori_q8 = c->ori_q8; wk->ori_mr = c->ori_mr; wk->ori_ps = c->ori_ps;
       wk->ext_net = c->ext_net; wk->ext_q8 = c->ext_q8; wk->ext_mr = c->ext_mr; wk->ext_ps = c->ext_ps;
     }
-    mods_ctx::StageArena &A = c->helper_stage[k];
+    mods::Buf<mods_region> &A = c->helper_stage[k];
     size_t used = 0;
     auto park = [&](int ji, int slot) {                         // regions of context slot `slot` -> this worker's arena
       ViewJob &j = jobs[ji];
       const size_t need = used + (size_t)j.nr * (j.want_half ? 2 : 1);
-      if (need > A.cap) {                                       // grow, keeping what earlier jobs of this step left
-        const size_t cap = std::max<size_t>(need + need / 2, 1 << 14);
-        mods_region *nb = nullptr;
-        if (hipMalloc(&nb, cap * sizeof(mods_region)) != hipSuccess) { j.rc = MODS_E_HIP; set_error("view staging: out of device memory"); return; }
+      if (need > A.capacity()) {                                // grow, keeping what earlier jobs of this step left
+        mods::Buf<mods_region> nb;
+        if (nb.reserve(std::max<size_t>(need + need / 2, 1 << 14)) != hipSuccess) { j.rc = MODS_E_HIP; set_error("view staging: out of device memory"); return; }
         (void)mods::stream_wait(wk->stream);                 // copies into the old arena may still be in flight
-        if (used) (void)mods::copy_wait(wk->stream, nb, A.buf, used * sizeof(mods_region), hipMemcpyDeviceToDevice);
-        (void)hipFree(A.buf);
-        A.buf = nb; A.cap = cap;
+        if (used) (void)mods::copy_wait(wk->stream, nb, A, used * sizeof(mods_region), hipMemcpyDeviceToDevice);
+        A.swap(nb);                                          // (the old arena goes with nb)
       }
       // the copies are ordered on the worker's stream before the next view overwrites the context's region lists: no
       // synchronisation per view, one per worker at the end
       placed[ji].off = used;
-      if (j.nr > 0 && hipMemcpyAsync(A.buf + used, wk->regions_dev + (size_t)slot * wk->max_cand, sizeof(mods_region) * (size_t)j.nr, hipMemcpyDeviceToDevice,
+      if (j.nr > 0 && hipMemcpyAsync(A + used, wk->regions_dev + (size_t)slot * wk->max_cand, sizeof(mods_region) * (size_t)j.nr, hipMemcpyDeviceToDevice,
                                      wk->stream) != hipSuccess) j.rc = MODS_E_HIP;
       used += j.nr;
       if (!j.rc && j.want_half && j.nr > 0) {
         placed[ji].off_half = used;
         if (!wk->have_half || !wk->regions_half_dev) { j.rc = MODS_E_ARG; set_error("view job: no HalfRootSIFT descriptors in the context"); }
-        else if (hipMemcpyAsync(A.buf + used, wk->regions_half_dev + (size_t)slot * wk->max_cand, sizeof(mods_region) * (size_t)j.nr, hipMemcpyDeviceToDevice,
+        else if (hipMemcpyAsync(A + used, wk->regions_half_dev + (size_t)slot * wk->max_cand, sizeof(mods_region) * (size_t)j.nr, hipMemcpyDeviceToDevice,
                                 wk->stream) != hipSuccess) j.rc = MODS_E_HIP;
         used += j.nr;
       }
@@ -434,8 +433,8 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
   for (size_t i = 0; i < jobs.size(); i++) {
     ViewJob &j = jobs[i];
     if (j.rc) { set_error("%s", j.err.c_str()); return j.rc; }
-    j.src = c->helper_stage[owner[i]].buf + placed[i].off;           // arenas may have moved while growing: resolved here
-    j.src_half = j.want_half ? c->helper_stage[owner[i]].buf + placed[i].off_half : nullptr;
+    j.src = c->helper_stage[owner[i]] + placed[i].off;           // arenas may have moved while growing: resolved here
+    j.src_half = j.want_half ? c->helper_stage[owner[i]] + placed[i].off_half : nullptr;
   }
   return MODS_OK;
 }

@@ -941,12 +941,9 @@ int match_ensure_buffers(mods_ctx *ctx, int n_sets) {
   if (n_sets > MATCH_MAX_JOBS) n_sets = MATCH_MAX_JOBS;
   if (ctx->m_desc && ctx->m_sets >= n_sets) return MODS_OK;
   const size_t n = match_pad(ctx);
-  if (ctx->m_desc) {        // more sets than before: the per-search scratch is reallocated (nothing in it outlives a search)
-    MODS_HIP_CHECK(mods::stream_wait(ctx->stream));
-    MODS_HIP_CHECK(hipFree(ctx->m_desc)); MODS_HIP_CHECK(hipFree(ctx->m_c)); MODS_HIP_CHECK(hipFree(ctx->m_xy)); MODS_HIP_CHECK(hipFree(ctx->m_u64));
-    MODS_HIP_CHECK(hipFree(ctx->m_int)); MODS_HIP_CHECK(hipFree(ctx->m_mid)); MODS_HIP_CHECK(hipFree(ctx->m_p2));
-    ctx->m_desc = nullptr; ctx->m_c = nullptr; ctx->m_xy = nullptr; ctx->m_u64 = nullptr; ctx->m_int = nullptr; ctx->m_mid = nullptr; ctx->m_p2 = nullptr;
-  }
+  // more sets than before: the per-search scratch is reallocated (nothing in it outlives a search)
+  if (ctx->m_desc) MODS_HIP_CHECK(mods::stream_wait(ctx->stream));
+  ctx->m_sets = 0;
   // pass-1 key table (one 16-byte triple per query and train split): the largest product splits * padded queries over the list
   // sizes this context admits (the split count grows with the train list, so only the query count is scanned)
   {
@@ -960,19 +957,16 @@ int match_ensure_buffers(mods_ctx *ctx, int n_sets) {
   MatchJobs st;
   match_strides(ctx, &st);
   const size_t S = (size_t)n_sets;
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_desc, S * st.s_desc));
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_c, S * st.s_c * sizeof(int)));   // c of queries, trains; seeds of both; parity words of both
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_xy, S * st.s_xy * sizeof(double2)));
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_u64, S * st.s_u64 * sizeof(unsigned long long)));
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_int, S * st.s_int * sizeof(int)));   // n_lt, bad, per-block counts of the compaction
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_mid, S * st.s_mid * sizeof(QueryMid)));
-  // m_p2: key table | exact top-2 per query | pass-2 subset: state, descriptors, list, norms, count
-  MODS_HIP_CHECK(hipMalloc(&ctx->m_p2, S * st.s_p2));
-  if (!ctx->m_regs) MODS_HIP_CHECK(hipMalloc(&ctx->m_regs, 2 * (size_t)ctx->max_cand * sizeof(mods_region)));
-  if (!ctx->m_tent) MODS_HIP_CHECK(hipMalloc(&ctx->m_tent, tent_bytes(n) + 64));
+  // a failed growth leaves all seven empty (m_desc is the "already allocated" test) and m_sets at 0.  m_c: c of queries, trains;
+  // seeds of both; parity words of both.  m_int: n_lt, bad, per-block counts of the compaction.  m_p2: key table | exact top-2 per
+  // query | pass-2 subset: state, descriptors, list, norms, count
+  MODS_HIP_CHECK(mods::reserve_group(ctx->m_desc, S * st.s_desc, ctx->m_c, S * st.s_c, ctx->m_xy, S * st.s_xy, ctx->m_u64, S * st.s_u64,
+                                     ctx->m_int, S * st.s_int, ctx->m_mid, S * st.s_mid * sizeof(QueryMid), ctx->m_p2, S * st.s_p2));
+  MODS_HIP_CHECK(ctx->m_regs.reserve(2 * (size_t)ctx->max_cand));
+  MODS_HIP_CHECK(ctx->m_tent.reserve(tent_bytes(n) + 64));
   // the tentative count lives in pinned host memory: the emit kernel's single store lands there, the host reads it after a
   // stream synchronisation - no 4-byte copy launch per search
-  if (!ctx->m_count) MODS_HIP_CHECK(hipHostMalloc(&ctx->m_count, mods::kCountInts * sizeof(int)));   // (slots: common.hpp)
+  MODS_HIP_CHECK(ctx->m_count.reserve(mods::kCountInts));   // (slots: common.hpp)
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_desc, 0, S * st.s_desc, ctx->stream));
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_c, 0, S * st.s_c * sizeof(int), ctx->stream));
   ctx->m_sets = n_sets;
@@ -1028,12 +1022,12 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
   int8_t *qd = ctx->m_desc, *td = ctx->m_desc + n * 128;
   int *qc = ctx->m_c, *tc = ctx->m_c + n, *qc2 = ctx->m_c + 2 * n, *tc2 = ctx->m_c + 3 * n;
   unsigned int *qpar = (unsigned int *)(ctx->m_c + 4 * n), *tpar = qpar + n / 32 + 2;
-  double2 *qxy = (double2 *)ctx->m_xy, *txy = (double2 *)ctx->m_xy + n;
+  double2 *qxy = ctx->m_xy, *txy = ctx->m_xy + n;
   unsigned long long *key_ge = ctx->m_u64 + n, *key_lt = ctx->m_u64 + 2 * n;
   int *n_lt = ctx->m_int, *bad = ctx->m_int + n;
   StageScope ts(ctx, MODS_STAGE_MATCH);
   // carve of m_p2 (every part 16-byte aligned)
-  uint4 *best3 = (uint4 *)ctx->m_p2;
+  uint4 *best3 = (uint4 *)ctx->m_p2.get();
   unsigned long long *best2 = (unsigned long long *)(best3 + ctx->m_best2_cap);
   QueryMid *mid2 = (QueryMid *)(best2 + 2 * n);
   int8_t *qd2 = (int8_t *)(mid2 + n);
@@ -1049,7 +1043,7 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
     }
     hipLaunchKernelGGL(match_fix_kernel, dim3((max_q + 7) / 8, G), dim3(256), 0, ctx->stream, J, k, (const uint4 *)best3, qd, qc, td, tc, best2);
     hipLaunchKernelGGL(match_mid_kernel, dim3((max_q + 255) / 256, G), dim3(256), 0, ctx->stream, J, k, (const unsigned long long *)best2, txy,
-                       (QueryMid *)ctx->m_mid, key_ge, key_lt, n_lt, bad, list2, count2, qd, qc, qd2, qcs, mid2);
+                       (QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, list2, count2, qd, qc, qd2, qcs, mid2);
     // pass 2 on the undecided queries only (their number stays on the device: the grid covers the worst case, idle blocks exit)
     {
       const int qblocks = (max_q + 128 * MATCH_QB - 1) / (128 * MATCH_QB);
@@ -1059,8 +1053,8 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
                          (const QueryMid *)mid2, key_ge, key_lt, n_lt, bad, count2, list2);
     }
     int *block_counts = (int *)(ctx->m_int + 2 * n);
-    hipLaunchKernelGGL(match_emit_count_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid, key_ge, key_lt, n_lt, bad, block_counts);
-    hipLaunchKernelGGL(match_emit_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid, key_ge, key_lt, n_lt, bad, qxy, txy,
+    hipLaunchKernelGGL(match_emit_count_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, block_counts);
+    hipLaunchKernelGGL(match_emit_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qxy, txy,
                        block_counts, ctx->max_cand);
   }
   MODS_HIP_CHECK(hipGetLastError());
@@ -1073,7 +1067,7 @@ int match_run(mods_ctx *ctx, const mods_region *q_dev, int n_q, const mods_regio
   int rc = match_ensure_buffers(ctx);
   if (rc) return rc;
   // where the packed list and its length go: the context's own buffer / counter, or what a batch of pairs set (pair.hip: pairs_gpu_stage)
-  mods_tentative *tent_out = ctx->m_tent_out ? ctx->m_tent_out : ctx->m_tent;
+  mods_tentative *tent_out = ctx->m_tent_out ? ctx->m_tent_out : (mods_tentative *)ctx->m_tent.get();
   int *count_out = ctx->m_count_out ? ctx->m_count_out : ctx->m_count;
   return match_run_group(ctx, 1, &q_dev, &n_q, &t_dev, &n_t, &tent_out, &count_out, ratio, contradDist, nn);
 }
@@ -1135,22 +1129,22 @@ int match_run_distance(mods_ctx *ctx, const mods_region *q_dev, int n_q, const m
   int *qc = ctx->m_c, *tc = ctx->m_c + n, *qc2 = ctx->m_c + 2 * n, *tc2 = ctx->m_c + 3 * n;
   unsigned int *qpar = (unsigned int *)(ctx->m_c + 4 * n), *tpar = qpar + n / 32 + 2;
   MODS_HIP_CHECK(hipMemsetAsync(qpar, 0, sizeof(unsigned int) * 2 * (n / 32 + 2), ctx->stream));
-  double2 *qxy = (double2 *)ctx->m_xy, *txy = (double2 *)ctx->m_xy + n;
+  double2 *qxy = ctx->m_xy, *txy = ctx->m_xy + n;
   unsigned long long *key_ge = ctx->m_u64 + n, *key_lt = ctx->m_u64 + 2 * n;
   int *n_lt = ctx->m_int, *bad = ctx->m_int + n;
   StageScope ts(ctx, MODS_STAGE_MATCH);
   hipLaunchKernelGGL(match_pack_kernel, dim3(std::min(2048, (n_q + 3) / 4)), dim3(256), 0, ctx->stream, q_dev, (const int *)nullptr, n_q, qd, qc, qc2, qpar, qxy, ctx->max_cand);
   hipLaunchKernelGGL(match_pack_kernel, dim3(std::min(2048, (n_t + 3) / 4)), dim3(256), 0, ctx->stream, t_dev, (const int *)nullptr, n_t, td, tc, tc2, tpar, txy, ctx->max_cand);
-  hipLaunchKernelGGL(hamming_nn2_kernel, dim3((n_q + 255) / 256), dim3(256), 0, ctx->stream, k, qd, td, (QueryMid *)ctx->m_mid, key_ge);
+  hipLaunchKernelGGL(hamming_nn2_kernel, dim3((n_q + 255) / 256), dim3(256), 0, ctx->stream, k, qd, td, (QueryMid *)ctx->m_mid.get(), key_ge);
   const int eblocks = (n_q + EMIT_T - 1) / EMIT_T;
   int *block_counts = (int *)(ctx->m_int + 2 * n);
   MatchJobs J;
   memset(&J, 0, sizeof(J));
   match_strides(ctx, &J);
   J.n_jobs = 1; J.n_q[0] = n_q; J.n_t[0] = n_t; J.eblocks[0] = eblocks;
-  J.q_reg[0] = q_dev; J.t_reg[0] = t_dev; J.tent_out[0] = ctx->m_tent; J.count_out[0] = ctx->m_count;
-  hipLaunchKernelGGL(match_emit_count_kernel, dim3(eblocks), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid, key_ge, key_lt, n_lt, bad, block_counts);
-  hipLaunchKernelGGL(match_emit_kernel, dim3(eblocks), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid, key_ge, key_lt, n_lt, bad, qxy, txy, block_counts, ctx->max_cand);
+  J.q_reg[0] = q_dev; J.t_reg[0] = t_dev; J.tent_out[0] = (mods_tentative *)ctx->m_tent.get(); J.count_out[0] = ctx->m_count;
+  hipLaunchKernelGGL(match_emit_count_kernel, dim3(eblocks), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, block_counts);
+  hipLaunchKernelGGL(match_emit_kernel, dim3(eblocks), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qxy, txy, block_counts, ctx->max_cand);
   MODS_HIP_CHECK(hipGetLastError());
   return MODS_OK;
 }

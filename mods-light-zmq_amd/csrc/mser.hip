@@ -27,46 +27,20 @@
 namespace mods {
 
 struct MserState {
-  unsigned char *img8 = nullptr; size_t img8_cap = 0;           // [n_img][h][w]
-  int32_t *pix_slot = nullptr; uint32_t *tpar = nullptr; uint8_t *tlev = nullptr; int32_t *inner = nullptr; size_t px_cap = 0;   // [jobs][P]
-  int *tab = nullptr; size_t tab_cap = 0;
-  unsigned long long *keys = nullptr; size_t keys_cap = 0;      // 4 arrays of keys_cap: starts in / out, ends in / out
-  void *sort_tmp = nullptr; size_t sort_tmp_cap = 0;
-  double *ell = nullptr; size_t ell_cap = 0;                    // [n_u][6]
-  unsigned long long *counters = nullptr;                       // device: starts, ends, errors
-  unsigned char *h_img8 = nullptr; size_t h_img8_cap = 0;       // pinned
-  int32_t *h_pix_slot = nullptr; uint32_t *h_tpar = nullptr; uint8_t *h_tlev = nullptr; size_t h_px_cap = 0;
-  int *h_tab = nullptr; size_t h_tab_cap = 0;
-  unsigned long long *h_counters = nullptr;
+  Buf<unsigned char> img8;                                      // [n_img][h][w]
+  Buf<int32_t> pix_slot; Buf<uint32_t> tpar; Buf<uint8_t> tlev; Buf<int32_t> inner;   // [jobs][P]
+  Buf<int> tab;
+  Buf<unsigned long long> keys;                                 // 4 arrays of capacity / 4: starts in / out, ends in / out
+  Buf<char> sort_tmp;
+  Buf<double> ell;                                              // [n_u][6]
+  Buf<unsigned long long> counters;                             // device: starts, ends, errors
+  PinnedBuf<unsigned char> h_img8;
+  PinnedBuf<int32_t> h_pix_slot; PinnedBuf<uint32_t> h_tpar; PinnedBuf<uint8_t> h_tlev;
+  PinnedBuf<int> h_tab;
+  PinnedBuf<unsigned long long> h_counters;
 };
 
-void mser_release(mods_ctx *c) {
-  MserState *s = (MserState *)c->mser;
-  if (!s) return;
-  (void)hipFree(s->img8); (void)hipFree(s->pix_slot); (void)hipFree(s->tpar); (void)hipFree(s->tlev); (void)hipFree(s->inner);
-  (void)hipFree(s->tab); (void)hipFree(s->keys); (void)hipFree(s->sort_tmp); (void)hipFree(s->ell); (void)hipFree(s->counters);
-  (void)hipHostFree(s->h_img8); (void)hipHostFree(s->h_pix_slot); (void)hipHostFree(s->h_tpar); (void)hipHostFree(s->h_tlev);
-  (void)hipHostFree(s->h_tab); (void)hipHostFree(s->h_counters);
-  delete s;
-  c->mser = nullptr;
-}
-
-template <typename T>
-static int grow_dev(T *&p, size_t &cap, size_t need) {
-  if (need <= cap) return MODS_OK;
-  if (p) MODS_HIP_CHECK(hipFree(p));
-  p = nullptr; cap = 0;
-  MODS_HIP_CHECK(hipMalloc(&p, need * sizeof(T)));
-  cap = need;
-  return MODS_OK;
-}
-template <typename T>
-static int grow_host(T *&p, size_t need) {
-  if (p) MODS_HIP_CHECK(hipHostFree(p));
-  p = nullptr;
-  MODS_HIP_CHECK(hipHostMalloc(&p, need * sizeof(T)));
-  return MODS_OK;
-}
+void mser_release(mods_ctx *c) { delete c->mser; c->mser = nullptr; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 struct MserTabs {
@@ -291,26 +265,22 @@ int mser_detect(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int 
   if (par->mode == MODS_DET_NOT_LESS_THAN_REGIONS && par->regionsNumber < 0) { set_error("regionsNumber must be >= 0 in this mode"); return MODS_E_ARG; }
   if ((size_t)(w + 2) * (h + 2) >= (1ull << 31)) { set_error("MSER: image too large"); return MODS_E_ARG; }
   if (!c->mser) c->mser = new MserState();
-  MserState &S = *(MserState *)c->mser;
+  MserState &S = *c->mser;
   const int n_jobs = 2 * n_img, cols = w + 2, rows = h + 2;
   const size_t npx = (size_t)w * h, P = (size_t)rows * cols;
   int rc;
-  if ((rc = grow_dev(S.img8, S.img8_cap, npx * n_img))) return rc;
-  if (P * n_jobs > S.px_cap) {
-    size_t cap = 0;
-    if ((rc = grow_dev(S.pix_slot, cap, P * n_jobs))) return rc;
-    cap = 0; if ((rc = grow_dev(S.tpar, cap, P * n_jobs))) return rc;
-    cap = 0; if ((rc = grow_dev(S.tlev, cap, P * n_jobs))) return rc;
-    cap = 0; if ((rc = grow_dev(S.inner, cap, P * n_jobs))) return rc;
-    S.px_cap = P * n_jobs;
+  const size_t px = P * n_jobs;
+  MODS_HIP_CHECK(reserve_scratch(c, S.img8, npx * n_img, npx * n_img));
+  if (px > S.inner.capacity()) {
+    MODS_HIP_CHECK(stream_wait(c->stream));
+    MODS_HIP_CHECK(reserve_group(S.pix_slot, px, S.tpar, px, S.tlev, px, S.inner, px));
   }
-  if (npx * n_img > S.h_img8_cap) { if ((rc = grow_host(S.h_img8, npx * n_img))) return rc; S.h_img8_cap = npx * n_img; }
-  if (P * n_jobs > S.h_px_cap) {
-    if ((rc = grow_host(S.h_pix_slot, P * n_jobs)) || (rc = grow_host(S.h_tpar, P * n_jobs)) || (rc = grow_host(S.h_tlev, P * n_jobs))) return rc;
-    S.h_px_cap = P * n_jobs;
+  MODS_HIP_CHECK(reserve_scratch(c, S.h_img8, npx * n_img, npx * n_img));
+  if (px > S.h_tlev.capacity()) {
+    MODS_HIP_CHECK(stream_wait(c->stream));
+    MODS_HIP_CHECK(reserve_group(S.h_pix_slot, px, S.h_tpar, px, S.h_tlev, px));
   }
-  if (!S.counters) MODS_HIP_CHECK(hipMalloc(&S.counters, 4 * sizeof(unsigned long long)));
-  if (!S.h_counters) MODS_HIP_CHECK(hipHostMalloc(&S.h_counters, 4 * sizeof(unsigned long long)));
+  MODS_HIP_CHECK(reserve_group(S.counters, 4, S.h_counters, 4));
   c->par = *par;
   c->last_w = w; c->last_h = h; c->last_n_img = n_img;
   c->last_img_dev = img_dev; c->last_stride = stride;
@@ -430,8 +400,8 @@ int mser_detect(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int 
   const size_t o_ss_slot = 0, o_ss_begin = o_ss_slot + n_ss, o_u_slot = o_ss_begin + n_ss + 1, o_u_thresh = o_u_slot + n_u,
                o_u_area = o_u_thresh + n_u, o_u_parent = o_u_area + n_u, o_job_ss = o_u_parent + n_u, o_job_u = o_job_ss + n_jobs + 1,
                o_out = o_job_u + n_jobs + 1, n_tab = o_out + 5 * (size_t)n_keys;
-  if ((rc = grow_dev(S.tab, S.tab_cap, n_tab))) return rc;
-  if (n_tab > S.h_tab_cap) { if ((rc = grow_host(S.h_tab, n_tab))) return rc; S.h_tab_cap = n_tab; }
+  MODS_HIP_CHECK(reserve_scratch(c, S.tab, n_tab, n_tab));
+  MODS_HIP_CHECK(reserve_scratch(c, S.h_tab, n_tab, n_tab));
   std::copy(ss_slot.begin(), ss_slot.end(), S.h_tab + o_ss_slot);
   std::copy(ss_begin.begin(), ss_begin.end(), S.h_tab + o_ss_begin);
   std::copy(u_slot.begin(), u_slot.end(), S.h_tab + o_u_slot);
@@ -468,32 +438,22 @@ int mser_detect(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int 
     set_error("MSER: %llu run starts, %llu run ends", S.h_counters[0], S.h_counters[1]);
     return MODS_E_HIP;
   }
-  if (n_runs > S.keys_cap) {
-    if (S.keys) MODS_HIP_CHECK(hipFree(S.keys));
-    S.keys = nullptr; S.keys_cap = 0;
-    const size_t cap = n_runs + n_runs / 4 + 1024;
-    MODS_HIP_CHECK(hipMalloc(&S.keys, 4 * cap * sizeof(unsigned long long)));
-    S.keys_cap = cap;
-  }
-  unsigned long long *s_in = S.keys, *s_out = S.keys + S.keys_cap, *e_in = S.keys + 2 * S.keys_cap, *e_out = S.keys + 3 * S.keys_cap;
+  MODS_HIP_CHECK(reserve_scratch(c, S.keys, 4 * n_runs, 4 * (n_runs + n_runs / 4 + 1024)));
+  const size_t keys_cap = S.keys.capacity() / 4;
+  unsigned long long *s_in = S.keys, *s_out = S.keys + keys_cap, *e_in = S.keys + 2 * keys_cap, *e_out = S.keys + 3 * keys_cap;
   MODS_HIP_CHECK(hipMemsetAsync(S.counters, 0, 2 * sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(mser_runs_kernel, pgrid, dim3(256), 0, c->stream, T, w, h, P, S.inner, 1, S.counters, s_in, e_in, S.keys_cap);
+  hipLaunchKernelGGL(mser_runs_kernel, pgrid, dim3(256), 0, c->stream, T, w, h, P, S.inner, 1, S.counters, s_in, e_in, keys_cap);
   MODS_HIP_CHECK(hipGetLastError());
   int ubits = 1;
   while ((1ll << ubits) < n_u) ubits++;
   size_t tmp_bytes = 0;
   MODS_HIP_CHECK(rocprim::radix_sort_keys(nullptr, tmp_bytes, s_in, s_out, n_runs, 0, 32 + ubits, c->stream));
-  if (tmp_bytes > S.sort_tmp_cap) {
-    if (S.sort_tmp) MODS_HIP_CHECK(hipFree(S.sort_tmp));
-    S.sort_tmp = nullptr; S.sort_tmp_cap = 0;
-    MODS_HIP_CHECK(hipMalloc(&S.sort_tmp, tmp_bytes));
-    S.sort_tmp_cap = tmp_bytes;
-  }
+  MODS_HIP_CHECK(reserve_scratch(c, S.sort_tmp, tmp_bytes, tmp_bytes));
   MODS_HIP_CHECK(rocprim::radix_sort_keys(S.sort_tmp, tmp_bytes, s_in, s_out, n_runs, 0, 32 + ubits, c->stream));
   MODS_HIP_CHECK(rocprim::radix_sort_keys(S.sort_tmp, tmp_bytes, e_in, e_out, n_runs, 0, 32 + ubits, c->stream));
 
   // 5. moments, frames, keypoints
-  if ((rc = grow_dev(S.ell, S.ell_cap, (size_t)n_u * 6))) return rc;
+  MODS_HIP_CHECK(reserve_scratch(c, S.ell, (size_t)n_u * 6, (size_t)n_u * 6));
   hipLaunchKernelGGL(mser_ellipse_kernel, dim3((n_u + 63) / 64), dim3(64), 0, c->stream, T, n_u, w, s_out, e_out, n_runs, S.ell, S.counters);
   const int *ot = S.tab + o_out;
   hipLaunchKernelGGL(mser_export_kernel, dim3((n_keys + 255) / 256), dim3(256), 0, c->stream, n_keys, ot, ot + n_keys, ot + 2 * (size_t)n_keys,

@@ -416,14 +416,13 @@ int mods_net_forward(mods_net *net, const float *patches_host, int n, int quanti
   if (n == 0) return MODS_OK;
   MODS_HIP_CHECK(hipSetDevice(net->device));
   hipStream_t s = mods::thread_stream(net->device);
-  float *in_dev = nullptr;
+  mods::Buf<float> in_dev;
   const size_t in_elems = (size_t)n * kPP, out_elems = (size_t)n * net->dim;
-  MODS_HIP_CHECK(hipMalloc(&in_dev, (in_elems + out_elems) * sizeof(float)));
+  MODS_HIP_CHECK(in_dev.reserve(in_elems + out_elems));
   hipError_t e = mods::copy_wait(s, in_dev, patches_host, in_elems * sizeof(float), hipMemcpyHostToDevice);
   int rc = MODS_OK;
   if (e == hipSuccess) rc = mods_net_forward_dev(net, s, in_dev, n, quantise_u8, in_dev + in_elems);
   if (e == hipSuccess && rc == MODS_OK) e = mods::copy_wait(s, out_host, in_dev + in_elems, out_elems * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(in_dev);
   if (rc) return rc;
   MODS_HIP_CHECK(e);
   return MODS_OK;
@@ -471,14 +470,7 @@ namespace mods {
 int net_run_to_host(mods_ctx *ctx, mods_net *net, const float *patches_dev, int n, int quantise_u8, float *out_host) {
   if (n <= 0) return MODS_OK;
   const size_t need = (size_t)n * net->dim;
-  if (need > ctx->net_out_cap) {
-    MODS_HIP_CHECK(mods::stream_wait(ctx->stream));
-    if (ctx->net_out_dev) MODS_HIP_CHECK(hipFree(ctx->net_out_dev));
-    ctx->net_out_dev = nullptr; ctx->net_out_cap = 0;
-    const size_t cap = std::max<size_t>(need + need / 2, 1 << 16);
-    MODS_HIP_CHECK(hipMalloc(&ctx->net_out_dev, cap * sizeof(float)));
-    ctx->net_out_cap = cap;
-  }
+  MODS_HIP_CHECK(mods::reserve_scratch(ctx, ctx->net_out_dev, need, std::max<size_t>(need + need / 2, 1 << 16)));
   const int rc = mods_net_forward_dev(net, ctx->stream, patches_dev, n, quantise_u8, ctx->net_out_dev);
   if (rc) return rc;
   MODS_HIP_CHECK(mods::copy_wait(ctx->stream, out_host, ctx->net_out_dev, need * sizeof(float), hipMemcpyDeviceToHost));

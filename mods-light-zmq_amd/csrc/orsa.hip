@@ -148,18 +148,12 @@ struct OrsaGpu {
   int device = -1;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  float4 *pts = nullptr; float *tabs = nullptr; int n_cap = 0;
-  float *models = nullptr; OrsaOut *out = nullptr; OrsaOut *out_host = nullptr; int m_cap = 0;
-  unsigned *gkeys = nullptr; size_t gk_cap = 0;
-  ~OrsaGpu() {
+  Buf<float4> pts; Buf<float> tabs;                                    // n points, 2 (n + 1) table entries: reserved together
+  Buf<float> models; Buf<OrsaOut> out; PinnedBuf<OrsaOut> out_host;    // 9 floats in, a record out per model: reserved together
+  Buf<unsigned> gkeys;
+  ~OrsaGpu() {                                                         // (the buffers free themselves)
     if (device < 0) return;
     (void)hipSetDevice(device);
-    if (pts) (void)hipFree(pts);
-    if (tabs) (void)hipFree(tabs);
-    if (models) (void)hipFree(models);
-    if (out) (void)hipFree(out);
-    if (out_host) (void)hipHostFree(out_host);
-    if (gkeys) (void)hipFree(gkeys);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
@@ -167,7 +161,8 @@ struct OrsaGpu {
 };
 
 static OrsaGpu *orsa_gpu() {
-  static thread_local OrsaGpu ws;
+  static thread_local ThreadWorkspace<OrsaGpu> tl;   // (ransac_gpu.hpp: the main thread's is not released at process exit)
+  OrsaGpu &ws = tl.get();
   if (ws.device < 0) {
     RansacGpu *r = ransac_gpu();   // the device the degensac entry points of this thread use (mods_ransac_set_device)
     if (!r) return nullptr;
@@ -208,14 +203,7 @@ struct DeviceScorer {
     ws = orsa_gpu();
     if (!ws) return false;
     const int n = Pr.n;
-    if (n > ws->n_cap) {
-      if (ws->pts) (void)hipFree(ws->pts);
-      if (ws->tabs) (void)hipFree(ws->tabs);
-      ws->pts = nullptr; ws->tabs = nullptr; ws->n_cap = 0;
-      RS_CHECK(hipMalloc(&ws->pts, sizeof(float4) * n));
-      RS_CHECK(hipMalloc(&ws->tabs, sizeof(float) * 2 * (n + 1)));
-      ws->n_cap = n;
-    }
+    RS_CHECK(reserve_group(ws->pts, (size_t)n, ws->tabs, 2 * ((size_t)n + 1)));
     std::vector<float4> pts(n);
     for (int i = 0; i < n; i++) pts[i] = make_float4(Pr.p1[2 * i], Pr.p1[2 * i + 1], Pr.p2[2 * i], Pr.p2[2 * i + 1]);
     std::vector<float> tabs(2 * (n + 1));
@@ -235,29 +223,17 @@ struct DeviceScorer {
   }
 
   bool score(const std::vector<float> &F, int m, std::vector<orsa::Score> &res) {
-    if (m > ws->m_cap) {
-      int cap = ws->m_cap ? ws->m_cap : 1024;
-      while (cap < m) cap *= 2;
-      if (ws->models) (void)hipFree(ws->models);
-      if (ws->out) (void)hipFree(ws->out);
-      if (ws->out_host) (void)hipHostFree(ws->out_host);
-      ws->models = nullptr; ws->out = nullptr; ws->out_host = nullptr; ws->m_cap = 0;
-      RS_CHECK(hipMalloc(&ws->models, sizeof(float) * 9 * cap));
-      RS_CHECK(hipMalloc(&ws->out, sizeof(OrsaOut) * cap));
-      RS_CHECK(hipHostMalloc(&ws->out_host, sizeof(OrsaOut) * cap, hipHostMallocDefault));
-      ws->m_cap = cap;
+    if ((size_t)m > ws->out.capacity()) {
+      size_t cap = ws->out.capacity() ? ws->out.capacity() : 1024;
+      while (cap < (size_t)m) cap *= 2;
+      RS_CHECK(reserve_group(ws->models, 9 * cap, ws->out, cap, ws->out_host, cap));
     }
     const int wgs_needed = (m + G - 1) / G;
     int grid = wgs_needed;
     if (!lds) {
       grid = wgs_needed < 256 ? wgs_needed : 256;
       const size_t need = (size_t)grid * seg;
-      if (need > ws->gk_cap) {
-        if (ws->gkeys) (void)hipFree(ws->gkeys);
-        ws->gkeys = nullptr; ws->gk_cap = 0;
-        RS_CHECK(hipMalloc(&ws->gkeys, sizeof(unsigned) * need));
-        ws->gk_cap = need;
-      }
+      RS_CHECK(ws->gkeys.reserve(need));
     }
     RS_CHECK(hipMemcpyAsync(ws->models, F.data(), sizeof(float) * 9 * m, hipMemcpyHostToDevice, ws->stream));
     OrsaConst k;
@@ -549,9 +525,8 @@ long long mods_test_orsa_log10_sweep(unsigned begin, unsigned count, unsigned *l
   OrsaGpu *ws = orsa_gpu();
   if (!ws) return MODS_E_NODEVICE;
   const unsigned chunk = 1u << 26;
-  float *d = nullptr, *hbuf = nullptr;
-  if (hipMalloc(&d, sizeof(float) * chunk) != hipSuccess || hipHostMalloc(&hbuf, sizeof(float) * chunk, hipHostMallocDefault) != hipSuccess) {
-    if (d) (void)hipFree(d);
+  Buf<float> d; PinnedBuf<float> hbuf;
+  if (reserve_group(d, chunk, hbuf, chunk) != hipSuccess) {
     set_error("log10_sweep: allocation failed");
     return MODS_E_HIP;
   }
@@ -561,7 +536,7 @@ long long mods_test_orsa_log10_sweep(unsigned begin, unsigned count, unsigned *l
   for (unsigned long long off = 0; off < count; off += chunk) {
     const unsigned c = (unsigned)std::min<unsigned long long>(chunk, count - off);
     const unsigned b0 = begin + (unsigned)off;
-    hipLaunchKernelGGL(orsa_log10_kernel, dim3((c + 255) / 256), dim3(256), 0, ws->stream, b0, c, d);
+    hipLaunchKernelGGL(orsa_log10_kernel, dim3((c + 255) / 256), dim3(256), 0, ws->stream, b0, c, d.get());
     if (hipMemcpyAsync(hbuf, d, sizeof(float) * c, hipMemcpyDeviceToHost, ws->stream) != hipSuccess ||
         hipStreamSynchronize(ws->stream) != hipSuccess) { bad = MODS_E_HIP; break; }
     const int parts = 64;
@@ -580,8 +555,6 @@ long long mods_test_orsa_log10_sweep(unsigned begin, unsigned count, unsigned *l
       }
     });
   }
-  (void)hipFree(d);
-  (void)hipHostFree(hbuf);
   return bad;
 }
 

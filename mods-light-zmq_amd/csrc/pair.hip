@@ -16,13 +16,13 @@ static bool dedup_on_device(const mods_pair_params *par) {
 
 // the filtered packed list of the single-pair path (mods_ctx::m_tent2), allocated on first use
 static int ensure_tent2(mods_ctx *c) {
-  if (!c->m_tent2) MODS_HIP_CHECK(hipMalloc(&c->m_tent2, tent_bytes(((size_t)c->max_cand + 127) & ~(size_t)63) + 64));
+  MODS_HIP_CHECK(c->m_tent2.reserve(tent_bytes(((size_t)c->max_cand + 127) & ~(size_t)63) + 64));
   return MODS_OK;
 }
 
 // the duplicate filter's job for the last single search: m_tent -> m_tent2, the counters of kLastSearch
 static DupJob single_pair_dup_job(mods_ctx *c) {
-  return {(const char *)c->m_tent, (char *)c->m_tent2, c->m_count + count_slot(), c->m_count + kept_slot(), c->m_count + status_slot()};
+  return {c->m_tent, c->m_tent2, c->m_count + count_slot(), c->m_count + kept_slot(), c->m_count + status_slot()};
 }
 
 constexpr size_t kPinArena = (size_t)24 << 20;   // pinned staging of a batch's tentative lists
@@ -44,7 +44,7 @@ extern "C" __global__ __launch_bounds__(256) void u8_rows_to_f32_kernel(const un
 }
 // the context's staging area for 8-bit host images, allocated at its first use
 int mods::u8_stage_ensure(mods_ctx *c) {
-  if (!c->u8_stage_dev) MODS_HIP_CHECK(hipMalloc(&c->u8_stage_dev, (size_t)c->max_w * c->max_h * c->batch + 16));
+  MODS_HIP_CHECK(c->u8_stage_dev.reserve((size_t)c->max_w * c->max_h * c->batch + 16));
   return MODS_OK;
 }
 // images [n_img][h][stride] of 8-bit grey in HBM -> fp32 [n_img][h][w]; any size, any alignment of src
@@ -155,7 +155,7 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
   // The tentative lists of the batch go to the host through a pinned arena: the packed list of a pair (tentatives |
   // correspondences | frames) is ONE transfer queued behind its match kernels, the stream is synchronised once per pair for the COUNT only (4 bytes) and once
   // per batch for the lists; a pair that does not fit the arena takes the direct (pageable, synchronous) path.
-  if (!c->pin_arena) { MODS_HIP_CHECK(hipHostMalloc(&c->pin_arena, kPinArena)); c->pin_arena_cap = kPinArena; }
+  MODS_HIP_CHECK(c->pin_arena.reserve(kPinArena));
   // every pair's search is queued without waiting: the packed list of pair i goes to its own segment of a device arena (a
   // list is at most as long as the query list), its length to slot i of the pinned counter array.  Then ONE synchronisation
   // for the lengths, the transfers of exactly those bytes, and one more for the lists (before: a synchronisation per pair).
@@ -164,14 +164,9 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
   for (int i = 0; i < n_pairs; i++) seg[i + 1] = seg[i] + ((tent_bytes((size_t)std::max(nr[2 * i], 1)) + 255) & ~(size_t)255);
   if ((rc = match_ensure_buffers(c))) return rc;
   const bool dedup = dedup_on_device(par);
-  const bool direct = dedup && seg[n_pairs] <= c->pin_arena_cap;
+  const bool direct = dedup && seg[n_pairs] <= c->pin_arena.capacity();
   // (the second half of the arena takes the filtered lists of the device duplicate filter)
-  if (2 * seg[n_pairs] > c->m_tent_batch_cap) {
-    if (c->m_tent_batch) MODS_HIP_CHECK(hipFree(c->m_tent_batch));
-    c->m_tent_batch = nullptr; c->m_tent_batch_cap = 0;
-    MODS_HIP_CHECK(hipMalloc(&c->m_tent_batch, 2 * seg[n_pairs] + seg[n_pairs] / 2));
-    c->m_tent_batch_cap = 2 * seg[n_pairs] + seg[n_pairs] / 2;
-  }
+  MODS_HIP_CHECK(mods::reserve_scratch(c, c->m_tent_batch, 2 * seg[n_pairs], 2 * seg[n_pairs] + seg[n_pairs] / 2));
   const double tm0 = now_ms();
   // the searches of the batch's pairs in grouped launches (csrc/match.hip: match_run_group), up to 16 pairs per set of launches
   for (int i0 = 0; i0 < n_pairs; i0 += 16) {
@@ -222,7 +217,7 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     if (n > 0) {
       const size_t bytes = tent_bytes((size_t)n);
       if (filtered && direct) off[i] = seg[i];          // already in the arena
-      else if (used + bytes <= c->pin_arena_cap) {
+      else if (used + bytes <= c->pin_arena.capacity()) {
         MODS_HIP_CHECK(hipMemcpyAsync(c->pin_arena + used, list, bytes, hipMemcpyDeviceToHost, c->stream));
         off[i] = used; used += (bytes + 15) & ~(size_t)15;
         copies = true;
@@ -297,7 +292,7 @@ int mods_ctx_warmup(mods_ctx *c, int n_img, int w, int h, const mods_pair_params
   if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("warmup: image larger than the context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
   if (int rc_stage = mods::u8_stage_ensure(c)) return rc_stage;
-  if (!c->pin_arena) { MODS_HIP_CHECK(hipHostMalloc(&c->pin_arena, kPinArena)); c->pin_arena_cap = kPinArena; }
+  MODS_HIP_CHECK(c->pin_arena.reserve(kPinArena));
   std::vector<float> img((size_t)w * h);
   // blobs every 14 px on top of blobs every 90 px: some ten thousand regions of both patch tiers on a 2-megapixel image; on larger
   // images the lattice is stretched so that the count stays there (a 4096 x 4096 image at the 14-px period overflows the lists)

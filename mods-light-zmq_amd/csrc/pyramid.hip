@@ -975,7 +975,8 @@ static int wide_blur(mods_ctx *ctx, const float *src, float *dst, float *tmp, in
 // Response() of one level for DET_DOG / DET_HARRIS, whole batch
 static int launch_alt_response(mods_ctx *ctx, const float *blur, float *resp, int w, int h, int n_img, int level, float level_sigma) {
   const size_t n = (size_t)w * h * n_img;
-  float *p0 = ctx->alt_planes, *p1 = p0 + ctx->alt_plane_elems, *p2 = p1 + ctx->alt_plane_elems, *p3 = p2 + ctx->alt_plane_elems;
+  const size_t pe = ctx->alt_planes.capacity() / 4;
+  float *p0 = ctx->alt_planes, *p1 = p0 + pe, *p2 = p1 + pe, *p3 = p2 + pe;
   const unsigned blocks = (unsigned)((n + 255) / 256);
   int rc;
   if (ctx->par.detectorType == MODS_DET_DOG) {
@@ -1047,19 +1048,9 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
     cw = nw; ch = nh;
     pd *= 2.0f;
   }
-  if (plane_elems > ctx->plane_pool_elems) {
-    if (ctx->plane_pool) MODS_HIP_CHECK(hipFree(ctx->plane_pool));
-    ctx->plane_pool = nullptr;
-    mods::dev_pool_reallocated(ctx); MODS_HIP_CHECK(hipMalloc(&ctx->plane_pool, plane_elems * sizeof(float)));
-    ctx->plane_pool_elems = plane_elems;
-  }
-  if (omap_elems > ctx->omap_pool_elems) {
-    if (ctx->omap_pool) MODS_HIP_CHECK(hipFree(ctx->omap_pool));
-    ctx->omap_pool = nullptr;
-    mods::dev_pool_reallocated(ctx); MODS_HIP_CHECK(hipMalloc(&ctx->omap_pool, omap_elems * sizeof(unsigned int)));
-    ctx->omap_pool_elems = omap_elems;
-    ctx->omap_dirty = true;
-  }
+  MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->plane_pool, plane_elems, plane_elems));
+  if (omap_elems > ctx->omap_pool.capacity()) ctx->omap_dirty = true;
+  MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->omap_pool, omap_elems, omap_elems));
   float *pp = ctx->plane_pool;
   unsigned int *mp = ctx->omap_pool;
   for (int oi = 0; oi < P.n_oct; oi++) {
@@ -1078,14 +1069,9 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
     ctx->pyr_dev_valid = true;
   }
   if (par->detectorType != MODS_DET_HESSIAN) {
-    if (!ctx->alt_taps_dev) MODS_HIP_CHECK(hipMalloc(&ctx->alt_taps_dev, sizeof(float) * kMaxLevels * kAltTapStride));
-    const size_t need = (size_t)w * h * n_img;
-    if (need > ctx->alt_plane_elems) {
-      if (ctx->alt_planes) MODS_HIP_CHECK(hipFree(ctx->alt_planes));
-      ctx->alt_planes = nullptr; ctx->alt_plane_elems = 0;
-      mods::dev_pool_reallocated(ctx); MODS_HIP_CHECK(hipMalloc(&ctx->alt_planes, 4 * need * sizeof(float)));
-      ctx->alt_plane_elems = need;
-    }
+    MODS_HIP_CHECK(ctx->alt_taps_dev.reserve((size_t)kMaxLevels * kAltTapStride));
+    const size_t need = 4 * (size_t)w * h * n_img;
+    MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->alt_planes, need, need));
     for (int l = 0; l < n_levels; l++) {
       const float sigma = alt_response_sigma(*par, P.oct[0].sigma[l]);
       if (ctx->alt_ntap[l] && ctx->alt_sigma[l] == sigma) continue;

@@ -138,15 +138,7 @@ __global__ void __launch_bounds__(256) ransac_gain_few_kernel(const double *__re
 
 RansacGpu::~RansacGpu() {
   if (device < 0) return;
-  // The workspace is thread-local.  A worker thread returns its HBM when it ends; the main thread's copy is
-  // destroyed during process exit, when the HIP runtime (or a profiler layered on it) may already be shutting
-  // down and a hipFree can block forever - the process is going away, so nothing is released there.
-  if ((long)getpid() == (long)syscall(SYS_gettid)) return;
   (void)hipSetDevice(device);
-  (void)hipFree(u_dev); (void)hipFree(hyp_dev); (void)hipHostFree(hyp_host); (void)hipFree(d_dev); (void)hipFree(gain_dev);
-  (void)hipFree(J_dev); (void)hipHostFree(J_host);   // (the counts live behind the J values in the same allocations)
-  (void)hipHostFree(row_host); (void)hipFree(aux_dev);
-  (void)hipHostFree(cand_host); (void)hipHostFree(candc_host); (void)hipHostFree(cntf_host); (void)hipHostFree(cntc_host);   // (cand_dev / candc_dev are their device addresses)
   for (int q = 0; q < 2; q++) if (cand_ev[q]) (void)hipEventDestroy(cand_ev[q]);
   if (stream) (void)hipStreamDestroy(stream);
 }
@@ -167,7 +159,8 @@ long ransac_pinned_seed() {
 }
 
 RansacGpu *ransac_gpu() {
-  static thread_local RansacGpu ws;
+  static thread_local ThreadWorkspace<RansacGpu> tl;
+  RansacGpu &ws = tl.get();
   if (ws.device < 0) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device: RANSAC scoring has no CPU path"); return nullptr; }
@@ -186,49 +179,26 @@ RansacGpu *ransac_gpu() {
 }
 
 bool ransac_ws_reserve(RansacGpu *ws, int len, int n_hyp) {
-  if ((size_t)len * 6 > ws->u_cap) {
-    if (ws->u_dev) RS_CHECK(hipFree(ws->u_dev));
-    ws->u_cap = (size_t)len * 6 * 2;
-    if (ws->u_cap < 6 * 16384) ws->u_cap = 6 * 16384;
-    RS_CHECK(hipMalloc(&ws->u_dev, ws->u_cap * sizeof(double)));
-  }
+  RS_CHECK(ws->u_dev.reserve((size_t)len * 6, std::max<size_t>((size_t)len * 6 * 2, 6 * 16384)));
   if (n_hyp > ws->hyp_cap) {
-    if (ws->hyp_dev) { RS_CHECK(hipFree(ws->hyp_dev)); RS_CHECK(hipHostFree(ws->hyp_host));
-                       RS_CHECK(hipFree(ws->J_dev)); RS_CHECK(hipHostFree(ws->J_host)); }
-    ws->hyp_cap = 64;
-    while (ws->hyp_cap < n_hyp) ws->hyp_cap *= 2;
-    n_hyp = ws->hyp_cap;
-    RS_CHECK(hipMalloc(&ws->hyp_dev, (size_t)HYP_SLOT_BYTES * n_hyp));
-    RS_CHECK(hipHostMalloc(&ws->hyp_host, (size_t)HYP_SLOT_BYTES * n_hyp));
-    // J[hyp_cap] | counts[2 * hyp_cap] in ONE allocation on either side: the scores of a batch come back in one copy
-    RS_CHECK(hipMalloc(&ws->J_dev, 2 * sizeof(double) * n_hyp));
-    RS_CHECK(hipHostMalloc(&ws->J_host, 2 * sizeof(double) * n_hyp));
-    ws->counts_dev = (int *)(ws->J_dev + n_hyp);
-    ws->counts_host = (int *)(ws->J_host + n_hyp);
+    ws->hyp_cap = 0;
+    size_t cap = 64;
+    while (cap < (size_t)n_hyp) cap *= 2;
+    RS_CHECK(reserve_group(ws->hyp_dev, HYP_SLOT_BYTES * cap, ws->hyp_host, HYP_SLOT_BYTES * cap, ws->J_dev, 2 * cap, ws->J_host, 2 * cap));
     // on the workspace's own stream: a memset on the legacy stream is refused while ANY blocking stream of the process is being
     // captured (another thread recording a context's launch chain), and it would wait for every blocking stream besides
-    RS_CHECK(hipMemsetAsync(ws->J_dev, 0, 2 * sizeof(double) * n_hyp, ws->stream));
+    RS_CHECK(hipMemsetAsync(ws->J_dev, 0, 2 * sizeof(double) * cap, ws->stream));
     RS_CHECK(mods::stream_wait(ws->stream));
     ws->counts_dirty = false;
-    ws->dg_cap = 0;
+    ws->hyp_cap = (int)cap;
   }
   // hipFree / hipMalloc synchronise the whole device (20+ ms under a running pipeline): grow in powers of two from a
   // floor that covers an ordinary pair, so that a worker stops reallocating after its first call
   size_t len_cap = 16384;
   while (len_cap < (size_t)len) len_cap *= 2;
   const size_t need = len_cap * ws->hyp_cap;
-  if (need > ws->dg_cap) {
-    if (ws->d_dev) { RS_CHECK(hipFree(ws->d_dev)); RS_CHECK(hipFree(ws->gain_dev)); }
-    ws->dg_cap = need;
-    RS_CHECK(hipMalloc(&ws->d_dev, need * sizeof(double)));
-    RS_CHECK(hipMalloc(&ws->gain_dev, need * sizeof(double)));
-  }
-  if ((size_t)len > ws->row_cap) {
-    if (ws->row_host) RS_CHECK(hipHostFree(ws->row_host));
-    ws->row_cap = (size_t)len * 2;
-    if (ws->row_cap < 16384) ws->row_cap = 16384;
-    RS_CHECK(hipHostMalloc(&ws->row_host, ws->row_cap * sizeof(double)));
-  }
+  RS_CHECK(reserve_group(ws->d_dev, need, ws->gain_dev, need));
+  RS_CHECK(ws->row_host.reserve((size_t)len, std::max<size_t>((size_t)len * 2, 16384)));
   return true;
 }
 
@@ -236,7 +206,7 @@ bool ransac_ws_reserve(RansacGpu *ws, int len, int n_hyp) {
 // after it has read them.  A round that fails between its score and gain launches (or is abandoned) leaves counts behind; the
 // flag makes the next round of this workspace clear them first.
 bool ransac_counts_begin(RansacGpu *ws) {
-  if (ws->counts_dirty) RS_CHECK(hipMemsetAsync(ws->counts_dev, 0, 2 * sizeof(int) * (size_t)ws->hyp_cap, ws->stream));
+  if (ws->counts_dirty) RS_CHECK(hipMemsetAsync(ws->counts_dev(), 0, 2 * sizeof(int) * (size_t)ws->hyp_cap, ws->stream));
   ws->counts_dirty = true;      // until the gain kernel of this round has run and been waited for
   return true;
 }
@@ -245,12 +215,12 @@ bool ransac_counts_begin(RansacGpu *ws) {
 static bool gpu_score(RansacGpu *ws, int len, int n, int err_type, int do_sym, double th, double th_check) {
   if (!ransac_counts_begin(ws)) return false;
   RS_CHECK(hipMemcpyAsync(ws->hyp_dev, ws->hyp_host, sizeof(HypDev) * n, hipMemcpyHostToDevice, ws->stream));
-  hipLaunchKernelGGL(ransac_score_kernel, dim3((len + 255) / 256, n), dim3(256), 0, ws->stream, ws->u_dev, len, (const HypDev *)ws->hyp_dev, err_type,
-                     do_sym, th, th_check, ws->d_dev, ws->gain_dev, ws->hyp_cap, ws->counts_dev);
-  if (n <= GAIN_FEW) hipLaunchKernelGGL(ransac_gain_few_kernel, dim3(1), dim3(256), 0, ws->stream, ws->gain_dev, len, n, ws->hyp_cap, ws->counts_dev, ws->J_host,
-                     ws->counts_host);
-  else hipLaunchKernelGGL(ransac_gain_kernel, dim3((n + 63) / 64), dim3(256), 0, ws->stream, ws->gain_dev, len, n, ws->hyp_cap, ws->counts_dev, ws->J_host,
-                     ws->counts_host);
+  hipLaunchKernelGGL(ransac_score_kernel, dim3((len + 255) / 256, n), dim3(256), 0, ws->stream, ws->u_dev, len, (const HypDev *)ws->hyp_dev.get(), err_type,
+                     do_sym, th, th_check, ws->d_dev, ws->gain_dev, ws->hyp_cap, ws->counts_dev());
+  if (n <= GAIN_FEW) hipLaunchKernelGGL(ransac_gain_few_kernel, dim3(1), dim3(256), 0, ws->stream, ws->gain_dev, len, n, ws->hyp_cap, ws->counts_dev(), ws->J_host,
+                     ws->counts_host());
+  else hipLaunchKernelGGL(ransac_gain_kernel, dim3((n + 63) / 64), dim3(256), 0, ws->stream, ws->gain_dev, len, n, ws->hyp_cap, ws->counts_dev(), ws->J_host,
+                     ws->counts_host());
   RS_CHECK(hipGetLastError());
   RS_CHECK(mods::stream_wait(ws->stream));
   ws->counts_dirty = false;
@@ -326,7 +296,7 @@ int mods_ransac_warmup(int device, int len) {
   RansacGpu *ws = ransac_gpu();
   if (!ws) return MODS_E_NODEVICE;
   if (!ransac_ws_reserve(ws, len > 0 ? len : 1, 64)) return MODS_E_HIP;
-  hipLaunchKernelGGL(ransac_gain_kernel, dim3(1), dim3(256), 0, ws->stream, ws->gain_dev, 0, 0, ws->hyp_cap, ws->counts_dev, ws->J_host, ws->counts_host);   // loads the code object
+  hipLaunchKernelGGL(ransac_gain_kernel, dim3(1), dim3(256), 0, ws->stream, ws->gain_dev, 0, 0, ws->hyp_cap, ws->counts_dev(), ws->J_host, ws->counts_host());   // loads the code object
   if (mods::stream_wait(ws->stream) != hipSuccess) { set_error("ransac warm-up failed"); return MODS_E_HIP; }
   return MODS_OK;
 }
@@ -793,7 +763,7 @@ static Score ransac_h_run(double *u, int len, double th, double conf, int max_sa
       if (std::fabs(v / tol) < 10e-2) continue;     // close to singular
       memcpy(sm.h, sol, sizeof(sm.h));
       sm.valid = 1;
-      HypDev *hyp_host = (HypDev *)ws->hyp_host;
+      HypDev *hyp_host = (HypDev *)ws->hyp_host.get();
       HypDev &hd = hyp_host[n_valid];
       memcpy(hd.h, sol, sizeof(hd.h));
       rs::SymH sh; rs::sym_prepare(sol, &sh);
@@ -810,11 +780,11 @@ static Score ransac_h_run(double *u, int len, double th, double conf, int max_sa
         custom_d.resize((size_t)n_valid * len);
         for (int kq = 0; kq < n_valid; kq++) {
           double *dd = custom_d.data() + (size_t)kq * len;
-          custom(nullptr, u, ((HypDev *)ws->hyp_host)[kq].h, dd, len);
+          custom(nullptr, u, ((HypDev *)ws->hyp_host.get())[kq].h, dd, len);
           unsigned I = 0, Is = 0; double J = 0;
           for (int j = 0; j < len; j++) { if (dd[j] <= th) I++; J += rs::trunc_quad(dd[j], th); }
-          if (doSymCheck) { HDsSym(nullptr, u, ((HypDev *)ws->hyp_host)[kq].h, d_check.data(), len); for (int j = 0; j < len; j++) if (d_check[j] <= th_check) Is++; }
-          ws->counts_host[2 * kq] = (int)I; ws->counts_host[2 * kq + 1] = (int)Is; ws->J_host[kq] = J;
+          if (doSymCheck) { HDsSym(nullptr, u, ((HypDev *)ws->hyp_host.get())[kq].h, d_check.data(), len); for (int j = 0; j < len; j++) if (d_check[j] <= th_check) Is++; }
+          ws->counts_host()[2 * kq] = (int)I; ws->counts_host()[2 * kq + 1] = (int)Is; ws->J_host[kq] = J;
         }
       } else if (!gpu_score(ws, len, n_valid, err_type, doSymCheck, th, th_check)) ransac_fail();
     }
@@ -832,12 +802,12 @@ static Score ransac_h_run(double *u, int len, double th, double conf, int max_sa
       if (sm.valid == 0) continue;
       const int slot = sm.valid - 1;
       bool new_max = false;
-      S.I = (unsigned)ws->counts_host[2 * slot];
+      S.I = (unsigned)ws->counts_host()[2 * slot];
       S.J = ws->J_host[slot];
       double *d = L.errs[0];
       bool have_d = false;
       if (rs::score_less(maxS, S)) {
-        if (doSymCheck) bad_model = (unsigned)ws->counts_host[2 * slot + 1] <= MIN_GOOD_SYM_PTS;
+        if (doSymCheck) bad_model = (unsigned)ws->counts_host()[2 * slot + 1] <= MIN_GOOD_SYM_PTS;
         if (bad_model) continue;
         fetch_row(slot, d); have_d = true;
         L.errs[0] = L.errs[3];

@@ -150,10 +150,10 @@ static bool gpu_score_f(RansacGpu *ws, int len, int n, int err_type, int do_sym,
   // (device counters: zero on entry, read out to the host's pinned result block and cleared again by ransac_gain_kernel; ransac.hip)
   if (!ransac_counts_begin(ws)) return false;
   RS_CHECK(hipMemcpyAsync(ws->hyp_dev, ws->hyp_host, sizeof(HypF) * n, hipMemcpyHostToDevice, ws->stream));
-  hipLaunchKernelGGL(ransacf_score_kernel, dim3((len + 255) / 256, n), dim3(256), 0, ws->stream, ws->u_dev, len, (const HypF *)ws->hyp_dev,
-                     err_type, do_sym, th, th_check, ws->d_dev, ws->gain_dev, ws->hyp_cap, ws->counts_dev);
-  hipLaunchKernelGGL(ransac_gain_kernel, dim3((n + 63) / 64), dim3(256), 0, ws->stream, ws->gain_dev, len, n, ws->hyp_cap, ws->counts_dev, ws->J_host,
-                     ws->counts_host);
+  hipLaunchKernelGGL(ransacf_score_kernel, dim3((len + 255) / 256, n), dim3(256), 0, ws->stream, ws->u_dev, len, (const HypF *)ws->hyp_dev.get(),
+                     err_type, do_sym, th, th_check, ws->d_dev, ws->gain_dev, ws->hyp_cap, ws->counts_dev());
+  hipLaunchKernelGGL(ransac_gain_kernel, dim3((n + 63) / 64), dim3(256), 0, ws->stream, ws->gain_dev, len, n, ws->hyp_cap, ws->counts_dev(), ws->J_host,
+                     ws->counts_host());
   RS_CHECK(hipGetLastError());
   RS_CHECK(mods::stream_wait(ws->stream));
   ws->counts_dirty = false;
@@ -194,15 +194,23 @@ struct SimdEval : rs::PointEval {
 
 // off-plane set of rFtH (uN) and its plane-transferred form (us, may be null) -> aux_dev: uN in the first half of the buffer, us behind it
 static bool gpu_upload_aux(RansacGpu *ws, const double *uN, const double *us, unsigned n) {
-  if ((size_t)n * 12 > ws->aux_cap) {
-    if (ws->aux_dev) RS_CHECK(hipFree(ws->aux_dev));
-    ws->aux_cap = (size_t)n * 12 * 2;
-    RS_CHECK(hipMalloc(&ws->aux_dev, ws->aux_cap * sizeof(double)));
-  }
+  RS_CHECK(ws->aux_dev.reserve((size_t)n * 12, (size_t)n * 12 * 2));
   RS_CHECK(hipMemcpyAsync(ws->aux_dev, uN, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ws->stream));
   if (us) RS_CHECK(hipMemcpyAsync(ws->aux_dev + (size_t)6 * n, us, sizeof(double) * 6 * n, hipMemcpyHostToDevice, ws->stream));
   RS_CHECK(mods::stream_wait(ws->stream));
   return true;
+}
+// Two mapped host buffers of one capacity count and their device addresses; a failure leaves the buffers empty and the addresses null
+template <class A, class B>
+static bool reserve_mapped_pair(MappedBuf<A> &a, size_t na, A *&a_dev, MappedBuf<B> &b, size_t nb, B *&b_dev) {
+  a_dev = nullptr; b_dev = nullptr;
+  hipError_t e = reserve_group(a, na, b, nb);
+  if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&a_dev, a.get(), 0);
+  if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&b_dev, b.get(), 0);
+  if (e == hipSuccess) return true;
+  a.release(); b.release(); a_dev = nullptr; b_dev = nullptr;
+  set_error("mapped host buffers of the F verification: %s", hipGetErrorString(e));
+  return false;
 }
 // Count of k candidates given as index pairs into the off-plane set (pairs: 2 k unsigned; us sits behind uN in aux_dev), in two
 // calls with a buffer slot (0 / 1) between them: begin queues upload, count and copy back on the workspace's stream and records the
@@ -210,16 +218,13 @@ static bool gpu_upload_aux(RansacGpu *ws, const double *uN, const double *us, un
 static bool gpu_count_pairs_begin(RansacGpu *ws, int slot, unsigned n, const unsigned *pairs, int k, const double *Ht, double limit) {
   if (k > ws->cand_cap) {
     RS_CHECK(hipStreamSynchronize(ws->stream));                            // (no slot is in flight when the first block of a call is the largest)
-    if (ws->cand_host) { RS_CHECK(hipHostFree(ws->cand_host)); RS_CHECK(hipHostFree(ws->candc_host)); }
-    const int cap = k > 2048 ? k : 2048;                                   // rFtH's block size: never grown with a slot in flight
-    ws->cand_cap = cap;
+    const size_t cap = k > 2048 ? k : 2048;                                // rFtH's block size: never grown with a slot in flight
+    ws->cand_cap = 0;
     // both in pinned host memory the kernel addresses itself (16 KB of index pairs in, 8 KB of counts out per block): a block of
     // candidates is ONE launch and one event, no copies to queue - the calls, not the work, were the cost of a block here
     // (coherent: what the kernel writes is in host memory when its event has completed, whatever HIP_HOST_COHERENT says)
-    RS_CHECK(hipHostMalloc(&ws->cand_host, sizeof(unsigned) * 2 * 2 * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    RS_CHECK(hipHostMalloc(&ws->candc_host, sizeof(int) * 2 * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    RS_CHECK(hipHostGetDevicePointer((void **)&ws->cand_dev, ws->cand_host, 0));
-    RS_CHECK(hipHostGetDevicePointer((void **)&ws->candc_dev, ws->candc_host, 0));
+    if (!reserve_mapped_pair(ws->cand_host, 2 * 2 * cap, ws->cand_dev, ws->candc_host, 2 * cap, ws->candc_dev)) return false;
+    ws->cand_cap = (int)cap;
   }
   if (!ws->cand_ev[slot]) RS_CHECK(hipEventCreateWithFlags(&ws->cand_ev[slot], hipEventDisableTiming));
   memcpy(ws->cand_host + (size_t)slot * 2 * ws->cand_cap, pairs, sizeof(unsigned) * 2 * k);
@@ -235,13 +240,10 @@ static bool gpu_count_pairs_begin(RansacGpu *ws, int slot, unsigned n, const uns
 // the models of one round of innerFH samples counted over the run's correspondences (ws->u_dev), see ransacf_count_models_kernel
 static bool gpu_count_models(RansacGpu *ws, int len, const double *Fs, int k, double limit, unsigned *counts) {
   if (k > ws->cntf_cap) {
-    if (ws->cntf_host) { RS_CHECK(hipHostFree(ws->cntf_host)); RS_CHECK(hipHostFree(ws->cntc_host)); }
-    const int cap = k > 256 ? k : 256;
-    ws->cntf_cap = cap;
-    RS_CHECK(hipHostMalloc(&ws->cntf_host, sizeof(double) * 9 * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    RS_CHECK(hipHostMalloc(&ws->cntc_host, sizeof(int) * COUNT_PARTS * cap, hipHostMallocMapped | hipHostMallocCoherent));
-    RS_CHECK(hipHostGetDevicePointer((void **)&ws->cntf_dev, ws->cntf_host, 0));
-    RS_CHECK(hipHostGetDevicePointer((void **)&ws->cntc_dev, ws->cntc_host, 0));
+    const size_t cap = k > 256 ? k : 256;
+    ws->cntf_cap = 0;
+    if (!reserve_mapped_pair(ws->cntf_host, 9 * cap, ws->cntf_dev, ws->cntc_host, COUNT_PARTS * cap, ws->cntc_dev)) return false;
+    ws->cntf_cap = (int)cap;
   }
   memcpy(ws->cntf_host, Fs, sizeof(double) * 9 * k);
   hipLaunchKernelGGL(ransacf_count_models_kernel, dim3(k, COUNT_PARTS), dim3(256), 0, ws->stream, (const double *)ws->u_dev, len, (const double *)ws->cntf_dev,
@@ -604,7 +606,7 @@ static int ransac_f_run(double *u, int len, double th, double conf, int max_sam,
     if (want > max_sam - no_sam) want = max_sam - no_sam;
     batch.resize(want);
     if (!ransac_ws_reserve(ws, len, 3 * want)) F_FATAL();
-    HypF *hyp_host = (HypF *)ws->hyp_host;
+    HypF *hyp_host = (HypF *)ws->hyp_host.get();
     int n_hyp = 0;
     const double tg0 = prof ? wall_ms() : 0;
     for (int b = 0; b < want; b++) {
@@ -651,13 +653,13 @@ static int ransac_f_run(double *u, int len, double th, double conf, int max_sam,
           unsigned I = 0, Is = 0; double J = 0;
           for (int j = 0; j < len; j++) { if (dd[j] <= th) I++; J += rs::trunc_quad(dd[j], th); }
           if (doSymCheck) { FDsSym(u, hyp_host[kq].f, d_check.data(), len); for (int j = 0; j < len; j++) if (d_check[j] <= th_check) Is++; }
-          ws->counts_host[2 * kq] = (int)I; ws->counts_host[2 * kq + 1] = (int)Is; ws->J_host[kq] = J;
+          ws->counts_host()[2 * kq] = (int)I; ws->counts_host()[2 * kq + 1] = (int)Is; ws->J_host[kq] = J;
         }
       } else if (!gpu_score_f(ws, len, n_hyp, err_type, doSymCheck, th, th_check)) F_FATAL();
     }
     if (prof) t_score += wall_ms() - tg1;
-    std::vector<int> cnt(ws->counts_host, ws->counts_host + 2 * n_hyp);
-    std::vector<double> Jv(ws->J_host, ws->J_host + n_hyp);
+    std::vector<int> cnt(ws->counts_host(), ws->counts_host() + 2 * n_hyp);
+    std::vector<double> Jv(ws->J_host.get(), ws->J_host.get() + n_hyp);
     auto fetch_row = [&](int slot, double *dst) {
       if (err_type < 0) memcpy(dst, host_d.data() + (size_t)slot * len, sizeof(double) * len);
       else if (!ransac_fetch_row(ws, len, slot, dst)) F_FATAL();

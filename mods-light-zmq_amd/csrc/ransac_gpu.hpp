@@ -3,30 +3,45 @@
 #pragma once
 #include "common.hpp"
 #include <mutex>
+#include <sys/syscall.h>
+#include <unistd.h>
 
 namespace mods {
 
 struct RansacGpu {
   int device = -1;
   hipStream_t stream = nullptr;
-  double *u_dev = nullptr; size_t u_cap = 0;
-  void *hyp_dev = nullptr; void *hyp_host = nullptr; int hyp_cap = 0;   // hyp_cap slots of HYP_SLOT_BYTES
-  double *d_dev = nullptr; double *gain_dev = nullptr; size_t dg_cap = 0;
-  int *counts_dev = nullptr; double *J_dev = nullptr;
-  int *counts_host = nullptr; double *J_host = nullptr;
+  Buf<double> u_dev;
+  // hyp_cap slots: hypotheses of HYP_SLOT_BYTES on either side, and J[hyp_cap] | counts[2 * hyp_cap] in ONE allocation on either
+  // side (the scores of a batch come back in one copy).  hyp_cap is set once all four hold that many
+  Buf<char> hyp_dev; PinnedBuf<char> hyp_host; Buf<double> J_dev; PinnedBuf<double> J_host; int hyp_cap = 0;
+  int *counts_dev() const { return (int *)(J_dev + hyp_cap); }
+  int *counts_host() const { return (int *)(J_host + hyp_cap); }
+  Buf<double> d_dev, gain_dev;                          // [len_cap][hyp_cap], reserved together
   bool counts_dirty = false;                            // a scoring round did not complete: counts_dev is cleared before the next one
-  double *row_host = nullptr; size_t row_cap = 0;
-  double *aux_dev = nullptr; size_t aux_cap = 0;        // second point set (off-plane correspondences of rFtH)
+  PinnedBuf<double> row_host;
+  Buf<double> aux_dev;                                  // second point set (off-plane correspondences of rFtH)
   // two-point candidates of rFtH as index pairs and their counts: two slots of cand_cap candidates each (a block is counted while
-  // the next one is drawn), an event per slot behind its count's copy back
-  unsigned int *cand_dev = nullptr, *cand_host = nullptr;
-  int *candc_dev = nullptr, *candc_host = nullptr; int cand_cap = 0;
+  // the next one is drawn), an event per slot behind its count's copy back.  The host writes and reads them in place (mapped
+  // memory); *_dev is the device address of *_host and null whenever that is empty
+  MappedBuf<unsigned int> cand_host; MappedBuf<int> candc_host; int cand_cap = 0;
+  unsigned int *cand_dev = nullptr; int *candc_dev = nullptr;
   hipEvent_t cand_ev[2] = {nullptr, nullptr};
   // models counted over all correspondences in one launch (innerFH's samples): k x 9 doubles in, k x COUNT_PARTS partial counts out,
   // both in mapped host memory
-  double *cntf_host = nullptr, *cntf_dev = nullptr; int *cntc_host = nullptr, *cntc_dev = nullptr; int cntf_cap = 0;
+  MappedBuf<double> cntf_host; MappedBuf<int> cntc_host; int cntf_cap = 0;
+  double *cntf_dev = nullptr; int *cntc_dev = nullptr;
   double score_ms = 0; long launches = 0;
-  ~RansacGpu();
+  ~RansacGpu();                                         // events and the stream; the buffers free themselves
+};
+
+// A workspace of the calling thread, made at its first use.  A worker thread returns its HBM when it ends; the main thread's copy
+// would be destroyed during process exit, when the HIP runtime (or a profiler layered on it) may already be shutting down and a
+// hipFree can block forever - the process is going away, so the main thread's workspace is leaked on purpose.
+template <class W> struct ThreadWorkspace {
+  W *ws = nullptr;
+  W &get() { if (!ws) ws = new W(); return *ws; }
+  ~ThreadWorkspace() { if ((long)getpid() != (long)syscall(SYS_gettid)) delete ws; }
 };
 enum { HYP_SLOT_BYTES = 27 * 8 };   // largest hypothesis record (homography + its two symmetric operands)
 

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void blur_table_kernel(int ps, float *__restri
 // previous table
 int launch_blur_table(mods_ctx *ctx, int ps) {
   if (ctx->blur_table_ps == ps && ctx->blur_table_dev) return MODS_OK;
-  if (!ctx->blur_table_dev) MODS_HIP_CHECK(hipMalloc(&ctx->blur_table_dev, sizeof(float) * (SMALL_CAP + 1) * BT_ENTRY));
+  MODS_HIP_CHECK(ctx->blur_table_dev.reserve((size_t)(SMALL_CAP + 1) * BT_ENTRY));
   mods::dev_state_changed(ctx);      // (device state changes: the next detect + describe call is not a repeat - capi.hip: dd_run)
   hipLaunchKernelGGL(blur_table_kernel, dim3(SMALL_CAP + 1), dim3(256), 0, ctx->stream, ps, ctx->blur_table_dev);
   MODS_HIP_CHECK(hipGetLastError());
@@ -1557,13 +1557,7 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
   const unsigned long long area_units = std::max<unsigned long long>(1, ((unsigned long long)k.w * k.h + (1ull << 21) - 1) >> 21);
   const unsigned long long pool_elems = std::max<unsigned long long>(256ull << 20, (unsigned long long)n_img * area_units * (64ull << 20));
   const size_t need = patch_elems + book_elems + pool_elems;
-  if (need > ctx->desc_scratch_elems) {
-    MODS_HIP_CHECK(mods::stream_wait(ctx->stream));
-    if (ctx->desc_scratch) MODS_HIP_CHECK(hipFree(ctx->desc_scratch));
-    ctx->desc_scratch = nullptr;
-    mods::dev_pool_reallocated(ctx); MODS_HIP_CHECK(hipMalloc(&ctx->desc_scratch, need * sizeof(float)));
-    ctx->desc_scratch_elems = need;
-  }
+  MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->desc_scratch, need, need));
   float *patches = ctx->desc_scratch;
   BigLists *bl = (BigLists *)(ctx->desc_scratch + patch_elems);
   BigRegion *bregs = (BigRegion *)(bl + 1);
@@ -1664,7 +1658,7 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
 
 int launch_half_sift(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, const SiftTab *tab) {
   StageScope ts(ctx, MODS_STAGE_DESCRIBE);
-  if (!ctx->regions_half_dev) MODS_HIP_CHECK(hipMalloc(&ctx->regions_half_dev, sizeof(mods_region) * (size_t)ctx->max_cand * ctx->batch));
+  MODS_HIP_CHECK(ctx->regions_half_dev.reserve((size_t)ctx->max_cand * ctx->batch));
   MODS_HIP_CHECK(hipMemcpyAsync(ctx->regions_half_dev, ctx->regions_dev, sizeof(mods_region) * (size_t)ctx->max_cand * n_img,
                                 hipMemcpyDeviceToDevice, ctx->stream));
   k.half_desc = 1;

@@ -254,7 +254,7 @@ int mods_gauss_blur_xy(mods_ctx *c, const float *src, int w, int h, int kx, int 
   if (!c || !src || !dst) { set_error("gauss_blur_xy: null argument"); return MODS_E_ARG; }
   if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("image larger than the context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  if (!c->view_dev) MODS_HIP_CHECK(hipMalloc(&c->view_dev, sizeof(float) * (size_t)c->max_w * c->max_h * c->batch));
+  MODS_HIP_CHECK(c->view_dev.reserve((size_t)c->max_w * c->max_h * c->batch));
   MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev, src, sizeof(float) * (size_t)w * h, hipMemcpyHostToDevice, c->stream));
   int rc = launch_blur_xy_reflect(c, c->input_dev, c->tmp_dev, c->view_dev, w, h, kx, ky, sx, sy);
   if (rc) return rc;
@@ -283,7 +283,7 @@ static int view_detect_describe(mods_ctx *c, const float *const *src_dev, int n_
     c->last_inside_counts.assign(n_src, 0);
     return MODS_OK;
   }
-  if (!c->view_dev) MODS_HIP_CHECK(hipMalloc(&c->view_dev, sizeof(float) * (size_t)c->max_w * c->max_h * c->batch));
+  MODS_HIP_CHECK(c->view_dev.reserve((size_t)c->max_w * c->max_h * c->batch));
   const size_t vpx = (size_t)g.w_new * g.h_new;
   for (int i = 0; i < n_src; i++)
     if ((rc = mods_synth_view_dev(c, src_dev[i], w, h, stride, &g, doBlur, c->view_dev + i * vpx))) return rc;

@@ -195,3 +195,23 @@ def test_matrix_core_kernels_own_their_simds(pkg):
         assert k["wg_size"] % 256 == 0 and waves_of_wg_per_simd >= 1, (k["name"], k["wg_size"])
         assert k["alloc"] * waves_of_wg_per_simd == 512, (k["name"], k["vgpr"], k["alloc"], k["wg_size"])
         assert k["scratch"] == 0, (k["name"], k["scratch"])
+
+
+def test_buffer_growth_and_failure_paths(pkg):
+    """csrc/buffer.hpp through mods_test_buffer_growth: the owning buffer over a memory policy that counts calls and fails on a
+    chosen allocation (no device).  The report's entries are described in include/mods_hip.h."""
+    lib = pkg.lib()
+    n = 16
+    r = (C.c_int * n)()
+    assert lib.mods_test_buffer_growth(r, 4) < 0                  # a report that is too short is refused
+    assert lib.mods_test_buffer_growth(r, n) == n
+    r = list(r)
+    assert r[0] == 0                                              # 1. a reserve below the capacity neither allocates nor frees
+    assert (r[1], r[2]) == (1, 1)                                 # 2. a growth frees once and allocates once
+    assert (r[3], r[4], r[5]) == (1, 0, 1)                        # 3. a failed growth: get() == nullptr, capacity() == 0, old freed once
+    assert r[6] == 1                                              #    ... and the next reserve allocates again
+    assert r[7] == 1                                              # 4. move construction / assignment, swap, detach behave
+    assert r[11] == 0 and r[12] == 0                              #    nothing freed twice, nothing left alive
+    assert r[13] == r[14] > 10                                    #    every allocation freed exactly once
+    assert r[8] == 0                                              # 5. a failed group reservation empties the whole group
+    assert r[9] == 1 and r[10] == r[15] == 4
