@@ -136,6 +136,7 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_MATCH_NN1,    /* the matrix-core kernel of the search alone (match_nn1_kernel, i8 MFMA), inside MODS_STAGE_MATCH */
        MODS_STAGE_EXTRACT,      /* measurement-region extraction alone (classify .. column pass + resampling), inside MODS_STAGE_DESCRIBE */
        MODS_STAGE_SIFT,         /* the SIFT kernels alone, inside MODS_STAGE_DESCRIBE */
+       MODS_STAGE_GUIDED,       /* a guided search (mods_match_guided[_reps]): pack, both gate sweeps, accept, compaction and emit */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -765,6 +766,49 @@ int mods_pipeline_next(mods_pipeline *p, mods_pair_result *res, long *tag);
  * min(res->n_inliers, max_matches) rows are written */
 int mods_pipeline_next_matches(mods_pipeline *p, mods_pair_result *res, long *tag, double *matches_out, int max_matches);
 void mods_pipeline_destroy(mods_pipeline *p);
+
+/* ---- guided matching under a verified model ----------------------------------------------------------
+ * No counterpart in the reference.  After a verification has produced a model (mods_pair_result.H / mods_ladder_result.H), every
+ * query region is matched again, but only against the trains that the model allows ("the gate"), which recovers the
+ * correspondences the global FGINN test at ratio 0.8 over all trains discards.  csrc/guided.hip.
+ *
+ * All geometry is fp64, one rounding per operation, in the order written; a sum of three terms is (a*b + c*d) + e; r2 = radius *
+ * radius, rho2 = ratio * ratio.  Mij = entry (i, j) of the model: model_type 0, H row-major image 1 -> image 2, Mij = model[3*i + j];
+ * model_type 1, F as degensac stores it (x2^T F x1 = 0), Mij = model[3*j + i].
+ *   Homography gate.  Hinv = adjugate(H) * (1 / det H), the closed form of cv::invert for 3 x 3.  Per query (x1, y1):
+ *     X = (M00*x1 + M01*y1) + M02, Y = (M10*x1 + M11*y1) + M12, W = (M20*x1 + M21*y1) + M22, px = X / W, py = Y / W; per train
+ *     (x2, y2): (bx, by) the same with Hinv.  A pair passes when (px-x2)*(px-x2) + (py-y2)*(py-y2) <= r2 and
+ *     (bx-x1)*(bx-x1) + (by-y1)*(by-y1) <= r2.  Comparisons with NaN or infinity fail (W = 0 gates nothing).
+ *   Epipolar gate.  Per query a = (M00*x1 + M01*y1) + M02, b = (M10*x1 + M11*y1) + M12, c0 = (M20*x1 + M21*y1) + M22,
+ *     gq = r2 * (a*a + b*b); per train a' = (M00*x2 + M10*y2) + M20, b' = (M01*x2 + M11*y2) + M21, gt = r2 * (a'*a' + b'*b');
+ *     per pair e = (a*x2 + b*y2) + c0: passes when e*e <= gq and e*e <= gt (within `radius` of the epipolar line in both images).
+ *   Distance d(q, t) = sum over the 128 descriptor bytes of (dq[i] - dt[i])^2, an exact integer.
+ *   Per query: (d1, t1) = the smallest (d, t) over the gated trains (ties: lower train index); (d2, t_bad) = the smallest (d, t)
+ *     over the gated trains t != t1 whose centre lies farther than contradDist from t1's: (x2-x2')^2 + (y2-y2')^2 > contradDist^2.
+ *     Accepted when (max_dist == 0 or d1 <= max_dist) and (no t_bad, or (double)d1 < rho2 * (double)d2).
+ *   one_to_one: of the accepted queries that chose the same train only the one with the smallest (d1, q) stays; the others are
+ *     dropped, not re-assigned.
+ *   Output in query order: q, t = t1, t_bad (-1: none), t_2nd = -1, d1, d2 (0: none), d2nd = 0, ratio = sqrt((double)d1 /
+ *     (double)d2) (0: none); u6 / laf as mods_match_fginn lays them out.  The result does not depend on launch geometry.
+ * MODS_E_ARG with a mods_last_error text, before any device call: a null pointer, model_type not 0 or 1, a model entry that is
+ * not finite, a homography whose determinant is 0 (or not finite), radius not finite or <= 0, ratio outside (0, 1], contradDist
+ * negative or not finite, max_dist < 0, a negative count.  A result longer than max_out: as mods_match_fginn, *n_out = the full
+ * length, MODS_E_CAPACITY, and nothing is copied.  The search has buffers of its own: it leaves the matcher's "last search" alone. */
+typedef struct mods_guided_params {
+  int model_type;        /* 0 homography, 1 fundamental matrix */
+  double model[9];       /* as mods_pair_result.H / mods_ladder_result.H deliver it */
+  double radius;         /* px */
+  double ratio;          /* (0, 1]; 1 = only the strict d1 < d2 test */
+  double contradDist;    /* px, [Matching] contradDist */
+  int max_dist;          /* squared L2 cap, 0 = none */
+  int one_to_one;
+} mods_guided_params;
+int mods_match_guided(mods_ctx *ctx, const mods_region *q, int n_q, const mods_region *t, int n_t,
+                      const mods_guided_params *par, mods_tentative *out, double *u6_out, double *laf_out,
+                      int max_out, int *n_out);                       /* host lists, the testing seam */
+int mods_match_guided_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgrep *t,
+                           const mods_guided_params *par, mods_tentative *out, double *u6_out, double *laf_out,
+                           int max_out, int *n_out);                  /* HBM-resident banks */
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MODS_LIB") or os.path.join(PKG_DIR, "libmodsgpu.so")
 
 MODS_OK = 0
 STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "orient", "describe", "match",
-          "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift"]
+          "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided"]
 
 
 class ModsError(RuntimeError):
@@ -563,6 +563,19 @@ class Context:
                                          u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return out[:n.value].copy(), u6[:n.value].copy()
 
+    def match_guided(self, q, t, params):
+        """mods_match_guided: the model-guided search of two host region lists (GuidedParams); returns (tent, u6, laf)."""
+        q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
+        cap = max(len(q), 1)
+        out = np.zeros(cap, TENT_DTYPE)
+        u6 = np.zeros((cap, 6), np.float64)
+        laf = np.zeros((cap, 14), np.float64)
+        n = C.c_int()
+        _check(lib().mods_match_guided(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
+                                       C.byref(params), out.ctypes.data_as(C.c_void_p), u6.ctypes.data_as(C.c_void_p),
+                                       laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+
     def clahe(self, img_u8, clip_limit=4.0, tiles=(8, 8)):
         """mods_clahe: CLAHE of one 8-bit grey image [h, w] (host in, host out); tiles = (tiles_x, tiles_y)"""
         a = np.ascontiguousarray(img_u8, np.uint8)
@@ -951,6 +964,34 @@ def match_reps(ctx, q, t, q_begin=0, q_end=None, ratio=0.8, contrad=10.0, nn=50)
     _check(lib().mods_match_reps(ctx.h, q.h, q_begin, q_end, t.h, C.c_double(ratio), C.c_double(contrad), nn,
                                  out.ctypes.data_as(C.c_void_p), u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p),
                                  cap, C.byref(n)))
+    return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+
+
+class GuidedParams(C.Structure):
+    """mods_guided_params: the model-guided search behind a verification (no counterpart in the reference)."""
+    _fields_ = [("model_type", C.c_int), ("model", C.c_double * 9), ("radius", C.c_double), ("ratio", C.c_double),
+                ("contradDist", C.c_double), ("max_dist", C.c_int), ("one_to_one", C.c_int)]
+
+    @staticmethod
+    def default(model=None, model_type=0, radius=4.0, ratio=0.9, contrad=10.0, max_dist=0, one_to_one=1):
+        """radius = [RANSAC] err_threshold, contradDist = [Matching] contradDist of config_affori_classic.ini; model: 9 values as
+        PairResult.H / LadderResult.H deliver them (model_type 1: F in degensac's layout)"""
+        p = GuidedParams(model_type, (C.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1), radius, ratio, contrad, max_dist, one_to_one)
+        if model is not None:
+            p.model = (C.c_double * 9)(*[float(v) for v in np.asarray(model, np.float64).reshape(9)])
+        return p
+
+
+def match_guided_reps(ctx, rep_q, rep_t, params, cap=None):
+    """mods_match_guided_reps: the guided search of ImgRep rep_q against ImgRep rep_t (HBM resident); returns (tent, u6, laf).
+    cap: room for that many tentatives (default: one per query, which always suffices)."""
+    cap = max(len(rep_q), 1) if cap is None else cap
+    out = np.zeros(max(cap, 1), TENT_DTYPE)
+    u6 = np.zeros((max(cap, 1), 6), np.float64)
+    laf = np.zeros((max(cap, 1), 14), np.float64)
+    n = C.c_int()
+    _check(lib().mods_match_guided_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p),
+                                        u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
     return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
 
 

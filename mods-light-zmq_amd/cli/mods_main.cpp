@@ -58,6 +58,10 @@ struct Config {
   int load_color = 1;
   int do_clahe = 0;                // [Matching] doCLAHE (io_mods.cpp:526): CLAHE on both 8-bit grey images before detection
   int verbose = 0, time_log = 1, write_keypoints = 1, write_matches = 1, output_h = 0;
+  // [Matching] guidedMatching (no counterpart in the reference): behind the final verification every bank is searched again under
+  // the verified model (mods_match_guided_reps) and the de-duplicated result is what the matches file holds
+  int guided = 0, guided_max_dist = 0, guided_one_to_one = 1;
+  double guided_radius = 0, guided_ratio = 0.9;
   // [zmqDescriptor] (io_mods.cpp:395-407): used when a step asks for the "ZMQ" descriptor instead of RootSIFT
   bool use_zmq = false;
   std::string zmq_port = "tcp://localhost:5555";
@@ -176,6 +180,16 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   // LORANSAC inliers that the ground truth confirms, RANSACforStopping stops the step loop on the RANSAC inlier count
   r.groundTruth = ver_type == 1 ? (ini.GetInteger("Matching", "doBothRANSACgroundTruth", 1) ? 2 : 1) : 0;
   r.ransacForStopping = ini.GetInteger("Matching", "RANSACforStopping", 1) ? 1 : 0;
+  cfg->guided = (int)ini.GetInteger("Matching", "guidedMatching", 0);
+  cfg->guided_radius = ini.GetDouble("Matching", "guidedRadius", r.err_threshold);
+  cfg->guided_ratio = ini.GetDouble("Matching", "guidedRatio", 0.9);
+  cfg->guided_max_dist = (int)ini.GetInteger("Matching", "guidedMaxDist", 0);
+  cfg->guided_one_to_one = (int)ini.GetInteger("Matching", "guidedOneToOne", 1);
+  if (cfg->guided != 0 && cfg->guided != 1) { std::cerr << "[Matching] guidedMatching must be 0 or 1" << std::endl; return 1; }
+  if (!std::isfinite(cfg->guided_radius) || !(cfg->guided_radius > 0)) { std::cerr << "[Matching] guidedRadius must be a positive number of pixels, not " << cfg->guided_radius << std::endl; return 1; }
+  if (!(cfg->guided_ratio > 0 && cfg->guided_ratio <= 1)) { std::cerr << "[Matching] guidedRatio must lie in (0, 1], not " << cfg->guided_ratio << std::endl; return 1; }
+  if (cfg->guided_max_dist < 0) { std::cerr << "[Matching] guidedMaxDist must not be negative (0 = no cap)" << std::endl; return 1; }
+  if (cfg->guided_one_to_one != 0 && cfg->guided_one_to_one != 1) { std::cerr << "[Matching] guidedOneToOne must be 0 or 1" << std::endl; return 1; }
   // [TextOutput], [Computing]
   cfg->time_log = (int)ini.GetInteger("TextOutput", "timeLog", 0);
   cfg->write_keypoints = (int)ini.GetInteger("TextOutput", "writeKeypoints", 1);
@@ -734,6 +748,45 @@ int main(int argc, char **argv) {
                                           cfg.groups.empty() ? nullptr : cfg.groups.data(), cfg.group_pos, (int)cfg.steps.size() / n_det, n_det, cfg.min_matches,
                                           &cfg.pair, reps1.data(), reps2.data(), &res, matches.data(), 1 << 20))
     return fail("matching");
+  // [Matching] guidedMatching = 1: the banks of every detector, in detector order, searched again under the verified model; the
+  // joint list goes through the duplicate filter and replaces the rows of the matches file (the log rows stay the reference's)
+  int n_guided = -1, n_guided_unique = 0;
+  {
+    bool have_model = res.n_inliers > 0;
+    for (int i = 0; i < 9 && have_model; i++) if (!std::isfinite(res.H[i])) have_model = false;
+    bool all_m1 = true;
+    for (int i = 0; i < 9; i++) if (res.H[i] != -1.0) all_m1 = false;
+    if (cfg.guided && multi) std::cerr << "Note: guidedMatching is not run with MODS_DEVICES" << std::endl;
+    else if (cfg.guided && have_model && !all_m1) {
+      mods_guided_params gp;
+      memset(&gp, 0, sizeof(gp));
+      gp.model_type = cfg.pair.ransac.useF ? 1 : 0;
+      for (int i = 0; i < 9; i++) gp.model[i] = res.H[i];
+      gp.radius = cfg.guided_radius; gp.ratio = cfg.guided_ratio; gp.contradDist = cfg.pair.contradDist;
+      gp.max_dist = cfg.guided_max_dist; gp.one_to_one = cfg.guided_one_to_one;
+      std::vector<mods_tentative> gt;
+      std::vector<double> gu, gl;
+      for (int d = 0; d < n_det; d++) {
+        const int cap = mods_imgrep_count(reps1[d]);
+        if (cap <= 0 || mods_imgrep_count(reps2[d]) <= 0) continue;
+        const size_t at = gt.size();
+        gt.resize(at + cap); gu.resize((at + cap) * 6); gl.resize((at + cap) * 14);
+        int m = 0;
+        if (mods_match_guided_reps(ctx, reps1[d], reps2[d], &gp, gt.data() + at, gu.data() + at * 6, gl.data() + at * 14, cap, &m)) return fail("guided matching");
+        gt.resize(at + m); gu.resize((at + m) * 6); gl.resize((at + m) * 14);
+      }
+      n_guided = (int)gt.size();
+      n_guided_unique = n_guided;
+      if (n_guided > 0 && mods_duplicate_filter_gpu(ctx, gt.data(), gu.data(), gl.data(), n_guided, cfg.pair.dup_dist, cfg.pair.dup_mode, &n_guided_unique, nullptr))
+        return fail("guided matching: duplicate filter");
+      if ((size_t)n_guided_unique * 4 > matches.size()) matches.resize((size_t)n_guided_unique * 4);
+      for (int i = 0; i < n_guided_unique; i++) {
+        matches[4 * (size_t)i] = gu[6 * (size_t)i]; matches[4 * (size_t)i + 1] = gu[6 * (size_t)i + 1];
+        matches[4 * (size_t)i + 2] = gu[6 * (size_t)i + 3]; matches[4 * (size_t)i + 3] = gu[6 * (size_t)i + 4];
+      }
+    } else if (cfg.guided && cfg.verbose) std::cerr << "Guided matching: no verified model, skipped" << std::endl;
+  }
+  const int n_written = n_guided >= 0 ? n_guided_unique : res.n_inliers;
   const double final_time = now_s() - c_start;
   const int final_step = res.steps_done <= 0 ? 0 : (hessian_only && !pre_extracted && !multi) ? step_index[res.steps_done - 1] + 1 : res.steps_done;
   if (cfg.verbose) {
@@ -749,6 +802,8 @@ int main(int argc, char **argv) {
       std::cerr << (cfg.pair.ransac.useF ? "LO-RANSAC(epipolar)" : "LO-RANSAC(homography)") << " verification is used..." << std::endl;
       std::cerr << res.n_inliers << " RANSAC correspondences got" << std::endl;
     }
+    if (n_guided >= 0) std::cerr << "Guided matching (radius " << cfg.guided_radius << ", ratio " << cfg.guided_ratio << "): " << n_guided
+                                 << " correspondences, " << n_guided_unique << " after duplicate filtering" << std::endl;
   }
   std::cerr << "Done in " << final_step << " iterations" << std::endl << "*********************" << std::endl;
 
@@ -783,7 +838,7 @@ int main(int argc, char **argv) {
     if (cfg.write_matches) {
       std::ofstream mf(match_fn);
       if (mf.is_open())
-        for (int i = 0; i < res.n_inliers; i++)
+        for (int i = 0; i < n_written; i++)
           mf << matches[4 * (size_t)i] << " " << matches[4 * (size_t)i + 1] << " " << matches[4 * (size_t)i + 2] << " " << matches[4 * (size_t)i + 3] << std::endl;
     }
     if (cfg.write_keypoints && !pre_extracted) {   // mods.cpp:433-447

@@ -274,6 +274,15 @@ struct mods_ctx {
   mods::Buf<char> m_tent2;           // the filtered packed list of the last search (single-pair path)
   mods::TentList h_list;             // host copy for the sequential stages
   std::vector<unsigned char> h_mask;
+  // guided matching (guided.hip), its own buffers: gate records and dense descriptor rows of both lists (queries first), the
+  // per-query (nearest, inconsistent second) and per-train keys, accept flags + block counts, the packed result and its length
+  mods::Buf<double4> g_rec;
+  mods::Buf<unsigned char> g_desc;
+  mods::Buf<unsigned long long> g_key;
+  mods::Buf<int> g_int;
+  mods::Buf<char> g_tent;
+  mods::Buf<mods_region> g_regs;     // staging of host lists
+  mods::PinnedBuf<int> g_count;
   mods::MserState *mser = nullptr;   // MserState (mser.hip): buffers of the MSER detector, allocated on first use
   // the step loop spreads the views of a step over a few more contexts of the same GPU (imgrep.hip: run_view_jobs)
   std::vector<mods_ctx *> helpers;
