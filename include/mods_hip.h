@@ -286,6 +286,13 @@ int  mods_net_forward_dev(mods_net *net, void *hip_stream, const float *patches_
 int  mods_ctx_set_builtin_shape(mods_ctx *ctx, mods_net *net, double mrSize, int quantise_u8);
 int  mods_ctx_set_builtin_orientation(mods_ctx *ctx, mods_net *net, double mrSize, int quantise_u8);
 int  mods_ctx_set_builtin_descriptor(mods_ctx *ctx, mods_net *net, double mrSize, int quantise_u8);
+/* self-test hook: one stage of a network alone, host to host, through the launch functions mods_net_forward_dev uses.  stage 0 =
+ * the input normalisation ([n][1024] -> [n][1024]; quantise_u8 as above, ignored by the other stages), 1..6 = the convolution
+ * blocks ([n][cin][h][h] -> [n][cout][h / stride][h / stride]; channels C, C, 2C, 2C, 4C, 4C with C = 16 or 32 (HardNet), maps of
+ * 32, 32, 16, 16, 8, 8 pixels a side at the output), 7 = the head ([n][4C * 64] -> [n][dim]).  1 <= n <= mods_net_chunk().  The
+ * device output has one more patch's worth of elements behind it, filled with a sentinel before the launch; *guard_ok = 1 when
+ * the stage left them alone. */
+int  mods_test_net_stage(mods_net *net, int stage, const float *in_host, int n, int quantise_u8, float *out_host, int *guard_ok);
 int mods_patches_fetch(mods_ctx *ctx, int img, int ps, float *out, int max_regions, int *n_out);   /* patches of the last describe call */
 /* Baumberg work counters of image slot img (bench.py's per-keypoint figures): keypoints that entered the affine-shape iteration and
  * iterations run since mods_baumberg_stats_enable(ctx, 1); one iteration = smmWindowSize^2 bilinear taps (affine.cpp:26-158). */

@@ -228,6 +228,28 @@ class Net:
         """device pointers ([n][32][32] fp32 in, [n][dim] fp32 out) on hipStream_t `stream` (an integer address); does not wait"""
         _check(lib().mods_net_forward_dev(self.h, C.c_void_p(stream), C.c_void_p(patches_ptr), n, 1 if quantise else 0, C.c_void_p(out_ptr)))
 
+    def stage_shapes(self, stage):
+        """per-patch shapes (input, output) of stage 0 (normalisation), 1..6 (convolution blocks), 7 (head)"""
+        c = 32 if self.kind == "hardnet" else 16
+        maps = [(1, 32), (c, 32), (c, 32), (2 * c, 16), (2 * c, 16), (4 * c, 8), (4 * c, 8)]       # between the stages
+        if stage not in range(8):
+            raise ModsError("Net.stage: stage %r, 0..7 expected" % (stage,))
+        i = maps[max(stage - 1, 0)]
+        return (i[0], i[1], i[1]), ((self.dim,) if stage == 7 else (maps[stage][0], maps[stage][1], maps[stage][1]))
+
+    def stage(self, stage, x, quantise=False):
+        """One stage alone (mods_test_net_stage; self-test hook): x = n <= net_chunk() patches with the elements of the stage's
+        input each -> (float32 [n] + output shape, guard_ok); guard_ok: nothing was written behind the n-th patch's output."""
+        shape_in, shape_out = self.stage_shapes(stage)
+        x = np.ascontiguousarray(x, np.float32)
+        n = len(x)
+        if n < 1 or n > net_chunk() or x.size != n * int(np.prod(shape_in)):
+            raise ModsError("Net.stage: input of shape %s, [n <= %d] + %s expected" % (tuple(x.shape), net_chunk(), shape_in))
+        out = np.zeros((n,) + shape_out, np.float32)
+        ok = C.c_int(0)
+        _check(lib().mods_test_net_stage(self.h, int(stage), _fp(x), n, 1 if quantise else 0, _fp(out), C.byref(ok)))
+        return out, bool(ok.value)
+
     def close(self):
         if self.h:
             lib().mods_net_destroy.restype = None

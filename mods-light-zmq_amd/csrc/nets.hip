@@ -256,15 +256,43 @@ void launch_conv(hipStream_t s, const float *in, float *out, const float *w, con
   hipLaunchKernelGGL((net_conv3_kernel<CIN, COUT, HIN, STRIDE>), grid, dim3(256), 0, s, in, out, w, b, n);
 }
 
+// block l of the six: conv l of a network of width C on n patches
 template <int C>
-void launch_blocks(const mods_net *net, hipStream_t s, float *A, float *B, int n) {
-  const float *P = net->params;
-  launch_conv<1, C, 32, 1>(s, B, A, P + net->w_off[0], P + net->b_off[0], n);
-  launch_conv<C, C, 32, 1>(s, A, B, P + net->w_off[1], P + net->b_off[1], n);
-  launch_conv<C, 2 * C, 32, 2>(s, B, A, P + net->w_off[2], P + net->b_off[2], n);
-  launch_conv<2 * C, 2 * C, 16, 1>(s, A, B, P + net->w_off[3], P + net->b_off[3], n);
-  launch_conv<2 * C, 4 * C, 16, 2>(s, B, A, P + net->w_off[4], P + net->b_off[4], n);
-  launch_conv<4 * C, 4 * C, 8, 1>(s, A, B, P + net->w_off[5], P + net->b_off[5], n);
+void launch_block(const mods_net *net, hipStream_t s, int l, const float *in, float *out, int n) {
+  const float *w = net->params + net->w_off[l], *b = net->params + net->b_off[l];
+  switch (l) {
+    case 0: launch_conv<1, C, 32, 1>(s, in, out, w, b, n); break;
+    case 1: launch_conv<C, C, 32, 1>(s, in, out, w, b, n); break;
+    case 2: launch_conv<C, 2 * C, 32, 2>(s, in, out, w, b, n); break;
+    case 3: launch_conv<2 * C, 2 * C, 16, 1>(s, in, out, w, b, n); break;
+    case 4: launch_conv<2 * C, 4 * C, 16, 2>(s, in, out, w, b, n); break;
+    default: launch_conv<4 * C, 4 * C, 8, 1>(s, in, out, w, b, n); break;
+  }
+}
+
+void launch_block(const mods_net *net, hipStream_t s, int l, const float *in, float *out, int n) {
+  if (net->C == 16) launch_block<16>(net, s, l, in, out, n);
+  else launch_block<32>(net, s, l, in, out, n);
+}
+
+void launch_norm(hipStream_t s, const float *in, float *out, int n, int quantise_u8) {
+  hipLaunchKernelGGL(net_norm_kernel, dim3((n + 3) / 4), dim3(256), 0, s, in, out, n, quantise_u8 ? 1 : 0);
+}
+
+void launch_head(const mods_net *net, hipStream_t s, const float *in, float *out, int n) {
+  const float *w = net->params + net->head_w, *b = net->params + net->head_b;
+  if (net->kind == MODS_NET_AFFNET) hipLaunchKernelGGL(net_head_aff_kernel, dim3((n + 3) / 4), dim3(256), 0, s, in, w, b, out, n);
+  else if (net->kind == MODS_NET_ORINET) hipLaunchKernelGGL(net_head_ori_kernel, dim3((n + 3) / 4), dim3(256), 0, s, in, w, b, out, n);
+  else hipLaunchKernelGGL(net_head_hard_kernel, dim3((n + kHeadP - 1) / kHeadP), dim3(256), 0, s, in, w, b, out, n);
+}
+
+// floats of one patch at the input (out = false) or the output of stage 0 (normalisation), 1..6 (blocks), 7 (head)
+size_t stage_elems(const mods_net *net, int stage, bool out) {
+  const int C = net->C;
+  const int ch[7] = {1, C, C, 2 * C, 2 * C, 4 * C, 4 * C}, size[7] = {32, 32, 32, 16, 16, 8, 8};   // the maps between the stages
+  if (stage == 7 && out) return net->dim;
+  const int m = stage == 0 ? 0 : stage - 1 + (out ? 1 : 0);
+  return (size_t)ch[m] * size[m] * size[m];
 }
 
 // expected element counts of the tensors of `kind`, network order
@@ -386,19 +414,11 @@ int mods_net_forward_dev(mods_net *net, void *hip_stream, const float *patches_d
   NetScratch sc;
   int rc = scratch_take(net, s, &sc);
   if (rc) { if (sc.a) (void)hipFree(sc.a); return rc; }
-  const float *P = net->params;
   for (int i0 = 0; i0 < n; i0 += kChunk) {
     const int m = std::min(kChunk, n - i0);
-    hipLaunchKernelGGL(net_norm_kernel, dim3((m + 3) / 4), dim3(256), 0, s, patches_dev + (size_t)i0 * kPP, sc.b, m, quantise_u8 ? 1 : 0);
-    if (net->C == 16) launch_blocks<16>(net, s, sc.a, sc.b, m);
-    else launch_blocks<32>(net, s, sc.a, sc.b, m);
-    float *o = out_dev + (size_t)i0 * net->dim;
-    if (net->kind == MODS_NET_AFFNET)
-      hipLaunchKernelGGL(net_head_aff_kernel, dim3((m + 3) / 4), dim3(256), 0, s, sc.b, P + net->head_w, P + net->head_b, o, m);
-    else if (net->kind == MODS_NET_ORINET)
-      hipLaunchKernelGGL(net_head_ori_kernel, dim3((m + 3) / 4), dim3(256), 0, s, sc.b, P + net->head_w, P + net->head_b, o, m);
-    else
-      hipLaunchKernelGGL(net_head_hard_kernel, dim3((m + kHeadP - 1) / kHeadP), dim3(256), 0, s, sc.b, P + net->head_w, P + net->head_b, o, m);
+    launch_norm(s, patches_dev + (size_t)i0 * kPP, sc.b, m, quantise_u8);
+    for (int l = 0; l < 6; l++) launch_block(net, s, l, l % 2 ? sc.a : sc.b, l % 2 ? sc.b : sc.a, m);
+    launch_head(net, s, sc.b, out_dev + (size_t)i0 * net->dim, m);
   }
   const hipError_t e_launch = hipGetLastError();
   const hipError_t e_rec = hipEventRecord(sc.done, s);
@@ -425,6 +445,33 @@ int mods_net_forward(mods_net *net, const float *patches_host, int n, int quanti
   if (e == hipSuccess && rc == MODS_OK) e = mods::copy_wait(s, out_host, in_dev + in_elems, out_elems * sizeof(float), hipMemcpyDeviceToHost);
   if (rc) return rc;
   MODS_HIP_CHECK(e);
+  return MODS_OK;
+}
+
+int mods_test_net_stage(mods_net *net, int stage, const float *in_host, int n, int quantise_u8, float *out_host, int *guard_ok) {
+  if (!net || !in_host || !out_host || !guard_ok || stage < 0 || stage > 7 || n < 1 || n > kChunk) { set_error("net_stage: bad argument"); return MODS_E_ARG; }
+  *guard_ok = 0;
+  MODS_HIP_CHECK(hipSetDevice(net->device));
+  hipStream_t s = mods::thread_stream(net->device);
+  const size_t in_elems = n * stage_elems(net, stage, false), per_out = stage_elems(net, stage, true), out_elems = (n + 1) * per_out;
+  mods::Buf<float> in_dev, out_dev;
+  MODS_HIP_CHECK(mods::reserve_group(in_dev, in_elems, out_dev, out_elems));
+  MODS_HIP_CHECK(mods::copy_wait(s, in_dev, in_host, in_elems * sizeof(float), hipMemcpyHostToDevice));
+  MODS_HIP_CHECK(mods::fill_wait(s, out_dev, 0xA5, out_elems * sizeof(float)));       // every word 0xA5A5A5A5 (-2.9e-16f)
+  if (stage == 0) launch_norm(s, in_dev, out_dev, n, quantise_u8);
+  else if (stage <= 6) launch_block(net, s, stage - 1, in_dev, out_dev, n);
+  else launch_head(net, s, in_dev, out_dev, n);
+  MODS_HIP_CHECK(hipGetLastError());
+  std::vector<float> host(out_elems);
+  MODS_HIP_CHECK(mods::copy_wait(s, host.data(), out_dev, out_elems * sizeof(float), hipMemcpyDeviceToHost));
+  memcpy(out_host, host.data(), n * per_out * sizeof(float));
+  int ok = 1;
+  for (size_t i = n * per_out; i < out_elems; i++) {
+    unsigned bits;
+    memcpy(&bits, &host[i], 4);
+    if (bits != 0xA5A5A5A5u) ok = 0;
+  }
+  *guard_ok = ok;
   return MODS_OK;
 }
 

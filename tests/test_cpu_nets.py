@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "nets.npz")
 NAMES = ["mods_net_create", "mods_net_destroy", "mods_net_dim", "mods_net_chunk", "mods_net_forward", "mods_net_forward_dev",
-         "mods_ctx_set_builtin_shape", "mods_ctx_set_builtin_orientation", "mods_ctx_set_builtin_descriptor"]
+         "mods_ctx_set_builtin_shape", "mods_ctx_set_builtin_orientation", "mods_ctx_set_builtin_descriptor", "mods_test_net_stage"]
 
 
 def _state(kind):
