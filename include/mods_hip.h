@@ -186,6 +186,10 @@ int mods_pyramid_octaves(mods_ctx *ctx);
 int mods_pyramid_dims(mods_ctx *ctx, int octave, int *w, int *h);
 int mods_pyramid_plane(mods_ctx *ctx, int img, int octave, int level, int kind, float *dst_host);
 int mods_pyramid_candidates(mods_ctx *ctx, int img, mods_candidate *out, int max_out, int *n_out);
+/* raw 3x3x3 NMS hits of the last detection, before localisation, in list (arbitrary) order: out4[4*i ..] = (octave, level, r0, c0)
+ * of the first min(count, capacity of the context's hit list) records; *n_out = the device's count, which exceeds that capacity
+ * after a detection that ended in MODS_E_CAPACITY "NMS hit list overflow".  MODS_E_CAPACITY here: max_out too small. */
+int mods_pyramid_nms_hits(mods_ctx *ctx, int img, int *out4, int max_out, int *n_out);
 
 /* single primitives (parity tests / building blocks; references: helpers.cpp:717-731,
  * pyramid.cpp:196-254, pyramid.cpp:476, helpers.cpp:551-626) */

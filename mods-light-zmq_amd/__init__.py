@@ -388,7 +388,16 @@ class Context:
         _check(lib().mods_pyramid_candidates(self.h, img, out.ctypes.data_as(C.c_void_p), max_out, C.byref(n)))
         return out[:n.value].copy()
 
-    # ---- orientation + description
+    def pyramid_nms_hits(self, img=0, max_out=1 << 22):
+        """(hits[n, 4] int32 rows (octave, level, r0, c0), count): the raw NMS hit list of the last detection in list (arbitrary)
+        order; count is the device's counter, n = min(count, the list's capacity) - they differ after "NMS hit list overflow"."""
+        n = C.c_int()
+        rc = lib().mods_pyramid_nms_hits(self.h, img, None, 0, C.byref(n))      # the count alone (E_CAPACITY: there are records)
+        if rc not in (MODS_OK, -3):                                               # -3: MODS_E_CAPACITY
+            _check(rc)
+        out = np.full((min(max(n.value, 0), max_out), 4), -1, np.int32)         # the call fills the list's capacity at the most
+        _check(lib().mods_pyramid_nms_hits(self.h, img, out.ctypes.data_as(C.c_void_p), len(out), C.byref(n)))
+        return out[:int(np.count_nonzero(out[:, 1] >= 0))].copy(), n.value
     def orient_describe(self, img, keys, params=None, max_out=None):
         params = params or DescribeParams.default()
         a = np.ascontiguousarray(img, np.float32)

@@ -383,6 +383,24 @@ int mods_pyramid_candidates(mods_ctx *c, int img, mods_candidate *out, int max_o
   *n_out = m;
   return m > max_out ? MODS_E_CAPACITY : MODS_OK;
 }
+// raw NMS hit records of image `img` in list (arbitrary) order, whatever localisation made of them: (octave, level, r0, c0) of the
+// first min(count, max_cand) records; *n_out = the device's count, which exceeds max_cand after an overflowing detection
+int mods_pyramid_nms_hits(mods_ctx *c, int img, int *out4, int max_out, int *n_out) {
+  if (!c || !n_out || img < 0 || img >= c->batch || (max_out > 0 && !out4)) { set_error("pyramid_nms_hits: bad argument"); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  MODS_HIP_CHECK(mods::stream_wait(c->stream));
+  int count = 0;
+  MODS_HIP_CHECK(mods::copy_wait(c->stream, &count, c->cand_count + img, sizeof(int), hipMemcpyDeviceToHost));
+  *n_out = count;
+  const int n = std::max(0, std::min(count, c->max_cand));
+  if (n > max_out) { set_error("NMS hit output overflow: %d > %d", n, max_out); return MODS_E_CAPACITY; }
+  std::vector<CandDev> v(n);
+  MODS_HIP_CHECK(mods::copy_wait(c->stream, v.data(), c->cand + (size_t)img * c->max_cand, sizeof(CandDev) * n, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    out4[4 * i] = v[i].octave; out4[4 * i + 1] = v[i].level; out4[4 * i + 2] = v[i].r0; out4[4 * i + 3] = v[i].c0;
+  }
+  return MODS_OK;
+}
 
 // ---- orientation + description ----------------------------------------------------------------
 static int check_desc_err(mods_ctx *c) {
