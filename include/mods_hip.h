@@ -137,6 +137,7 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_EXTRACT,      /* measurement-region extraction alone (classify .. column pass + resampling), inside MODS_STAGE_DESCRIBE */
        MODS_STAGE_SIFT,         /* the SIFT kernels alone, inside MODS_STAGE_DESCRIBE */
        MODS_STAGE_GUIDED,       /* a guided search (mods_match_guided[_reps]): pack, both gate sweeps, accept, compaction and emit */
+       MODS_STAGE_MATCH_MUTUAL, /* the mutual check of a search alone (mods_ctx_match_mutual: list + sweep), inside MODS_STAGE_MATCH */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -820,6 +821,38 @@ int mods_match_guided(mods_ctx *ctx, const mods_region *q, int n_q, const mods_r
 int mods_match_guided_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgrep *t,
                            const mods_guided_params *par, mods_tentative *out, double *u6_out, double *laf_out,
                            int max_out, int *n_out);                  /* HBM-resident banks */
+
+/* ---- mutual nearest-neighbour check of the FGINN matcher ----------------------------------------------
+ * No counterpart in the reference, whose matcher is one-directional: a query's tentative goes to the verification even when its
+ * train is much closer to another query.  csrc/mutual.hip.
+ *
+ * A forward FGINN search has produced its tentative list, as mods_match_fginn specifies.  For a tentative (q, t):
+ *   d(a, t) = the exact integer squared L2 distance over the 128 descriptor bytes; d1 = d(q, t); a rival is any query r != q of
+ *   the same query list, d_r = d(r, t); centres are the x, y doubles of mods_region.
+ *   Mode 0: off (the default), everything is as without this block.
+ *   Mode 1, mutual nearest neighbour: the tentative is dropped when some rival has d_r < d1, or d_r == d1 and r < q - q must be the
+ *     first query in (d, index) order for train t.
+ *   Mode 2, mode 1 plus the ratio test backwards: the tentative is also dropped when some rival with
+ *     (xr-xq)*(xr-xq) + (yr-yq)*(yr-yq) > contradDist*contradDist (fp64, as written) fails the forward search's own predicate with
+ *     the roles swapped, (double)((float)d1 / (float)d_r) <= ratio*ratio, taken with the search's own ratio and contradDist.  A
+ *     quotient that is NaN or infinite fails (d_r == 0): two far-apart queries with the descriptor of t are both dropped in mode 2;
+ *     in mode 1 the one with the lower index survives.
+ *   Survivors stay in query order, every field of mods_tentative, u6 and laf exactly as the forward search wrote it; nothing is
+ *   re-assigned to a second choice.  The result does not depend on launch geometry or on the grouping of searches.
+ * Every FGINN search of the context honours the mode: mods_match_fginn, mods_match_dev, mods_match_reps[_any] over the whole query
+ * list, mods_match_pair_dev, mods_match_verify_reps, the single-GPU ladder entry points (RootSIFT and HalfRootSIFT lists alike) and a
+ * pipeline's grouped searches; n_tentatives in their results is the count after the check, and the "last search" the fetch entry
+ * points read is the checked list.  The Hamming distance matcher (mods_match_distance, a ladder step's dist_threshold) is never
+ * checked.  The check needs the whole query list: mods_match_reps[_any] with a proper slice (q_begin > 0 or q_end < the bank's
+ * count) while the mode is not 0 answer MODS_E_ARG with a mods_last_error text, before any device call.  The multi-GPU ladder
+ * (mods_match_ladder_multi) shards the queries and has no switch: its searches are unchecked.
+ * mods_ctx_match_mutual: mode 0 / 1 / 2, anything else MODS_E_ARG (checked before ctx).  mods_match_mutual_counts: of the last single
+ * search of the context, the length of the forward list and what the check kept (equal when that search was not checked); waits for
+ * the context's stream.  mods_pipeline_match_mutual: the mode of every search of the pipeline, before the first submit - later:
+ * MODS_E_ARG. */
+int mods_ctx_match_mutual(mods_ctx *ctx, int mode);
+int mods_match_mutual_counts(mods_ctx *ctx, int *n_forward, int *n_kept);
+int mods_pipeline_match_mutual(mods_pipeline *p, int mode);
 
 #ifdef __cplusplus
 }

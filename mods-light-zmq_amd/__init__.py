@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MODS_LIB") or os.path.join(PKG_DIR, "libmodsgpu.so")
 
 MODS_OK = 0
 STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "orient", "describe", "match",
-          "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided"]
+          "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual"]
 
 
 class ModsError(RuntimeError):
@@ -448,6 +448,16 @@ class Context:
     def set_u8_kernels(self, mask):
         """bit 0 orient, 1 extract_small, 2 big_fused, 3 big_sample sample from the 8-bit images in detect_describe_dev_u8; -1: default"""
         _check(lib().mods_ctx_u8_kernels(self.h, int(mask)))
+
+    def set_match_mutual(self, mode):
+        """mods_ctx_match_mutual: 0 off, 1 every FGINN tentative must be its train's nearest query, 2 and pass the ratio test backwards"""
+        _check(lib().mods_ctx_match_mutual(self.h, int(mode)))
+
+    def match_mutual_counts(self):
+        """(forward tentatives, tentatives the mutual check kept) of the context's last single search"""
+        nf, nk = C.c_int(), C.c_int()
+        _check(lib().mods_match_mutual_counts(self.h, C.byref(nf), C.byref(nk)))
+        return nf.value, nk.value
 
     def detect_describe_dev_u8(self, dev_ptr, n_img, w, h, det=None, desc=None, stride=None):
         """detect_describe_dev for a batch of 8-bit grey images [n_img][h][stride] in HBM (stride in bytes, default w): the same regions,
@@ -1210,8 +1220,9 @@ class Pipeline:
     """mods_pipeline_*: GPU workers (detect/describe/match) overlapped with verify workers (duplicate
     filter + LO-RANSAC) across pairs; results in submission order."""
 
-    def __init__(self, device, w, h, params=None, gpu_workers=1, verify_workers=1, pairs_per_batch=1, clahe=None):
-        """clahe: a ClaheParams - 8-bit submissions are equalised with CLAHE on the GPU, fp32 submissions are refused"""
+    def __init__(self, device, w, h, params=None, gpu_workers=1, verify_workers=1, pairs_per_batch=1, clahe=None, mutual=0):
+        """clahe: a ClaheParams - 8-bit submissions are equalised with CLAHE on the GPU, fp32 submissions are refused; mutual: the
+        mutual check of every search (mods_pipeline_match_mutual: 0, 1 or 2)"""
         self.params = params or PairParams.default()
         self.h = C.c_void_p()
         if clahe is not None:
@@ -1222,6 +1233,16 @@ class Pipeline:
             _check(lib().mods_pipeline_create_ex(device, w, h, C.byref(self.params), gpu_workers, verify_workers, pairs_per_batch,
                                                  C.byref(self.h)))
         self.capacity = lib().mods_pipeline_capacity(self.h)
+        if mutual:
+            try:
+                self.set_match_mutual(mutual)
+            except ModsError:
+                self.close()
+                raise
+
+    def set_match_mutual(self, mode):
+        """before the first submit"""
+        _check(lib().mods_pipeline_match_mutual(self.h, int(mode)))
 
     def submit(self, dev_ptr, tag=0):
         _check(lib().mods_pipeline_submit(self.h, C.c_void_p(dev_ptr), C.c_long(tag)))

@@ -57,6 +57,7 @@ struct Config {
   int max_steps = 4, min_matches = 15;
   int load_color = 1;
   int do_clahe = 0;                // [Matching] doCLAHE (io_mods.cpp:526): CLAHE on both 8-bit grey images before detection
+  int mutual_check = 0;            // [Matching] mutualCheck (no counterpart in the reference): mods_ctx_match_mutual
   int verbose = 0, time_log = 1, write_keypoints = 1, write_matches = 1, output_h = 0;
   // [Matching] guidedMatching (no counterpart in the reference): behind the final verification every bank is searched again under
   // the verified model (mods_match_guided_reps) and the de-duplicated result is what the matches file holds
@@ -198,6 +199,8 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   if (ini.GetInteger("TextOutput", "outputAllTentatives", 0)) std::cerr << "Warning: outputAllTentatives is not supported, only verified matches are written" << std::endl;
   cfg->load_color = (int)ini.GetInteger("Computing", "LoadColor", 1);
   cfg->do_clahe = (int)ini.GetInteger("Matching", "doCLAHE", 0);
+  cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
+  if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
   if (ini.Has("zmqDescriptor", "port")) cfg->zmq_port = ini.GetString("zmqDescriptor", "port", "");
   cfg->zmq_mr = ini.GetDouble("zmqDescriptor", "mrSize", cfg->zmq_mr);
   cfg->zmq_ps = (int)ini.GetInteger("zmqDescriptor", "patchSize", cfg->zmq_ps);
@@ -352,6 +355,12 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
     if (!any_desc || g.n_dets == 0) { g.n_dets = 0; continue; }
     if ((g.fginn_ratio > 0 && !(g.fginn_ratio < 1)) || (g.fginn_ratio_half > 0 && !(g.fginn_ratio_half < 1))) { std::cerr << "[Matching] matchRatio* must lie in (0, 1)" << std::endl; return 1; }
     any_group = true;
+  }
+  if (cfg->mutual_check && cfg->verbose) {
+    bool by_distance = false;
+    for (const mods_ladder_step &st : cfg->steps) by_distance = by_distance || (st.n_tilts >= 0 && (st.dist_threshold > 0 || st.dist_threshold_half > 0));
+    for (const mods_ladder_group &g : groups) by_distance = by_distance || (g.n_dets > 0 && (g.dist_threshold > 0 || g.dist_threshold_half > 0));
+    if (by_distance) std::cerr << "Note: [Matching] mutualCheck: lists matched by DistanceThreshold are not checked" << std::endl;
   }
   if (any_group) {
     cfg->groups = groups;
@@ -635,6 +644,7 @@ int main(int argc, char **argv) {
   // One run of one pair: further contexts for the views of a step (MODS_LADDER_WORKERS) take longer to set up than they save
   setenv("MODS_LADDER_WORKERS", "1", 0);
   if (mods_ctx_create(device, (int)diag, (int)diag, 2, &ctx)) return fail("context");
+  if (cfg.mutual_check && mods_ctx_match_mutual(ctx, cfg.mutual_check)) return fail("mutualCheck");
   // mods.cpp:133-189: createCLAHE() (8 x 8 tiles), setClipLimit(4), on the 8-bit grey image (convertTo(CV_8UC1) of the colour average,
   // or imread's grey bytes); ImageRepresentation then takes the float of the result.  Before everything else, so that every path
   // below (one GPU, MODS_DEVICES, the ladders) sees the same pixels; the pre-extracted mode has no use for the images
@@ -716,6 +726,7 @@ int main(int argc, char **argv) {
     if (pre_extracted || cfg.use_zmq || cfg.aff_zmq || cfg.ori_zmq) std::cerr << "Note: MODS_DEVICES is ignored in pre-extracted mode and with ZMQ daemons" << std::endl;
     else if (!devs.empty()) {
       if (mods_multi_create(devs.data(), (int)devs.size(), std::max(img1.w, img2.w), std::max(img1.h, img2.h), 1 << 20, &multi)) return fail("multi-GPU setup");
+      if (cfg.mutual_check) std::cerr << "Note: [Matching] mutualCheck is ignored with MODS_DEVICES (the queries are sharded)" << std::endl;
       if (cfg.verbose) std::cerr << devs.size() << " device(s), exchange over " << (mods_multi_uses_rccl(multi) ? "RCCL" : "device copies") << std::endl;
     }
   }

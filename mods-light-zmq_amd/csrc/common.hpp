@@ -283,6 +283,12 @@ struct mods_ctx {
   mods::Buf<char> g_tent;
   mods::Buf<mods_region> g_regs;     // staging of host lists
   mods::PinnedBuf<int> g_count;
+  // mutual check of the FGINN searches (mutual.hip; mods_ctx_match_mutual), reserved on the first search with a mode set: 16 counters
+  // and the candidate lists (q, t, d1, D*) of the matcher's sets; the candidate counts again, pinned
+  int mutual_mode = 0;
+  bool mu_last_checked = false;      // the last single search of the context went through the check
+  mods::Buf<int4> mu_cand;
+  mods::PinnedBuf<int> mu_count;
   mods::MserState *mser = nullptr;   // MserState (mser.hip): buffers of the MSER detector, allocated on first use
   // the step loop spreads the views of a step over a few more contexts of the same GPU (imgrep.hip: run_view_jobs)
   std::vector<mods_ctx *> helpers;

@@ -177,6 +177,10 @@ int mods_match_reps(mods_ctx *c, const mods_imgrep *q, int q_begin, int q_end, c
                     int nn, mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out) {
   if (!c || !q || !t || !n_out) { set_error("match_reps: null argument"); return MODS_E_ARG; }
   if (q_begin < 0 || q_end > q->n || q_begin > q_end) { set_error("match_reps: bad query range"); return MODS_E_ARG; }
+  if (c->mutual_mode && (q_begin > 0 || q_end < q->n)) {
+    set_error("match_reps: the mutual check (mode %d) needs the whole query list, not the slice [%d, %d) of %d", c->mutual_mode, q_begin, q_end, q->n);
+    return MODS_E_ARG;
+  }
   MODS_HIP_CHECK(hipSetDevice(c->device));
   int rc = match_run(c, q->reg + q_begin, q_end - q_begin, t->reg, t->n, ratio, contradDist, nn);
   if (rc) return rc;

@@ -23,43 +23,12 @@
 // product comes from the matrix cores or from v_dot4 in the exact finish).
 // Trains are the MFMA rows (streamed), queries the columns (resident in registers), so every
 // lane reduces its 16 results per tile into per-query running values.
-#include "common.hpp"
-#include <type_traits>
+#include "match_types.hpp"
 
 namespace mods {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
-
-struct MatchConst {
-  int n_q, n_t;
-  int nn;
-  double sqminratio, contr_sq;
-  int tiles_per_split;
-  int max_distance;       // >= 0: MatchFLANNDistance (Hamming) decisions in the emit stage; -1: FGINN
-};
-
-// The searches of one grouped launch: blockIdx.y (blockIdx.z in the pack kernel) = search.  Every scratch buffer of the context
-// exists once per search of a group ("set"): set j = set 0 + j * stride, so a kernel takes the pointers of set 0 and moves them.
-// The pairs of a pipeline batch are matched in ONE set of launches (a 10 k x 9 k search fills 40 of the 256 CUs on its own, and
-// every dispatch costs the host a completion interrupt); a single search is a group of one.
-constexpr int MATCH_MAX_JOBS = 16;
-struct MatchJobs {
-  int n_jobs;
-  int n_q[MATCH_MAX_JOBS], n_t[MATCH_MAX_JOBS];
-  int tps[MATCH_MAX_JOBS], qblocks[MATCH_MAX_JOBS], splits[MATCH_MAX_JOBS];     // pass-1 geometry (nn1_grid)
-  int eblocks[MATCH_MAX_JOBS];                                                   // blocks of the emit stage
-  const mods_region *q_reg[MATCH_MAX_JOBS], *t_reg[MATCH_MAX_JOBS];
-  mods_tentative *tent_out[MATCH_MAX_JOBS];
-  int *count_out[MATCH_MAX_JOBS];
-  size_t s_desc, s_p2;                       // set strides in bytes (m_desc, m_p2)
-  size_t s_c, s_xy, s_u64, s_int, s_mid;     // set strides in elements of the buffer's type (m_c, m_xy, m_u64, m_int, m_mid)
-};
-template <class T> __device__ __forceinline__ T *set_el(T *p, int job, size_t stride) { return p + (size_t)job * stride; }
-template <class T> __device__ __forceinline__ T *set_by(T *p, int job, size_t stride_bytes) {
-  typedef typename std::conditional<std::is_const<T>::value, const char, char>::type C;
-  return (T *)((C *)p + (size_t)job * stride_bytes);
-}
 
 // Accumulator seed of a train row: acc = dot - floor(ct/2) + MATCH_BIAS.  dot lies in [-2^21, 2^21] and ct in [2^21, 2^22], so the
 // seeded accumulators of real rows lie in [1, 5*2^20 + 1] (23 bits, never negative); the rows past the end of the list inside the last
@@ -534,17 +503,6 @@ __global__ __launch_bounds__(256) void match_fix_kernel(MatchJobs J, MatchConst 
   if (hl == 0 && live) { best2[(size_t)j * 2] = k1; best2[(size_t)j * 2 + 1] = k2; }
 }
 
-struct QueryMid {        // per query state between the passes
-  int i0, d0, dstar, pad;
-  double x0, y0;
-};
-
-// fl32(d0/d) <= ratio^2, evaluated as the reference does (float quotient promoted to double)
-__device__ __forceinline__ bool ratio_ok(int d0, int d, double sqmin) {
-  const double ratio = (double)((float)d0 / (float)d);
-  return ratio <= sqmin;
-}
-
 // grid = ceil(n_q/256), block 256.  Merges the top-2 keys of the train splits and settles every query that does not need
 // pass 2.  With (d0, i0) the nearest train, D* the smallest distance passing the ratio test and (d1, t1) the smallest key over
 // t != i0:
@@ -785,32 +743,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // since round 6: at 1024 queries per block a 60 000-query search kept 59 CUs busy with chains of dependent loads - 24 + 5 us):
 // the first counts the accepted queries of every block, the second adds up the counts of the blocks before it
 // and writes its own tentatives at that offset (query order is the output order of the reference's loop).
-__device__ __forceinline__ bool fginn_accept(const MatchConst &k, int j, const QueryMid *__restrict__ mid,
-                                             const unsigned long long *__restrict__ key_ge, const unsigned long long *__restrict__ key_lt,
-                                             const int *__restrict__ n_lt, const int *__restrict__ bad, mods_tentative *tc) {
-  if (j >= k.n_q) return false;
-  if (k.max_distance >= 0) {   // MatchFLANNDistance, matching.cpp:612-627: mid = nearest, key_ge = second nearest
-    const QueryMid m = mid[j];
-    if (m.d0 > k.max_distance) return false;
-    const unsigned long long k2 = key_ge[j];
-    tc->q = j; tc->t = m.i0; tc->t_bad = tc->t_2nd = (int)(unsigned int)k2;
-    tc->d1 = (float)m.d0; tc->d2 = tc->d2nd = (float)(int)(k2 >> 32); tc->pad = 0;
-    tc->ratio = (double)tc->d1 / (double)tc->d2;
-    return true;
-  }
-  const int K = min(k.nn, k.n_t);
-  const unsigned long long kg = key_ge[j];
-  const int c = n_lt[j];
-  if (bad[j] || kg == ~0ull || c + 1 > K - 1) return false;
-  const QueryMid m = mid[j];
-  const unsigned long long k2 = c > 0 ? key_lt[j] : kg;
-  const int d2 = (int)(kg >> 32);
-  tc->q = j; tc->t = m.i0; tc->t_bad = (int)(unsigned int)kg; tc->t_2nd = (int)(unsigned int)k2;
-  tc->d1 = (float)m.d0; tc->d2 = (float)d2; tc->d2nd = (float)(int)(k2 >> 32); tc->pad = 0;
-  tc->ratio = sqrt((double)((float)m.d0 / (float)d2));
-  return true;
-}
-
 constexpr int EMIT_T = 256;        // queries (= threads) per block of the emit stage
 __global__ __launch_bounds__(EMIT_T) void match_emit_count_kernel(MatchJobs J, MatchConst k, const QueryMid *__restrict__ mid,
                                                                 const unsigned long long *__restrict__ key_ge,
@@ -1052,12 +984,15 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
       hipLaunchKernelGGL(match_fginn_kernel, dim3(row, G), dim3(256), 0, ctx->stream, J, k, qd2, qcs, td, tc, tc2, tpar, txy,
                          (const QueryMid *)mid2, key_ge, key_lt, n_lt, bad, count2, list2);
     }
+    // the mutual check (mods_ctx_match_mutual; mutual.hip) marks the accepted queries that fail it in bad[]
+    if (ctx->mutual_mode && (rc = mutual_stage(ctx, J, k, max_q, n, ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qd, qc, qxy, td, tc))) return rc;
     int *block_counts = (int *)(ctx->m_int + 2 * n);
     hipLaunchKernelGGL(match_emit_count_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, block_counts);
     hipLaunchKernelGGL(match_emit_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qxy, txy,
                        block_counts, ctx->max_cand);
   }
   MODS_HIP_CHECK(hipGetLastError());
+  if (n_jobs == 1 && count_out[0] == ctx->m_count.get() + count_slot()) ctx->mu_last_checked = ctx->mutual_mode && max_q > 0;
   return MODS_OK;
 }
 
@@ -1123,6 +1058,7 @@ int match_run_distance(mods_ctx *ctx, const mods_region *q_dev, int n_q, const m
   k.max_distance = (int)(float)threshold;                       // int max_distance = (int)float(par.matchDistanceThreshold)
   if (k.max_distance < 0) { set_error("match: negative distance threshold"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_count, 0, sizeof(int), ctx->stream));
+  ctx->mu_last_checked = false;      // (the distance matcher is never checked)
   if (n_q == 0 || n_t == 0) return MODS_OK;
   const size_t n = match_pad(ctx);
   int8_t *qd = ctx->m_desc, *td = ctx->m_desc + n * 128;

@@ -54,6 +54,7 @@ struct mods_pipeline {
   std::atomic<long long> cpu_gpu_ns{0}, cpu_verify_ns{0};
   bool clahe = false;             // mods_pipeline_create_clahe: 8-bit submissions only, equalised on the GPU
   mods_clahe_params clahe_par = {0.0, 0, 0};
+  bool submitted = false;         // a pair has been queued: the workers' contexts are no longer reconfigured (mods_pipeline_match_mutual)
 };
 static long long thread_cpu_ns() { timespec ts; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts); return (long long)ts.tv_sec * 1000000000ll + ts.tv_nsec; }
 
@@ -198,6 +199,16 @@ int mods_pipeline_cpu_seconds(mods_pipeline *p, double *gpu_workers_s, double *v
   return MODS_OK;
 }
 
+// the mutual check of every search of the pipeline (mods_ctx_match_mutual on the workers' contexts, which idle until the first submit)
+int mods_pipeline_match_mutual(mods_pipeline *p, int mode) {
+  if (mode < 0 || mode > 2) { set_error("pipeline: match_mutual mode %d (0, 1 or 2)", mode); return MODS_E_ARG; }
+  if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: match_mutual after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) { const int rc = mods_ctx_match_mutual(c, mode); if (rc) return rc; }
+  return MODS_OK;
+}
+
 int mods_pipeline_create_ex(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
                             int pairs_per_batch, mods_pipeline **out) {
   return mods_pipeline_create_clahe(device, w, h, par, gpu_workers, verify_workers, pairs_per_batch, nullptr, out);
@@ -260,6 +271,7 @@ static int submit_any(mods_pipeline *p, const void *img, int kind, long tag) {
   {
     std::unique_lock<std::mutex> lk(p->mu);
     p->cv_space.wait(lk, [&] { return (int)p->q_order.size() < p->max_in_flight; });
+    p->submitted = true;
     p->q_gpu.push_back(j);
     p->q_order.push_back(j);
   }
