@@ -379,6 +379,10 @@ int mods_match_distance(mods_ctx *ctx, const mods_region *q, int n_q, const mods
                         mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out);
 int mods_match_dev(mods_ctx *ctx, int img_q, int img_t, double ratio, double contradDist, int nn, mods_tentative *out,
                    double *u6_out, double *laf_out, int max_out, int *n_out);
+/* Launch geometry of the first pass of an n_q x n_t FGINN search: out = {query blocks, train splits, 32-row train tiles per split}.
+ * Host arithmetic only (no device, no launch); n_q or n_t < 1 or a null out: MODS_E_ARG.  The result of a search does not depend on
+ * it; tests use it to know which tile-loop variant a list length reaches. */
+int mods_match_grid(int n_q, int n_t, int out[3]);
 
 /* Replaces  void DuplicateFiltering(TentativeCorrespListExt &in, const double r, const int mode)
  * (matching.cpp:2615-2679).  Host-side, in place on (tent, u6); mode 0 = keep order (MODE_RANDOM),

@@ -700,6 +700,13 @@ def ransac_pin_seed(seed):
     lib().mods_ransac_pin_seed(seed)
 
 
+def match_grid(n_q, n_t):
+    """mods_match_grid: (query blocks, train splits, tiles per split) of the first pass of an n_q x n_t FGINN search; needs no device."""
+    out = (C.c_int * 3)()
+    _check(lib().mods_match_grid(int(n_q), int(n_t), out))
+    return out[0], out[1], out[2]
+
+
 def ransac_h(u6, th_sq, conf=0.99, max_sam=1000000, err="sampson", sym_check=1, seed_time=12345):
     """exp_ransacHcustom exactly as LORANSACFiltering calls it (matching.cpp:731)."""
     L = lib()

@@ -1087,3 +1087,15 @@ int match_run_distance(mods_ctx *ctx, const mods_region *q_dev, int n_q, const m
 
 }  // namespace mods
 
+extern "C" {
+
+// the pass-1 geometry of an n_q x n_t search (nn1_grid): host arithmetic only, no device, no launch
+int mods_match_grid(int n_q, int n_t, int out[3]) {
+  if (!out || n_q < 1 || n_t < 1) { mods::set_error("match_grid: null argument or an empty list"); return MODS_E_ARG; }
+  const mods::Nn1Grid gr = mods::nn1_grid(n_q, n_t);
+  out[0] = gr.qblocks; out[1] = gr.splits; out[2] = gr.tiles_per_split;
+  return MODS_OK;
+}
+
+}  // extern "C"
+
