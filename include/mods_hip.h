@@ -138,6 +138,7 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_SIFT,         /* the SIFT kernels alone, inside MODS_STAGE_DESCRIBE */
        MODS_STAGE_GUIDED,       /* a guided search (mods_match_guided[_reps]): pack, both gate sweeps, accept, compaction and emit */
        MODS_STAGE_MATCH_MUTUAL, /* the mutual check of a search alone (mods_ctx_match_mutual: list + sweep), inside MODS_STAGE_MATCH */
+       MODS_STAGE_OVERLAP,      /* an overlap search (mods_match_overlap[_reps]): pack, the sweep, accept, compaction and emit */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -825,6 +826,70 @@ int mods_match_guided(mods_ctx *ctx, const mods_region *q, int n_q, const mods_r
 int mods_match_guided_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgrep *t,
                            const mods_guided_params *par, mods_tentative *out, double *u6_out, double *laf_out,
                            int max_out, int *n_out);                  /* HBM-resident banks */
+
+/* ---- ground-truth overlap matching of two region lists -------------------------------------------------
+ * Which regions of image 1 have a geometric counterpart in image 2 under a known homography, and how repeatable the detector is on
+ * the pair.  The reference reads [OverlapMatching] doOverlapMatch / overlapError (io_mods.cpp:685-687) and prints "Overlap
+ * matches with E <" (mods.cpp:522-523); the error is the linearised one of ellipseOverlapH / ellipseOverlapHPrep
+ * (matching/matching.hpp:170-253) with linH (synth-detection.cpp:1498) and rectifyAffineTransformationUpIsUp
+ * (detectors/helpers.cpp:401), not the area of intersection of Mikolajczyk et al.  No descriptor takes part.  csrc/overlap.hip.
+ *
+ * fp64 throughout, one rounding per operation as written; sqrt and / are the correctly rounded ones.  H is row-major, image 1 ->
+ * image 2, as mods_ransac_params.gtH holds it; Hi = H[i].  A region is (x, y, s, a11, a12, a21, a22); k = 3.0.
+ *   Query record (a region of image 1):
+ *     X = (H0*x + H1*y) + H2, Y = (H3*x + H4*y) + H5, den = (H6*x + H7*y) + H8, px = X/den, py = Y/den;
+ *     den2 = den*den, n1 = X/den2, n2 = Y/den2;
+ *     L11 = H0/den - n1*H6, L12 = H1/den - n1*H7, L21 = H3/den - n2*H6, L22 = H4/den - n2*H7   (linH);
+ *     ks = 3.0*s, Bij = ks*aij;
+ *     C11 = L11*B11 + L12*B21, C12 = L11*B12 + L12*B22, C21 = L21*B11 + L22*B21, C22 = L21*B12 + L22*B22.
+ *   Train record (a region (x2, y2, ...) of image 2):
+ *     ks = 3.0*s, Mij = ks*aij, d = 1.0/(M11*M22 - M12*M21), I11 = M22*d, I12 = -(M12*d), I21 = -(M21*d), I22 = M11*d.
+ *   Pair (q, t):
+ *     dx = px - x2, dy = py - y2, u = I11*dx + I12*dy, v = I21*dx + I22*dy, dist = u*u + v*v;
+ *     G11 = I11*C11 + I12*C21, G12 = I11*C12 + I12*C22, G21 = I21*C11 + I22*C21, G22 = I21*C12 + I22*C22;
+ *     with oriented == 0, G is first replaced by its up-is-up form, so that an in-plane rotation of the frame does not count:
+ *       det = sqrt(fabs(G11*G22 - G12*G21)), r = sqrt(G12*G12 + G11*G11),
+ *       (G11, G12, G21, G22) <- (r/det, 0, (G22*G12 + G21*G11)/(r*det), det/r);
+ *     diff = 0.5*((((1-G11)*(1-G11) + G12*G12) + G21*G21) + (1-G22)*(1-G22)), E = diff + dist.
+ *   This restates ellipseOverlapH with one deliberate difference: the centre offset is mapped once, I*(p - x2), where the
+ *   reference maps the two absolute positions and subtracts.  cv::invert / cv::gemm cannot be pinned without OpenCV, so parity
+ *   with the reference is UNPINNED (as for CLAHE): the contract is this restatement.
+ *   Per query: (E1, t1) = the smallest (E, t) over the trains that take part (ties: the lower train index); accepted when
+ *     E1 < max_error (strict).  Every comparison with NaN fails: a singular train frame, den == 0 and non-finite input never match
+ *     and never fault.  (diff >= 0, so the shape term may be skipped whenever dist >= max_error; that is not observable.)
+ *   one_to_one: of the accepted queries that chose the same train only the one with the smallest (E1, q) stays; the others are
+ *     dropped, not re-assigned - the rule of mods_match_guided.
+ *   Common area: when w1, h1, w2, h2 are all > 0, a query takes part when 0 < px < w2 and 0 < py < h2, a train when its centre
+ *     sent back with Hinv = adjugate(H) * (1 / det H) (as the guided gate does: (bx, by) by the formulas of (px, py)) satisfies
+ *     0 < bx < w1 and 0 < by < h1.  With any of the four sizes 0 every region takes part and the two common counts are the list
+ *     lengths.
+ *   Output in query order; counts: n_q_common / n_t_common = the regions of either list that take part, n_matches = *n_out,
+ *     repeatability = (double)n_matches / (double)min(n_q_common, n_t_common), 0 when that minimum is 0.  The customary
+ *     repeatability figure is the one with one_to_one = 1 (otherwise several queries may count one train).  The result does not
+ *     depend on launch geometry, train splits or the order of atomics.
+ * MODS_E_ARG with a mods_last_error text starting "match_overlap: ", before the context is looked at and before any device call: a
+ * null pointer (a list may be null when its count is 0, `out` when max_out is 0), a negative count, an H entry that is not finite,
+ * det H zero or not finite, max_error not finite or <= 0, oriented or one_to_one other than 0 / 1, a negative image size.  A result
+ * longer than max_out: as mods_match_guided, *n_out = the full length, MODS_E_CAPACITY, and nothing is copied (the counts are
+ * filled).  The search has buffers of its own: it leaves the matcher's "last search" and the guided buffers alone.
+ * mods_ctx_overlap_splits: the number of train splits of the sweep (0 = chosen from the list lengths, the default); a testing knob,
+ * the result does not depend on it. */
+typedef struct mods_overlap_params {
+  double H[9];
+  double max_error;      /* [OverlapMatching] overlapError, 0.09 in the reference's configurations */
+  int oriented;          /* 1: the frames' orientations count; 0: up-is-up form */
+  int one_to_one;
+  int w1, h1, w2, h2;    /* image sizes for the common-area test; any 0: no test */
+} mods_overlap_params;
+typedef struct mods_overlap_match { int q, t; double E, dist, diff; } mods_overlap_match;
+typedef struct mods_overlap_counts { int n_q_common, n_t_common, n_matches; double repeatability; } mods_overlap_counts;
+int mods_match_overlap(mods_ctx *ctx, const mods_region *q, int n_q, const mods_region *t, int n_t,
+                       const mods_overlap_params *par, mods_overlap_match *out, int max_out, int *n_out,
+                       mods_overlap_counts *counts);                  /* host lists, the testing seam */
+int mods_match_overlap_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgrep *t,
+                            const mods_overlap_params *par, mods_overlap_match *out, int max_out, int *n_out,
+                            mods_overlap_counts *counts);             /* HBM-resident banks */
+int mods_ctx_overlap_splits(mods_ctx *ctx, int splits);
 
 /* ---- mutual nearest-neighbour check of the FGINN matcher ----------------------------------------------
  * No counterpart in the reference, whose matcher is one-directional: a query's tentative goes to the verification even when its

@@ -17,7 +17,8 @@ LIB_PATH = os.environ.get("MODS_LIB") or os.path.join(PKG_DIR, "libmodsgpu.so")
 
 MODS_OK = 0
 STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "orient", "describe", "match",
-          "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual"]
+          "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
+          "overlap"]
 
 
 class ModsError(RuntimeError):
@@ -617,6 +618,22 @@ class Context:
                                        laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
         return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
 
+    def match_overlap(self, q, t, params):
+        """mods_match_overlap: ground-truth overlap matching of two host region lists (OverlapParams); returns (matches as
+        OVERLAP_DTYPE rows in query order, OverlapCounts)."""
+        q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
+        cap = max(len(q), 1)
+        out = np.zeros(cap, OVERLAP_DTYPE)
+        n = C.c_int()
+        counts = OverlapCounts()
+        _check(lib().mods_match_overlap(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
+                                        C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(counts)))
+        return out[:n.value].copy(), counts
+
+    def overlap_splits(self, splits):
+        """mods_ctx_overlap_splits: train splits of the overlap sweep (0 = automatic); the result does not depend on it."""
+        _check(lib().mods_ctx_overlap_splits(self.h, int(splits)))
+
     def clahe(self, img_u8, clip_limit=4.0, tiles=(8, 8)):
         """mods_clahe: CLAHE of one 8-bit grey image [h, w] (host in, host out); tiles = (tiles_x, tiles_y)"""
         a = np.ascontiguousarray(img_u8, np.uint8)
@@ -1041,6 +1058,41 @@ def match_guided_reps(ctx, rep_q, rep_t, params, cap=None):
     _check(lib().mods_match_guided_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p),
                                         u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
     return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+
+
+OVERLAP_DTYPE = np.dtype([("q", "i4"), ("t", "i4"), ("E", "f8"), ("dist", "f8"), ("diff", "f8")])
+
+
+class OverlapParams(C.Structure):
+    """mods_overlap_params: ground-truth overlap matching ([OverlapMatching] of the reference's configuration)."""
+    _fields_ = [("H", C.c_double * 9), ("max_error", C.c_double), ("oriented", C.c_int), ("one_to_one", C.c_int),
+                ("w1", C.c_int), ("h1", C.c_int), ("w2", C.c_int), ("h2", C.c_int)]
+
+    @staticmethod
+    def default(H=None, max_error=0.09, oriented=1, one_to_one=1, w1=0, h1=0, w2=0, h2=0):
+        """max_error = [OverlapMatching] overlapError of config_affori_classic.ini; H: 9 values row-major, image 1 -> image 2;
+        sizes 0: no common-area test"""
+        p = OverlapParams((C.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1), max_error, oriented, one_to_one, w1, h1, w2, h2)
+        if H is not None:
+            p.H = (C.c_double * 9)(*[float(v) for v in np.asarray(H, np.float64).reshape(9)])
+        return p
+
+
+class OverlapCounts(C.Structure):
+    """mods_overlap_counts; the customary repeatability figure is the one with one_to_one = 1."""
+    _fields_ = [("n_q_common", C.c_int), ("n_t_common", C.c_int), ("n_matches", C.c_int), ("repeatability", C.c_double)]
+
+
+def match_overlap_reps(ctx, rep_q, rep_t, params, cap=None):
+    """mods_match_overlap_reps: overlap matching of ImgRep rep_q against ImgRep rep_t (HBM resident); returns (matches, counts).
+    cap: room for that many matches (default: one per query, which always suffices)."""
+    cap = max(len(rep_q), 1) if cap is None else cap
+    out = np.zeros(max(cap, 1), OVERLAP_DTYPE)
+    n = C.c_int()
+    counts = OverlapCounts()
+    _check(lib().mods_match_overlap_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
+                                         C.byref(counts)))
+    return out[:n.value].copy(), counts
 
 
 def match_ladder_dev(ctx, img_ptr, w, h, steps, rep1, rep2, params=None, min_matches=15, max_matches=0, img2_ptr=None, w2=None, h2=None):

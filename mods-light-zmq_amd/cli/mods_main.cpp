@@ -63,6 +63,10 @@ struct Config {
   // the verified model (mods_match_guided_reps) and the de-duplicated result is what the matches file holds
   int guided = 0, guided_max_dist = 0, guided_one_to_one = 1;
   double guided_radius = 0, guided_ratio = 0.9;
+  // [OverlapMatching] doOverlapMatch / overlapError (io_mods.cpp:685-687) and matchOriented (ours): with ver_type 1 every detector's
+  // banks go through mods_match_overlap_reps under the ground-truth H and the count is printed as mods.cpp:522-523 does
+  int overlap = 0, overlap_oriented = 1;
+  double overlap_error = 0.09;
   // [zmqDescriptor] (io_mods.cpp:395-407): used when a step asks for the "ZMQ" descriptor instead of RootSIFT
   bool use_zmq = false;
   std::string zmq_port = "tcp://localhost:5555";
@@ -191,6 +195,12 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   if (!(cfg->guided_ratio > 0 && cfg->guided_ratio <= 1)) { std::cerr << "[Matching] guidedRatio must lie in (0, 1], not " << cfg->guided_ratio << std::endl; return 1; }
   if (cfg->guided_max_dist < 0) { std::cerr << "[Matching] guidedMaxDist must not be negative (0 = no cap)" << std::endl; return 1; }
   if (cfg->guided_one_to_one != 0 && cfg->guided_one_to_one != 1) { std::cerr << "[Matching] guidedOneToOne must be 0 or 1" << std::endl; return 1; }
+  cfg->overlap = (int)ini.GetInteger("OverlapMatching", "doOverlapMatch", 0);
+  cfg->overlap_error = ini.GetDouble("OverlapMatching", "overlapError", 0.09);
+  cfg->overlap_oriented = (int)ini.GetInteger("OverlapMatching", "matchOriented", 1);
+  if (cfg->overlap != 0 && cfg->overlap != 1) { std::cerr << "[OverlapMatching] doOverlapMatch must be 0 or 1" << std::endl; return 1; }
+  if (!std::isfinite(cfg->overlap_error) || !(cfg->overlap_error > 0)) { std::cerr << "[OverlapMatching] overlapError must be a positive number, not " << cfg->overlap_error << std::endl; return 1; }
+  if (cfg->overlap_oriented != 0 && cfg->overlap_oriented != 1) { std::cerr << "[OverlapMatching] matchOriented must be 0 or 1" << std::endl; return 1; }
   // [TextOutput], [Computing]
   cfg->time_log = (int)ini.GetInteger("TextOutput", "timeLog", 0);
   cfg->write_keypoints = (int)ini.GetInteger("TextOutput", "writeKeypoints", 1);
@@ -871,6 +881,31 @@ int main(int argc, char **argv) {
                                                << 100.0 * res.gt_true_of_ransac / res.gt_ransac_inliers << "% RANSACed  1st geom inc" << std::endl;
       else std::cerr << res.gt_true_of_ransac << " | " << res.gt_ransac_inliers << " | -  RANSACed  1st geom inc" << std::endl;
     }
+  }
+  // [OverlapMatching] doOverlapMatch = 1 (mods.cpp:522-523): the banks of every detector under the ground-truth homography, one to one
+  if (cfg.overlap && ver_type != 1) std::cerr << "Note: doOverlapMatch needs the ground truth homography (verification type 1), skipped" << std::endl;
+  else if (cfg.overlap && multi) std::cerr << "Note: doOverlapMatch is not run with MODS_DEVICES" << std::endl;
+  else if (cfg.overlap) {
+    mods_overlap_params op;
+    memset(&op, 0, sizeof(op));
+    for (int i = 0; i < 9; i++) op.H[i] = cfg.pair.ransac.gtH[i];
+    op.max_error = cfg.overlap_error; op.oriented = cfg.overlap_oriented; op.one_to_one = 1;
+    op.w1 = img1.w; op.h1 = img1.h; op.w2 = img2.w; op.h2 = img2.h;
+    long n_overlap = 0;
+    std::vector<mods_overlap_counts> oc((size_t)n_det);
+    std::vector<mods_overlap_match> om;
+    for (int d = 0; d < n_det; d++) {
+      const int cap = mods_imgrep_count(reps1[d]);
+      om.resize((size_t)std::max(cap, 1));
+      int m = 0;
+      if (mods_match_overlap_reps(ctx, reps1[d], reps2[d], &op, om.data(), cap, &m, &oc[d])) return fail("overlap matching");
+      n_overlap += m;
+    }
+    std::cerr << "Overlap matches with E < " << cfg.overlap_error << std::endl << n_overlap << std::endl;
+    if (cfg.verbose)
+      for (int d = 0; d < n_det; d++)
+        std::cerr << cfg.det_names[d] << ": " << oc[d].n_q_common << " | " << oc[d].n_t_common << " regions in the common area, repeatability "
+                  << oc[d].repeatability << std::endl;
   }
   const double total = now_s() - c_start;
   std::cerr << std::endl << "Main matching | All Time: " << std::endl << final_time << " | " << total << " seconds" << std::endl;

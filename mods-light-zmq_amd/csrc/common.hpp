@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -99,6 +100,20 @@ __host__ __device__ inline size_t tent_laf_off(size_t n) { return tent_u6_off(n)
 __host__ __device__ inline size_t tent_bytes(size_t n) { return tent_laf_off(n) + n * 14 * sizeof(double); }
 
 namespace mods {
+
+// The inverse of a row-major 3 x 3 matrix as the guided gate and the overlap search's common-area test take it: the closed form of
+// invert3_cv (describe.hip), adjugate times the reciprocal of the determinant, one rounding per operation.  false (and *det) when the
+// determinant is 0 or not finite
+inline bool invert3_adjugate(const double *S, double *t, double *det) {
+  double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
+  *det = d;
+  if (d == 0. || !std::isfinite(d)) return false;
+  d = 1. / d;
+  t[0] = (S[4] * S[8] - S[5] * S[7]) * d; t[1] = (S[2] * S[7] - S[1] * S[8]) * d; t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
+  t[3] = (S[5] * S[6] - S[3] * S[8]) * d; t[4] = (S[0] * S[8] - S[2] * S[6]) * d; t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
+  t[6] = (S[3] * S[7] - S[4] * S[6]) * d; t[7] = (S[1] * S[6] - S[0] * S[7]) * d; t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
+  return true;
+}
 
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -283,6 +298,16 @@ struct mods_ctx {
   mods::Buf<char> g_tent;
   mods::Buf<mods_region> g_regs;     // staging of host lists
   mods::PinnedBuf<int> g_count;
+  // overlap matching (overlap.hip), its own buffers: 48-byte fp64 records of both lists (queries first, 6 doubles each), the error
+  // keys (per train, per query, per split and query), the integer twins (common counts, per-train owner, per-query train, block
+  // counts, per split and query), the matches and (matches, common queries, common trains); o_splits: mods_ctx_overlap_splits
+  mods::Buf<double> o_rec;
+  mods::Buf<unsigned long long> o_key;
+  mods::Buf<int> o_int;
+  mods::Buf<mods_overlap_match> o_out;
+  mods::Buf<mods_region> o_regs;     // staging of host lists
+  mods::PinnedBuf<int> o_count;
+  int o_splits = 0;
   // mutual check of the FGINN searches (mutual.hip; mods_ctx_match_mutual), reserved on the first search with a mode set: 16 counters
   // and the candidate lists (q, t, d1, D*) of the matcher's sets; the candidate counts again, pinned
   int mutual_mode = 0;

@@ -262,15 +262,8 @@ static int guided_check(const mods_guided_params *par, GuidedConst *k) {
     for (int c = 0; c < 3; c++) k->M[3 * r + c] = par->model_type == 0 ? par->model[3 * r + c] : par->model[3 * c + r];
   for (int i = 0; i < 9; i++) k->Minv[i] = 0;
   if (par->model_type == 0) {
-    // the closed form of invert3_cv (describe.hip): adjugate times the reciprocal of the determinant
-    const double *S = k->M;
-    double *t = k->Minv;
-    double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
-    if (d == 0. || !std::isfinite(d)) { set_error("match_guided: singular homography (determinant %g)", d); return MODS_E_ARG; }
-    d = 1. / d;
-    t[0] = (S[4] * S[8] - S[5] * S[7]) * d; t[1] = (S[2] * S[7] - S[1] * S[8]) * d; t[2] = (S[1] * S[5] - S[2] * S[4]) * d;
-    t[3] = (S[5] * S[6] - S[3] * S[8]) * d; t[4] = (S[0] * S[8] - S[2] * S[6]) * d; t[5] = (S[2] * S[3] - S[0] * S[5]) * d;
-    t[6] = (S[3] * S[7] - S[4] * S[6]) * d; t[7] = (S[1] * S[6] - S[0] * S[7]) * d; t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
+    double d;
+    if (!invert3_adjugate(k->M, k->Minv, &d)) { set_error("match_guided: singular homography (determinant %g)", d); return MODS_E_ARG; }
   }
   k->r2 = par->radius * par->radius;
   k->rho2 = par->ratio * par->ratio;
