@@ -923,6 +923,37 @@ int mods_ctx_match_mutual(mods_ctx *ctx, int mode);
 int mods_match_mutual_counts(mods_ctx *ctx, int *n_forward, int *n_kept);
 int mods_pipeline_match_mutual(mods_pipeline *p, int mode);
 
+/* ---- domain-size pooling of the SIFT descriptor (DSP-SIFT) -------------------------------------------
+ * Dong and Soatto, "Domain-size pooling in local descriptors: DSP-SIFT", CVPR 2015.  The reference reads [SIFTDescriptor] numScales /
+ * startCoef / endCoef (io_mods.cpp:431-433, siftdesc.h:21-30) and never uses them; this is their contract here (restated in
+ * tests/dsp_ref.py).  Off by default; with it off every entry point launches what it launches without this section.
+ *   Coefficients   c_k = startCoef + k * ((endCoef - startCoef) / (K - 1)), k = 0 .. K-1, K = numScales; domain k is described at
+ *                  mr_k = desc_mrSize * c_k (all in double).
+ *   Patches        patch k of a region is what the unpooled extraction makes at desc_mrSize = mr_k: the same size rule and tiers,
+ *                  samples outside the image are 0, photometric normalisation per patch when photoNorm is set.
+ *   Histograms     h_k[128]: the raw histogram of patch k - before the HalfSIFT fold and before any normalisation.
+ *   Pooling        pooled[i] = ((h_0[i] + h_1[i]) + h_2[i]) + ..., in double, in scale order; no division by K (the L2 normalisation
+ *                  that follows removes the factor).
+ *   Tail           unchanged, on `pooled`: the HalfSIFT fold when halfDesc asks for it, normalise / clip at maxBinValue /
+ *                  renormalise, RootSIFT or plain SIFT, quantisation.
+ *   Regions        every field of mods_region but the descriptor bytes - count and order included - is that of the unpooled call
+ *                  (the border rule does not depend on desc_mrSize).
+ * 2 <= numScales <= 8, 0 < startCoef < endCoef <= 4, finite; numScales 0 or 1 switches pooling off (the coefficients are then
+ * ignored); anything else is MODS_E_ARG (checked before ctx).  With pooling on, a describe call with fastExtraction = 1, or on a
+ * context with an external descriptor or a descriptor network, is MODS_E_ARG before anything is launched; external shape and
+ * orientation hooks are compatible.  The pair, ladder, view, image-representation and verify entry points inherit the context's
+ * setting; mods_multi does not (its contexts stay unpooled).  A recorded detect + describe graph (mods_ctx_graphs) is never
+ * replayed across a change, and with pooling on the chain is issued eagerly.  After a pooled call mods_patches_fetch returns the
+ * patches of the last domain.  The accumulators (1 KB per region slot of the batch) are reserved by the first pooled call.
+ * mods_pipeline_domain_pooling: every GPU worker's context, before the first submit - later: MODS_E_ARG.
+ * mods_test_sift_pooled: the pooled twin of mods_sift_patch - K (1 .. 8) host patches [K][ps][ps] of one region through the
+ * accumulate and finish kernels; half != 0: out128 receives the HalfSIFT bytes (64 values, then 64 zeros). */
+int mods_ctx_domain_pooling(mods_ctx *ctx, int numScales, double startCoef, double endCoef);
+int mods_ctx_domain_pooling_get(const mods_ctx *ctx, int *numScales, double *startCoef, double *endCoef);
+int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCoef, double endCoef);
+int mods_test_sift_pooled(mods_ctx *ctx, const float *patches, int K, int ps, int rootsift, int half, int photoNorm, double maxBinValue,
+                          uint8_t *out128);
+
 #ifdef __cplusplus
 }
 #endif

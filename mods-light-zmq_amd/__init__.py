@@ -460,6 +460,17 @@ class Context:
         _check(lib().mods_match_mutual_counts(self.h, C.byref(nf), C.byref(nk)))
         return nf.value, nk.value
 
+    def set_domain_pooling(self, num_scales, start_coef=0.5, end_coef=1.5):
+        """mods_ctx_domain_pooling (DSP-SIFT): the raw SIFT histograms of num_scales (2 .. 8) domains desc_mrSize * c_k, c_k from
+        start_coef to end_coef in equal steps, are summed before the normalisation; num_scales 0 or 1: off"""
+        _check(lib().mods_ctx_domain_pooling(self.h, int(num_scales), C.c_double(start_coef), C.c_double(end_coef)))
+
+    def domain_pooling(self):
+        """(num_scales, start_coef, end_coef) of the context; (0, 0.0, 0.0) when pooling is off"""
+        k, a, b = C.c_int(), C.c_double(), C.c_double()
+        _check(lib().mods_ctx_domain_pooling_get(self.h, C.byref(k), C.byref(a), C.byref(b)))
+        return k.value, a.value, b.value
+
     def detect_describe_dev_u8(self, dev_ptr, n_img, w, h, det=None, desc=None, stride=None):
         """detect_describe_dev for a batch of 8-bit grey images [n_img][h][stride] in HBM (stride in bytes, default w): the same regions,
         sampled from the 8-bit images where the rows are packed, from their fp32 copy otherwise."""
@@ -540,6 +551,15 @@ class Context:
         out = np.zeros(128, np.uint8)
         _check(lib().mods_sift_patch(self.h, _fp(a), a.shape[0], int(rootsift), C.c_double(max_bin),
                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def sift_pooled(self, patches, rootsift=True, half=False, photo_norm=False, max_bin=0.2):
+        """mods_test_sift_pooled: patches [K][ps][ps] of one region through the accumulate and finish kernels of the pooled
+        description; 128 bytes (half: the 64 HalfSIFT values, then zeros)"""
+        a = np.ascontiguousarray(patches, np.float32)
+        out = np.zeros(128, np.uint8)
+        _check(lib().mods_test_sift_pooled(self.h, _fp(a), a.shape[0], a.shape[1], int(rootsift), int(half), int(photo_norm),
+                                           C.c_double(max_bin), out.ctypes.data_as(C.c_void_p)))
         return out
 
     # ---- view synthesis
@@ -1302,6 +1322,10 @@ class Pipeline:
     def set_match_mutual(self, mode):
         """before the first submit"""
         _check(lib().mods_pipeline_match_mutual(self.h, int(mode)))
+
+    def set_domain_pooling(self, num_scales, start_coef=0.5, end_coef=1.5):
+        """mods_pipeline_domain_pooling: Context.set_domain_pooling on every GPU worker's context, before the first submit"""
+        _check(lib().mods_pipeline_domain_pooling(self.h, int(num_scales), C.c_double(start_coef), C.c_double(end_coef)))
 
     def submit(self, dev_ptr, tag=0):
         _check(lib().mods_pipeline_submit(self.h, C.c_void_p(dev_ptr), C.c_long(tag)))

@@ -58,6 +58,10 @@ struct Config {
   int load_color = 1;
   int do_clahe = 0;                // [Matching] doCLAHE (io_mods.cpp:526): CLAHE on both 8-bit grey images before detection
   int mutual_check = 0;            // [Matching] mutualCheck (no counterpart in the reference): mods_ctx_match_mutual
+  // [SIFTDescriptor] domainSizePooling (the gate; no counterpart in the reference) with the reference's numScales / startCoef /
+  // endCoef (io_mods.cpp:431-433, parsed there and never used): mods_ctx_domain_pooling
+  int dsp = 0, dsp_scales = 3;
+  double dsp_start = 0.5, dsp_end = 1.5;
   int verbose = 0, time_log = 1, write_keypoints = 1, write_matches = 1, output_h = 0;
   // [Matching] guidedMatching (no counterpart in the reference): behind the final verification every bank is searched again under
   // the verified model (mods_match_guided_reps) and the de-duplicated result is what the matches file holds
@@ -154,6 +158,20 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   q.rootSift = 1;
   q.maxBinValue = ini.GetDouble("SIFTDescriptor", "maxBinValue", 0.2);
   q.fastExtraction = ini.GetBoolean("SIFTDescriptor", "FastPatchExtraction", false) ? 1 : 0;
+  cfg->dsp = (int)ini.GetInteger("SIFTDescriptor", "domainSizePooling", 0);
+  if (cfg->dsp != 0 && cfg->dsp != 1) { std::cerr << "[SIFTDescriptor] domainSizePooling must be 0 or 1" << std::endl; return 1; }
+  if (cfg->dsp) {   // (with the gate 0 the three keys are ignored, as the reference ignores them)
+    cfg->dsp_scales = (int)ini.GetInteger("SIFTDescriptor", "numScales", 3);
+    cfg->dsp_start = ini.GetDouble("SIFTDescriptor", "startCoef", 0.5);
+    cfg->dsp_end = ini.GetDouble("SIFTDescriptor", "endCoef", 1.5);
+    if (cfg->dsp_scales < 0 || cfg->dsp_scales > 8) { std::cerr << "[SIFTDescriptor] numScales must lie in 2 .. 8 (0 or 1: no pooling) with domainSizePooling = 1, not " << cfg->dsp_scales << std::endl; return 1; }
+    if (cfg->dsp_scales < 2) cfg->dsp = 0;          // one domain is the unpooled descriptor (mods_ctx_domain_pooling: off)
+    if (cfg->dsp) {
+      if (!std::isfinite(cfg->dsp_start) || !(cfg->dsp_start > 0)) { std::cerr << "[SIFTDescriptor] startCoef must be a positive number, not " << cfg->dsp_start << std::endl; return 1; }
+      if (!std::isfinite(cfg->dsp_end) || !(cfg->dsp_end > cfg->dsp_start) || cfg->dsp_end > 4) { std::cerr << "[SIFTDescriptor] endCoef must lie in (startCoef, 4], not " << cfg->dsp_end << std::endl; return 1; }
+      if (q.fastExtraction) { std::cerr << "[SIFTDescriptor] domainSizePooling = 1 cannot be combined with FastPatchExtraction = 1" << std::endl; return 1; }
+    }
+  }
   if (ini.GetInteger("SIFTDescriptor", "spatialBins", 4) != 4 || ini.GetInteger("SIFTDescriptor", "orientationBins", 8) != 8) {
     std::cerr << "Only 4x4x8 SIFT is supported" << std::endl;
     return 1;
@@ -260,7 +278,7 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
     // DSPLevels / minSigma / maxSigma (io_mods.cpp:480-482): SetVSPars stores them in ViewSynthParameters
     // (synth-detection.cpp:244-289) and nothing in the reference reads them again
     if (cfg->verbose && (it.Has(sec, "DSPLevels") || it.Has(sec, "minSigma") || it.Has(sec, "maxSigma")))
-      std::cerr << "Note: [" << sec << "] DSPLevels / minSigma / maxSigma are stored and never used by the reference; no effect" << std::endl;
+      std::cerr << "Note: [" << sec << "] DSPLevels / minSigma / maxSigma are stored and never used by the reference; no effect (domain-size pooling: [SIFTDescriptor] domainSizePooling = 1)" << std::endl;
     st.fginn_ratio = 0.0;
     if (it.Has(sec, "TiltSet") && it.Has(sec, "ScaleSet")) {
       const std::vector<double> tilts = it.GetDoubleVector(sec, "TiltSet"), scales = it.GetDoubleVector(sec, "ScaleSet");
@@ -655,6 +673,9 @@ int main(int argc, char **argv) {
   setenv("MODS_LADDER_WORKERS", "1", 0);
   if (mods_ctx_create(device, (int)diag, (int)diag, 2, &ctx)) return fail("context");
   if (cfg.mutual_check && mods_ctx_match_mutual(ctx, cfg.mutual_check)) return fail("mutualCheck");
+  if (cfg.dsp && cfg.use_zmq) { std::cerr << "[SIFTDescriptor] domainSizePooling = 1 pools SIFT histograms: it cannot be combined with the [zmqDescriptor] descriptor" << std::endl; return 1; }
+  if (cfg.dsp && mods_ctx_domain_pooling(ctx, cfg.dsp_scales, cfg.dsp_start, cfg.dsp_end)) return fail("domainSizePooling");
+  if (cfg.dsp && cfg.verbose) std::cerr << "Domain-size pooling: " << cfg.dsp_scales << " domains, " << cfg.dsp_start << " .. " << cfg.dsp_end << " x mrSize" << std::endl;
   // mods.cpp:133-189: createCLAHE() (8 x 8 tiles), setClipLimit(4), on the 8-bit grey image (convertTo(CV_8UC1) of the colour average,
   // or imread's grey bytes); ImageRepresentation then takes the float of the result.  Before everything else, so that every path
   // below (one GPU, MODS_DEVICES, the ladders) sees the same pixels; the pre-extracted mode has no use for the images
@@ -737,6 +758,7 @@ int main(int argc, char **argv) {
     else if (!devs.empty()) {
       if (mods_multi_create(devs.data(), (int)devs.size(), std::max(img1.w, img2.w), std::max(img1.h, img2.h), 1 << 20, &multi)) return fail("multi-GPU setup");
       if (cfg.mutual_check) std::cerr << "Note: [Matching] mutualCheck is ignored with MODS_DEVICES (the queries are sharded)" << std::endl;
+      if (cfg.dsp) std::cerr << "Note: [SIFTDescriptor] domainSizePooling is ignored with MODS_DEVICES (the devices' contexts describe unpooled)" << std::endl;
       if (cfg.verbose) std::cerr << devs.size() << " device(s), exchange over " << (mods_multi_uses_rccl(multi) ? "RCCL" : "device copies") << std::endl;
     }
   }

@@ -454,7 +454,9 @@ static unsigned long long fnv1a(const void *p, size_t n, unsigned long long h) {
 // whose scale space does not fork (small images, small batches, mods_ctx_pyramid_streams(1)) stay eager.
 static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
                   const mods_describe_params *desc) {
-  const bool can = c->dd_graphs && c->timing_mask == 0 && !mods::has_hooks(c) && !mods::has_nets(c) && det->detectorType != MODS_DET_MSER;
+  // (domain-size pooling: the chain runs eagerly - K extractions are K times the launches, and no recording of it has been tried)
+  const bool can = c->dd_graphs && c->timing_mask == 0 && !mods::has_hooks(c) && !mods::has_nets(c) && det->detectorType != MODS_DET_MSER &&
+                   c->dsp_scales < 2;
   if (!can) { mods::dev_state_changed(c); return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc); }
   mods_ctx::DdKey key;
   key.img = img_dev; key.img_u8 = c->img_u8_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
@@ -529,6 +531,7 @@ int mods_ctx_u8_kernels(mods_ctx *c, int mask) {
 static int dd_call(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
                    const mods_describe_params *desc, int *n_detected_host, int *n_regions_host) {
   int rc;
+  if ((rc = mods::dsp_check(c, desc))) return rc;      // (before the detector's launches)
   if ((rc = dd_run(c, img_dev, n_img, w, h, stride, det, desc))) return rc;
   int *hc = c->host_counts;
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
@@ -761,6 +764,49 @@ int mods_sift_patch(mods_ctx *c, const float *patch, int ps, int rootsift, doubl
   if (rc) return rc;
   MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev, patch, sizeof(float) * ps * ps, hipMemcpyHostToDevice, c->stream));
   if ((rc = launch_sift_patch_test(c, c->input_dev, ps, rootsift, maxBinValue, (uint8_t *)c->tmp_dev.get()))) return rc;
+  MODS_HIP_CHECK(hipMemcpyAsync(out128, c->tmp_dev, 128, hipMemcpyDeviceToHost, c->stream));
+  MODS_HIP_CHECK(mods::stream_wait(c->stream));
+  return MODS_OK;
+}
+
+// ---- domain-size pooling of the SIFT descriptor (contract in include/mods_hip.h) ----------------
+static int dsp_args(const char *who, int K, double a, double b) {
+  if (K == 0 || K == 1) return MODS_OK;
+  if (K < 0 || K > 8) { set_error("%s: numScales %d (0 or 1: off; 2 .. 8)", who, K); return MODS_E_ARG; }
+  if (!std::isfinite(a) || !(a > 0)) { set_error("%s: startCoef %g (finite, > 0)", who, a); return MODS_E_ARG; }
+  if (!std::isfinite(b) || !(b > a) || b > 4) { set_error("%s: endCoef %g (finite, startCoef < endCoef <= 4)", who, b); return MODS_E_ARG; }
+  return MODS_OK;
+}
+int mods_ctx_domain_pooling(mods_ctx *c, int numScales, double startCoef, double endCoef) {
+  const int rc = dsp_args("domain_pooling", numScales, startCoef, endCoef);
+  if (rc) return rc;
+  if (!c) { set_error("domain_pooling: null context"); return MODS_E_ARG; }
+  const bool on = numScales >= 2;
+  c->dsp_scales = on ? numScales : 0;
+  c->dsp_start = on ? startCoef : 0;
+  c->dsp_end = on ? endCoef : 0;
+  mods::dev_state_changed(c);        // (recorded launch chains are not replayed across the change)
+  return MODS_OK;
+}
+int mods_ctx_domain_pooling_get(const mods_ctx *c, int *numScales, double *startCoef, double *endCoef) {
+  if (!c) { set_error("domain_pooling_get: null context"); return MODS_E_ARG; }
+  if (numScales) *numScales = c->dsp_scales;
+  if (startCoef) *startCoef = c->dsp_start;
+  if (endCoef) *endCoef = c->dsp_end;
+  return MODS_OK;
+}
+// the pooled twin of mods_sift_patch: K host patches [K][ps][ps] of one region through the accumulate and finish kernels
+int mods_test_sift_pooled(mods_ctx *c, const float *patches, int K, int ps, int rootsift, int half, int photoNorm, double maxBinValue,
+                          uint8_t *out128) {
+  if (!c || !patches || !out128) { set_error("test_sift_pooled: null argument"); return MODS_E_ARG; }
+  if (K < 1 || K > 8) { set_error("test_sift_pooled: %d patches (1 .. 8)", K); return MODS_E_ARG; }
+  if ((size_t)K * ps * ps > (size_t)c->max_w * c->max_h * c->batch) { set_error("test_sift_pooled: the patches do not fit the context's input buffer"); return MODS_E_ARG; }
+  mods_describe_params dp = {5.1962, c->desc_ori_ps ? c->desc_ori_ps : 32, 1, 0.8, 5.1962, ps, photoNorm, rootsift, maxBinValue};
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  int rc = describe_configure(c, &dp);
+  if (rc) return rc;
+  MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev, patches, sizeof(float) * (size_t)K * ps * ps, hipMemcpyHostToDevice, c->stream));
+  if ((rc = launch_sift_pooled_test(c, c->input_dev, K, ps, rootsift, half, photoNorm, maxBinValue, (uint8_t *)c->tmp_dev.get()))) return rc;
   MODS_HIP_CHECK(hipMemcpyAsync(out128, c->tmp_dev, 128, hipMemcpyDeviceToHost, c->stream));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   return MODS_OK;

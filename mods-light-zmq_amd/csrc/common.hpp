@@ -249,6 +249,11 @@ struct mods_ctx {
   mods::Buf<int> inside_count;       // [batch] keypoints that pass the centre test (the reference's unoriented list)
   std::vector<int> last_inside_counts;
   mods::Buf<float> desc_scratch;
+  // domain-size pooling of the SIFT descriptor (mods_ctx_domain_pooling; sift.hip): dsp_scales = 0 is off; the accumulators
+  // [batch][reg_cap][128] are reserved by the first describe call with pooling on
+  int dsp_scales = 0;
+  double dsp_start = 0, dsp_end = 0;
+  mods::Buf<double> dsp_acc;
   int blur_table_ps = 0;
   mods::Buf<float> blur_table_dev;   // per-P2 taps / resampling sequence / source indices of the LDS extraction tier (sift.hip: blur_table_kernel)
   // external descriptor (e.g. a ZMQ daemon): when set, patches go to this function instead of the SIFT kernel
@@ -423,6 +428,11 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par);
 int launch_dominant_angle_test(mods_ctx *ctx, const float *patch_dev, int ps, double th, float *out_dev);
 int launch_sift_patch_test(mods_ctx *ctx, const float *patch_dev, int ps, int root, double max_bin, uint8_t *out_dev);
+// its pooled twin (mods_test_sift_pooled), and what a describe call with domain-size pooling on cannot be combined with
+// (MODS_E_ARG, before anything is launched)
+int launch_sift_pooled_test(mods_ctx *ctx, const float *patches_dev, int K, int ps, int root, int half, int photo, double max_bin,
+                            uint8_t *out_dev);
+int dsp_check(mods_ctx *ctx, const mods_describe_params *par);
 
 // nets.hip
 inline bool has_hooks(const mods_ctx *c) { return c->ext_fn || c->shape_fn || c->ori_fn; }          // host callbacks (one context)

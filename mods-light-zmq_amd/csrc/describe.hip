@@ -776,6 +776,13 @@ static int external_orientation(mods_ctx *ctx, const float *img_dev, int n_img, 
   return MODS_OK;
 }
 
+int dsp_check(mods_ctx *ctx, const mods_describe_params *par) {
+  if (ctx->dsp_scales < 2) return MODS_OK;
+  if (par->fastExtraction) { set_error("domain-size pooling with FastPatchExtraction is not supported"); return MODS_E_ARG; }
+  if (ctx->ext_fn || ctx->ext_net) { set_error("domain-size pooling with an external descriptor or a descriptor network is not supported"); return MODS_E_ARG; }
+  return MODS_OK;
+}
+
 // cv::invert(H, Hinv, DECOMP_LU) for 3x3 doubles: OpenCV's closed form (all zeros when singular)
 static void invert3_cv(const double *S, double *t) {
   double d = S[0] * (S[4] * S[8] - S[5] * S[7]) - S[1] * (S[3] * S[8] - S[5] * S[6]) + S[2] * (S[3] * S[7] - S[4] * S[6]);
@@ -791,8 +798,9 @@ static void invert3_cv(const double *S, double *t) {
 // 144-149): identity view.  det_copy_dev (optional): receives the described regions in the view frame.
 int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev) {
-  int rc = describe_configure(ctx, par);
+  int rc = dsp_check(ctx, par);
   if (rc) return rc;
+  if ((rc = describe_configure(ctx, par))) return rc;
   DescConst k;
   k.view = 0; k.ow = w; k.oh = h;
   for (int i = 0; i < 6; i++) k.Hinv[i] = (i == 0 || i == 4) ? 1.0 : 0.0;
@@ -859,12 +867,28 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
                          (const OriOut *)ctx->ori_dev.get(), ctx->regions_dev, ctx->region_count, ctx->inside_count);
     MODS_HIP_CHECK(hipGetLastError());
   }
-  rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8);
-  if (rc) return rc;
-  ctx->have_half = false;
-  if (par->halfDesc && !external) {
-    if ((rc = launch_half_sift(ctx, n_img, k, dmask, tab))) return rc;
-    ctx->have_half = true;
+  if (ctx->dsp_scales >= 2) {
+    // domain-size pooling: one extraction per domain size mr_k = desc_mrSize * c_k into the patch store, its raw histograms added
+    // to the accumulators in scale order, the tail once (the region lists do not depend on desc_mr: k.ks is the border rule)
+    const int K = ctx->dsp_scales;
+    const size_t need = (size_t)n_img * k.reg_cap * 128;
+    MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->dsp_acc, need, need));
+    for (int s = 0; s < K; s++) {
+      DescConst ks = k;
+      ks.desc_mr = par->desc_mrSize * (ctx->dsp_start + s * ((ctx->dsp_end - ctx->dsp_start) / (K - 1)));
+      if ((rc = launch_extract_and_sift(ctx, img_dev, n_img, ks, dmask, tab, false, img_u8))) return rc;
+      if ((rc = launch_dsp_accumulate(ctx, n_img, ks, dmask, tab, s == 0))) return rc;
+    }
+    if ((rc = launch_dsp_finish(ctx, n_img, k, par->halfDesc != 0))) return rc;
+    ctx->have_half = par->halfDesc != 0;
+  } else {
+    rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8);
+    if (rc) return rc;
+    ctx->have_half = false;
+    if (par->halfDesc && !external) {
+      if ((rc = launch_half_sift(ctx, n_img, k, dmask, tab))) return rc;
+      ctx->have_half = true;
+    }
   }
   if (external && (rc = external_describe(ctx, n_img, k))) return rc;
   if (det_copy_dev)

@@ -69,5 +69,9 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
 // patch store left by launch_extract_and_sift (block-per-region SIFT kernel)
 int launch_half_sift(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, const SiftTab *tab);
 int launch_sift_patch_test(mods_ctx *ctx, const float *patch_dev, int ps, int root, double max_bin, uint8_t *out_dev);
+// domain-size pooling (mods_ctx_domain_pooling): the raw histograms of the patch store added into ctx->dsp_acc (first: stored), and
+// the tail on the sums -> regions_dev (and the HalfSIFT twins)
+int launch_dsp_accumulate(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool first);
+int launch_dsp_finish(mods_ctx *ctx, int n_img, DescConst k, bool want_half);
 
 }  // namespace mods

@@ -209,6 +209,15 @@ int mods_pipeline_match_mutual(mods_pipeline *p, int mode) {
   return MODS_OK;
 }
 
+// domain-size pooling of every description of the pipeline (mods_ctx_domain_pooling on the workers' contexts)
+int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCoef, double endCoef) {
+  if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: domain_pooling after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) { const int rc = mods_ctx_domain_pooling(c, numScales, startCoef, endCoef); if (rc) return rc; }
+  return MODS_OK;
+}
+
 int mods_pipeline_create_ex(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
                             int pairs_per_batch, mods_pipeline **out) {
   return mods_pipeline_create_clahe(device, w, h, par, gpu_workers, verify_workers, pairs_per_batch, nullptr, out);

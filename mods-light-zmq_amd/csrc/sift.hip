@@ -964,10 +964,9 @@ __device__ void sift_tables(const SiftTab *__restrict__ tab, int ps, float *s_wr
   }
 }
 
-__device__ void sift_from_patch(float *s_patch, const float *__restrict__ mask, const float *s_w, const double *s_lut, int ps,
-                                bool rootsift, double max_bin, float2 *s_px, unsigned char *s_bo, double *s_vec, double *s_red,
-                                uint8_t *out, bool half = false) {
-  double *s_sq = (double *)(((uintptr_t)s_patch + 7) & ~(uintptr_t)7);   // the patch is dead once the gradients are taken
+// The raw histogram: gradients, LUT orientation bins and the ordered per-bin sums of samplePatch; leaves vec[128] in s_vec.
+__device__ void sift_hist_from_patch(const float *s_patch, const float *__restrict__ mask, const float *s_w, const double *s_lut, int ps,
+                                     float2 *s_px, unsigned char *s_bo, double *s_vec) {
   const int tid = threadIdx.x;
   const int pp = ps * ps;
   const double M_PI_DOUBLED = 6.28318530718;
@@ -1026,6 +1025,12 @@ __device__ void sift_from_patch(float *s_patch, const float *__restrict__ mask, 
     s_vec[tid] = acc;
   }
   __syncthreads();
+}
+
+// The tail on a raw histogram in s_vec: fold (half), normalise / clip / renormalise, RootSIFT or plain SIFT, quantise.
+// s_sq: 128 doubles of scratch, s_red: 2 doubles.  Block of at least 128 threads.
+__device__ void sift_tail(double *s_vec, double *s_sq, double *s_red, bool rootsift, double max_bin, uint8_t *out, bool half) {
+  const int tid = threadIdx.x;
   // doHalfSIFT (siftdesc.cpp:411-436): the raw histogram is folded, half[i*4 + j] = vec[i*8 + j] + vec[i*8 + j + 4], and the
   // 64 values take the place of the 128 below (the upper half is zero: it adds +0.0 to the ordered sums and quantises to 0)
   if (half) {
@@ -1094,6 +1099,14 @@ __device__ void sift_from_patch(float *s_patch, const float *__restrict__ mask, 
   __syncthreads();
 }
 
+__device__ void sift_from_patch(float *s_patch, const float *__restrict__ mask, const float *s_w, const double *s_lut, int ps,
+                                bool rootsift, double max_bin, float2 *s_px, unsigned char *s_bo, double *s_vec, double *s_red,
+                                uint8_t *out, bool half = false) {
+  double *s_sq = (double *)(((uintptr_t)s_patch + 7) & ~(uintptr_t)7);   // the patch is dead once the gradients are taken
+  sift_hist_from_patch(s_patch, mask, s_w, s_lut, ps, s_px, s_bo, s_vec);
+  sift_tail(s_vec, s_sq, s_red, rootsift, max_bin, out, half);
+}
+
 struct SiftLds {   // carve of the dynamic LDS of the SIFT kernels
   float *patch, *g, *w; float2 *px; unsigned char *bo; unsigned short *midx; double *vec, *red, *lut; float *redf;
   __device__ SiftLds(float *base, int ps) {
@@ -1115,18 +1128,13 @@ static size_t sift_lds_bytes(int ps) {
   return sizeof(float) * (ppa + 2 * ppa + 4 * ps + 4) + sizeof(double) * (130 + 256) + sizeof(unsigned short) * ppa + ppa + 32;
 }
 
-// grid = (N, n_img), block = 256: patches -> descriptors
-__global__ __launch_bounds__(256, 5) void sift_kernel(DescConst k, const float *__restrict__ patches, mods_region *__restrict__ reg_all,
-                                                   const int *__restrict__ reg_count, const float *__restrict__ mask,
-                                                   const SiftTab *__restrict__ tab) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int ps = k.desc_ps, pp = ps * ps;
-  SiftLds L(smem, ps);
-  const int tid = threadIdx.x;
-  const int b = blockIdx.y;
+// what a workgroup of the block-per-region kernels sets up once: spatial weights, the atan2 table and the raster-ordered list of
+// the masked pixels (one wave, ballot compaction); returns the length of that list.  Ends with a barrier.
+__device__ int sift_block_setup(const SiftLds &L, const float *__restrict__ mask, const SiftTab *__restrict__ tab, int ps) {
+  const int tid = threadIdx.x, pp = ps * ps;
   sift_tables(tab, ps, L.w);
   for (int i = tid; i < 256; i += 256) L.lut[i] = g_atan_lut[i];
-  if (tid < 64) {   // raster-ordered list of the masked pixels, one wave, ballot compaction
+  if (tid < 64) {
     int c = 0;
     for (int base = 0; base < pp; base += 64) {
       const int p = base + tid;
@@ -1138,7 +1146,19 @@ __global__ __launch_bounds__(256, 5) void sift_kernel(DescConst k, const float *
     if (tid == 0) ((int *)L.redf)[2] = c;
   }
   __syncthreads();
-  const int n_mask = ((int *)L.redf)[2];
+  return ((int *)L.redf)[2];
+}
+
+// grid = (N, n_img), block = 256: patches -> descriptors
+__global__ __launch_bounds__(256, 5) void sift_kernel(DescConst k, const float *__restrict__ patches, mods_region *__restrict__ reg_all,
+                                                   const int *__restrict__ reg_count, const float *__restrict__ mask,
+                                                   const SiftTab *__restrict__ tab) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int ps = k.desc_ps, pp = ps * ps;
+  SiftLds L(smem, ps);
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int n_mask = sift_block_setup(L, mask, tab, ps);
   mods_region *reg = reg_all + (size_t)b * k.max_reg;
   int n = reg_count[b];
   if (n > k.reg_cap) n = k.reg_cap;
@@ -1149,6 +1169,60 @@ __global__ __launch_bounds__(256, 5) void sift_kernel(DescConst k, const float *
     __syncthreads();
     if (k.photo) photonorm_patch(L.patch, L.midx, n_mask, L.g, pp, L.redf);
     sift_from_patch(L.patch, mask, L.w, L.lut, ps, k.root != 0, k.max_bin, L.px, L.bo, L.vec, L.red, reg[ri].desc, k.half_desc != 0);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// Domain-size pooling (mods_ctx_domain_pooling): the raw histograms of a region's patches at K domain sizes are summed in double,
+// in scale order, and the sum takes the tail once.  The host extracts one scale at a time into the patch store (describe.hip).
+// ---------------------------------------------------------------------------------------
+// grid = (N, n_img), block = 256: the raw histogram of every patch of the store -> acc[n_img][reg_cap][128]; the first scale stores,
+// the others add.  The block-per-region form, for the patch sizes that sift_wave2_kernel does not take
+__global__ __launch_bounds__(256, 5) void dsp_accumulate_kernel(DescConst k, const float *__restrict__ patches, double *__restrict__ acc,
+                                                                const int *__restrict__ reg_count, const float *__restrict__ mask,
+                                                                const SiftTab *__restrict__ tab, int first) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int ps = k.desc_ps, pp = ps * ps;
+  SiftLds L(smem, ps);
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  const int n_mask = sift_block_setup(L, mask, tab, ps);
+  int n = reg_count[b];
+  if (n > k.reg_cap) n = k.reg_cap;
+  for (int ri = blockIdx.x; ri < n; ri += gridDim.x) {
+    const size_t slot = (size_t)b * k.reg_cap + ri;
+    const float *src = patches + slot * pp;
+    __syncthreads();
+    for (int p = tid; p < pp; p += 256) L.patch[p] = src[p];
+    __syncthreads();
+    if (k.photo) photonorm_patch(L.patch, L.midx, n_mask, L.g, pp, L.redf);
+    sift_hist_from_patch(L.patch, mask, L.w, L.lut, ps, L.px, L.bo, L.vec);
+    if (tid < 128) {
+      double *a = acc + slot * 128;
+      a[tid] = first ? L.vec[tid] : a[tid] + L.vec[tid];
+    }
+  }
+}
+
+// grid = (N, n_img), block = 128: the tail on every pooled histogram.  out / out_half: where the descriptor bytes of (image 0,
+// region 0) go, full and HalfSIFT (either may be null); img_stride / reg_stride: bytes between images / regions.
+__global__ __launch_bounds__(128) void dsp_finish_kernel(DescConst k, const double *__restrict__ acc, const int *__restrict__ reg_count,
+                                                         uint8_t *__restrict__ out, uint8_t *__restrict__ out_half, size_t img_stride,
+                                                         size_t reg_stride) {
+  __shared__ double s_vec[128], s_sq[128], s_red[2];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.y;
+  int n = reg_count[b];
+  if (n > k.reg_cap) n = k.reg_cap;
+  for (int ri = blockIdx.x; ri < n; ri += gridDim.x) {
+    const double *a = acc + ((size_t)b * k.reg_cap + ri) * 128;
+    for (int half = 0; half < 2; half++) {
+      uint8_t *o = half ? out_half : out;
+      if (!o) continue;
+      s_vec[tid] = a[tid];
+      __syncthreads();
+      sift_tail(s_vec, s_sq, s_red, k.root != 0, k.max_bin, o + (size_t)b * img_stride + (size_t)ri * reg_stride, half != 0);
+    }
   }
 }
 
@@ -1194,10 +1268,13 @@ static size_t sift_wave2_lds_bytes(int ps) {
 
 // NC: pixel columns a histogram lane walks per row = the widest span of positive column weights of a spatial bin, rounded up to
 // an even number (15 -> 16 for the 41-pixel patch; SW_CW = 18 covers every patch size this kernel takes)
-template <int NC>
+// POOL (domain-size pooling): the kernel stops at the raw histograms and adds them to pool[n_img][reg_cap][128] (pool_first: stores
+// them) instead of taking them through the tail - the wave form of dsp_accumulate_kernel
+template <int NC, bool POOL = false>
 __global__ __launch_bounds__(64 * S2_WAVES, 3) void sift_wave2_kernel(DescConst k, const float *__restrict__ patches, mods_region *__restrict__ reg_all,
                                                                         const int *__restrict__ reg_count, const float *__restrict__ mask,
-                                                                        const SiftTab *__restrict__ tab, int n_img, int *__restrict__ next_unit) {
+                                                                        const SiftTab *__restrict__ tab, int n_img, int *__restrict__ next_unit,
+                                                                        double *__restrict__ pool, int pool_first) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ps = k.desc_ps, pp = ps * ps, ppa = (pp + 7) & ~7;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -1442,6 +1519,17 @@ __global__ __launch_bounds__(64 * S2_WAVES, 3) void sift_wave2_kernel(DescConst 
       S2PROF(4)
     }
     wave_sync();
+    if constexpr (POOL) {   // vec[i] of region rr sits at acc[s2_vec(rr, i)]: eight lanes per region, 64 contiguous bytes per step
+      const int rr = lane >> 3;
+      if (ri0 + rr < n) {
+        double *dst = pool + ((size_t)b * k.reg_cap + ri0 + rr) * 128;
+        for (int i = lane & 7; i < 128; i += 8) {
+          const double x = acc[s2_vec(rr, i)];
+          dst[i] = pool_first ? x : dst[i] + x;
+        }
+      }
+      continue;
+    }
     // ---- normalize / clip / renormalise (siftdesc.cpp:133-158, 199-210, 248-257) and the RootSIFT mapping
     double *tmp = (double *)pxrow;      // 8 doubles of hand-over; the pixel row is idle here
     unsigned long long redo = ~0ull;   // bit 8 rr.. : region rr still takes part
@@ -1542,6 +1630,22 @@ __global__ __launch_bounds__(256) void sift_patch_test_kernel(const float *__res
   sift_from_patch(L.patch, mask, L.w, L.lut, ps, root != 0, max_bin, L.px, L.bo, L.vec, L.red, out);
 }
 
+// widest span of positive column weights of a spatial bin (siftdesc.cpp:22-71: step = 5 / (2 * (ps / 2)), bins x - 1 and x)
+static int sift_col_span(int ps) {
+  int span = 0;
+  const float step = 5.0f / (float)(2 * (ps >> 1));
+  for (int bc = 0; bc < 4; bc++) {
+    int lo = ps, hi = -1;
+    for (int i = 0; i < ps; i++) {
+      const float x = step * i; const int xi = (int)x; const float w1 = x - xi, w0 = 1.0f - w1;
+      const bool on = (xi - 1 == bc && w0 > 0) || (xi == bc && w1 > 0);
+      if (on) { lo = std::min(lo, i); hi = i; }
+    }
+    if (hi >= lo) span = std::max(span, hi - lo + 1);
+  }
+  return span;
+}
+
 // ---------------------------------------------------------------------------------------
 int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool run_sift,
                             const unsigned char *img_u8) {
@@ -1623,20 +1727,7 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
     static DynLdsOnce once16, once18;
     MODS_HIP_CHECK(dyn_lds_once(once16, (const void *)sift_wave2_kernel<16>, 160 * 1024, ctx->device));
     MODS_HIP_CHECK(dyn_lds_once(once18, (const void *)sift_wave2_kernel<SW_CW>, 160 * 1024, ctx->device));
-    // widest span of positive column weights of a spatial bin (siftdesc.cpp:22-71: step = 5 / (2 * (ps / 2)), bins x - 1 and x)
-    int span = 0;
-    {
-      const float step = 5.0f / (float)(2 * (ps >> 1));
-      for (int bc = 0; bc < 4; bc++) {
-        int lo = ps, hi = -1;
-        for (int i = 0; i < ps; i++) {
-          const float x = step * i; const int xi = (int)x; const float w1 = x - xi, w0 = 1.0f - w1;
-          const bool on = (xi - 1 == bc && w0 > 0) || (xi == bc && w1 > 0);
-          if (on) { lo = std::min(lo, i); hi = i; }
-        }
-        if (hi >= lo) span = std::max(span, hi - lo + 1);
-      }
-    }
+    const int span = sift_col_span(ps);
     // persistent: one workgroup of 12 waves per CU, work units pulled from bl->sift_next (zeroed with bl above; batches of
     // more than S2_MAX_IMG images take one launch per S2_MAX_IMG images)
     for (int b0 = 0; b0 < n_img; b0 += S2_MAX_IMG) {
@@ -1646,10 +1737,10 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
       mods_region *regs = ctx->regions_dev + (size_t)b0 * k.max_reg;
       if (span <= 16)
         hipLaunchKernelGGL(sift_wave2_kernel<16>, dim3(ctx->n_cu), dim3(64 * S2_WAVES), sift_wave2_lds_bytes(ps), ctx->stream, k, pch,
-                           regs, ctx->region_count + b0, dmask, tab, nb, &bl->sift_next);
+                           regs, ctx->region_count + b0, dmask, tab, nb, &bl->sift_next, (double *)nullptr, 0);
       else
         hipLaunchKernelGGL(sift_wave2_kernel<SW_CW>, dim3(ctx->n_cu), dim3(64 * S2_WAVES), sift_wave2_lds_bytes(ps), ctx->stream, k, pch,
-                           regs, ctx->region_count + b0, dmask, tab, nb, &bl->sift_next);
+                           regs, ctx->region_count + b0, dmask, tab, nb, &bl->sift_next, (double *)nullptr, 0);
     }
   }
   MODS_HIP_CHECK(hipGetLastError());
@@ -1666,6 +1757,86 @@ int launch_half_sift(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, 
   const float *patches = ctx->desc_scratch;      // the patch store of launch_extract_and_sift: [n_img][reg_cap][ps*ps]
   hipLaunchKernelGGL(sift_kernel, dim3(2048, n_img), dim3(256), sift_lds_bytes(ps), ctx->stream, k, patches, ctx->regions_half_dev,
                      ctx->region_count, dmask, tab);
+  MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
+}
+
+// One scale of the pooled description: the raw histograms of patches[n_img][k.reg_cap][ps*ps] into acc[n_img][k.reg_cap][128] (first:
+// stored, else added).  Patch sizes up to 45 take the wave form (sift_wave2_kernel<.., true>, work units pulled from *next_unit, which
+// the caller has zeroed), larger ones the block-per-region form, as the unpooled description does.
+static int dsp_accumulate(mods_ctx *ctx, const float *patches, double *acc, const int *reg_count, int *next_unit, int n_img, DescConst k,
+                          const float *dmask, const SiftTab *tab, bool first) {
+  const int ps = k.desc_ps, pp = ps * ps;
+  if (ps > 45) {
+    hipLaunchKernelGGL(dsp_accumulate_kernel, dim3(2048, n_img), dim3(256), sift_lds_bytes(ps), ctx->stream, k, patches, acc, reg_count, dmask,
+                       tab, first ? 1 : 0);
+    MODS_HIP_CHECK(hipGetLastError());
+    return MODS_OK;
+  }
+  static DynLdsOnce once16, once18;
+  MODS_HIP_CHECK(dyn_lds_once(once16, (const void *)sift_wave2_kernel<16, true>, 160 * 1024, ctx->device));
+  MODS_HIP_CHECK(dyn_lds_once(once18, (const void *)sift_wave2_kernel<SW_CW, true>, 160 * 1024, ctx->device));
+  const int span = sift_col_span(ps);
+  for (int b0 = 0; b0 < n_img; b0 += S2_MAX_IMG) {
+    const int nb = std::min(S2_MAX_IMG, n_img - b0);
+    if (b0) MODS_HIP_CHECK(hipMemsetAsync(next_unit, 0, sizeof(int), ctx->stream));
+    const float *pch = patches + (size_t)b0 * k.reg_cap * pp;
+    double *pool = acc + (size_t)b0 * k.reg_cap * 128;
+    if (span <= 16)
+      hipLaunchKernelGGL((sift_wave2_kernel<16, true>), dim3(ctx->n_cu), dim3(64 * S2_WAVES), sift_wave2_lds_bytes(ps), ctx->stream, k, pch,
+                         (mods_region *)nullptr, reg_count + b0, dmask, tab, nb, next_unit, pool, first ? 1 : 0);
+    else
+      hipLaunchKernelGGL((sift_wave2_kernel<SW_CW, true>), dim3(ctx->n_cu), dim3(64 * S2_WAVES), sift_wave2_lds_bytes(ps), ctx->stream, k, pch,
+                         (mods_region *)nullptr, reg_count + b0, dmask, tab, nb, next_unit, pool, first ? 1 : 0);
+  }
+  MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
+}
+
+// ... of the patch store that launch_extract_and_sift (run_sift = false) has just filled: its work-unit counter was zeroed with the
+// big-tier bookkeeping and nothing has used it since
+int launch_dsp_accumulate(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool first) {
+  StageScope ts(ctx, MODS_STAGE_DESCRIBE);
+  StageScope ts_sift(ctx, MODS_STAGE_SIFT);
+  BigLists *bl = (BigLists *)(ctx->desc_scratch + (size_t)n_img * k.reg_cap * k.desc_ps * k.desc_ps);
+  return dsp_accumulate(ctx, ctx->desc_scratch, ctx->dsp_acc, ctx->region_count, &bl->sift_next, n_img, k, dmask, tab, first);
+}
+
+// ... and the tail: descriptors into regions_dev, and into the HalfSIFT twins (copies of the regions, as launch_half_sift makes them)
+int launch_dsp_finish(mods_ctx *ctx, int n_img, DescConst k, bool want_half) {
+  StageScope ts(ctx, MODS_STAGE_DESCRIBE);
+  StageScope ts_sift(ctx, MODS_STAGE_SIFT);
+  uint8_t *out_half = nullptr;
+  if (want_half) {
+    MODS_HIP_CHECK(ctx->regions_half_dev.reserve((size_t)ctx->max_cand * ctx->batch));
+    MODS_HIP_CHECK(hipMemcpyAsync(ctx->regions_half_dev, ctx->regions_dev, sizeof(mods_region) * (size_t)ctx->max_cand * n_img,
+                                  hipMemcpyDeviceToDevice, ctx->stream));
+    out_half = (uint8_t *)ctx->regions_half_dev.get() + offsetof(mods_region, desc);
+  }
+  hipLaunchKernelGGL(dsp_finish_kernel, dim3(4096, n_img), dim3(128), 0, ctx->stream, k, (const double *)ctx->dsp_acc.get(),
+                     (const int *)ctx->region_count, (uint8_t *)ctx->regions_dev.get() + offsetof(mods_region, desc), out_half,
+                     sizeof(mods_region) * (size_t)k.max_reg, sizeof(mods_region));
+  MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
+}
+
+// mods_test_sift_pooled: K patches [K][ps*ps] of one region in HBM -> 128 bytes (the HalfSIFT ones when half)
+int launch_sift_pooled_test(mods_ctx *ctx, const float *patches_dev, int K, int ps, int root, int half, int photo, double max_bin,
+                            uint8_t *out_dev) {
+  MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->dsp_acc, 130, 130));
+  DescConst k = {};
+  k.desc_ps = ps; k.photo = photo; k.root = root; k.max_bin = max_bin; k.reg_cap = 1; k.max_reg = 1;
+  const float *dmask = ctx->desc_tables_dev + kTabDescMask;
+  const SiftTab *tab = (const SiftTab *)(ctx->desc_tables_dev + kTabSift);
+  int *cnt = (int *)(ctx->dsp_acc.get() + 128);                 // behind the accumulator: {region count = 1, work-unit counter}
+  static const int cnt_init[2] = {1, 0};
+  for (int s = 0; s < K; s++) {
+    MODS_HIP_CHECK(hipMemcpyAsync(cnt, cnt_init, sizeof(cnt_init), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = dsp_accumulate(ctx, patches_dev + (size_t)s * ps * ps, ctx->dsp_acc, cnt, cnt + 1, 1, k, dmask, tab, s == 0);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(dsp_finish_kernel, dim3(1), dim3(128), 0, ctx->stream, k, (const double *)ctx->dsp_acc.get(), (const int *)cnt,
+                     half ? (uint8_t *)nullptr : out_dev, half ? out_dev : (uint8_t *)nullptr, (size_t)128, (size_t)128);
   MODS_HIP_CHECK(hipGetLastError());
   return MODS_OK;
 }
