@@ -158,9 +158,20 @@ long mods_ctx_graph_replays(const mods_ctx *ctx);
    included) */
 long mods_ctx_u8_source_calls(const mods_ctx *ctx);
 /* which kernels sample from the 8-bit images in such calls: bit 0 orient_kernel, 1 extract_small_kernel, 2 big_fused_kernel,
-   3 big_sample_kernel; mask < 0 (the default): the library's measured choice (extract_small and big_fused).  Every choice gives the
-   same regions; the tests use it to run the forms the default leaves out. */
+   3 big_sample_kernel; bits 4 - 7: the same four sample from the library's own copy of those images in 16-byte column strips, which
+   the conversion launch of the call then makes (it goes before bits 0 - 3); mask < 0 (the default): the library's measured choice
+   (orient, extract_small and big_fused from the strips, big_sample from fp32).  Every choice gives the same regions; the tests use
+   it to run the forms the default leaves out. */
 int mods_ctx_u8_kernels(mods_ctx *ctx, int mask);
+/* The strip layout, for the tests.  _layout: the layout's width limit and, for a w x h image, strips per image, bytes per strip
+   and bytes per image (no device needed); _strip_of: the strip of the columns 0 .. n - 1; _offsets: the byte offset of every
+   pixel pair's first pixel, out[h - 1][w - 1]; _fetch: the strip copy of a packed 8-bit host batch as the library makes it on
+   the device, the batch staged src_offset (0 .. 15) bytes into the staging area. */
+long mods_ctx_u8_strip_calls(const mods_ctx *ctx);          /* calls so far that had the strip copy as well */
+int mods_u8_strips_layout(int w, int h, unsigned *max_width, unsigned *n_strips, unsigned *pitch, size_t *image_bytes);
+void mods_u8_strips_strip_of(unsigned n, unsigned *out);
+int mods_u8_strips_offsets(int w, int h, unsigned *out);
+int mods_u8_strips_fetch(mods_ctx *ctx, const unsigned char *img_u8_host, int n_img, int w, int h, int src_offset, unsigned char *out);
 /* Streams the Hessian scale space of a large batch is built on: 2 (default) = the octaves from the third on, and their non-maximum
    suppression, run on a side stream next to the large octaves' last level and NMS; 1 = everything on the context's stream (what
    per-launch timing wants).  The planes and the candidates are the same either way. */
@@ -768,6 +779,10 @@ int mods_pipeline_capacity(const mods_pipeline *p);    /* pairs that may be in f
 int mods_pipeline_timing_enable(mods_pipeline *p, int stage_mask);
 int mods_pipeline_timing_read(mods_pipeline *p, int stage, double *total_ms, int *launches, double *bytes);
 long mods_pipeline_u8_source_calls(mods_pipeline *p);   /* sum of mods_ctx_u8_source_calls over the GPU workers' contexts */
+/* mods_ctx_u8_kernels on every GPU worker's context, before the first submit (later: MODS_E_ARG), and the sum of their
+   mods_ctx_u8_strip_calls */
+int mods_pipeline_u8_kernels(mods_pipeline *p, int mask);   /* on every worker's context; before the first submit */
+long mods_pipeline_u8_strip_calls(mods_pipeline *p);
 long mods_pipeline_graph_replays(mods_pipeline *p);   /* batches whose detect + describe chain was a graph replay (mods_ctx_graphs) */
 /* CPU seconds the GPU workers' / the verify workers' own threads have spent inside their stages since the last reset (thread clocks;
    the RANSAC task pool's helper threads are not in them).  What a pair costs the host: needed to size ranks per node. */

@@ -119,6 +119,28 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def u8_strips_layout(w, h):
+    """(width limit, strips per image, bytes per strip, bytes per image) of the 8-bit strip copy of a w x h image (csrc/u8_strips.hpp;
+    no device needed)"""
+    lim, ns, pitch, nbytes = C.c_uint(), C.c_uint(), C.c_uint(), C.c_size_t()
+    _check(lib().mods_u8_strips_layout(int(w), int(h), C.byref(lim), C.byref(ns), C.byref(pitch), C.byref(nbytes)))
+    return lim.value, ns.value, pitch.value, nbytes.value
+
+
+def u8_strips_strip_of(n):
+    """the strip of each column 0 .. n - 1, by the multiply and shift the kernels use"""
+    out = np.zeros(int(n), np.uint32)
+    lib().mods_u8_strips_strip_of(C.c_uint(int(n)), C.c_void_p(out.ctypes.data))
+    return out
+
+
+def u8_strips_offsets(w, h):
+    """byte offset in an image's strip copy of every pixel (x <= w - 2, y <= h - 2) that a pixel pair can start at: uint32 [h - 1][w - 1]"""
+    out = np.zeros((int(h) - 1, int(w) - 1), np.uint32)
+    _check(lib().mods_u8_strips_offsets(int(w), int(h), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 class ViewGeom(C.Structure):
     """mods_view_geom: what GenerateSynthImageCorr derives before touching pixels."""
     _fields_ = [("identity", C.c_int), ("w_rot", C.c_int), ("h_rot", C.c_int), ("w_new", C.c_int), ("h_new", C.c_int),
@@ -447,8 +469,24 @@ class Context:
         return int(lib().mods_ctx_u8_source_calls(self.h))
 
     def set_u8_kernels(self, mask):
-        """bit 0 orient, 1 extract_small, 2 big_fused, 3 big_sample sample from the 8-bit images in detect_describe_dev_u8; -1: default"""
+        """bit 0 orient, 1 extract_small, 2 big_fused, 3 big_sample sample from the 8-bit images in detect_describe_dev_u8, bits 4 - 7:
+        the same four from the strip copy of those images (it goes first); -1: default"""
         _check(lib().mods_ctx_u8_kernels(self.h, int(mask)))
+
+    def u8_strip_calls(self):
+        """calls so far whose 8-bit images were laid out in strips as well (a kernel of the mask samples from them)"""
+        lib().mods_ctx_u8_strip_calls.restype = C.c_long
+        return int(lib().mods_ctx_u8_strip_calls(self.h))
+
+    def u8_strips_fetch(self, batch_u8, src_offset=0):
+        """the strip copy (u8_strips_layout) of a packed uint8 batch [n][h][w] as the conversion launch makes it on the device, the batch
+        staged src_offset bytes into the staging area: uint8 [n][n_strips][strip_pitch // 16][16]"""
+        a = np.ascontiguousarray(batch_u8, np.uint8)
+        n, h, w = a.shape
+        _, ns, pitch, nbytes = u8_strips_layout(w, h)
+        out = np.zeros(n * nbytes, np.uint8)
+        _check(lib().mods_u8_strips_fetch(self.h, C.c_void_p(a.ctypes.data), n, w, h, int(src_offset), C.c_void_p(out.ctypes.data)))
+        return out.reshape(n, ns, pitch // 16, 16)
 
     def set_match_mutual(self, mode):
         """mods_ctx_match_mutual: 0 off, 1 every FGINN tentative must be its train's nearest query, 2 and pass the ratio test backwards"""
@@ -1322,6 +1360,14 @@ class Pipeline:
     def set_match_mutual(self, mode):
         """before the first submit"""
         _check(lib().mods_pipeline_match_mutual(self.h, int(mode)))
+
+    def set_u8_kernels(self, mask):
+        """Context.set_u8_kernels on every GPU worker's context, before the first submit"""
+        _check(lib().mods_pipeline_u8_kernels(self.h, int(mask)))
+
+    def u8_strip_calls(self):
+        lib().mods_pipeline_u8_strip_calls.restype = C.c_long
+        return int(lib().mods_pipeline_u8_strip_calls(self.h))
 
     def set_domain_pooling(self, num_scales, start_coef=0.5, end_coef=1.5):
         """mods_pipeline_domain_pooling: Context.set_domain_pooling on every GPU worker's context, before the first submit"""

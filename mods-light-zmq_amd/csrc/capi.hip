@@ -1,6 +1,7 @@
 // extern "C" surface of libmodsgpu.so (include/mods_hip.h): context management, timing,
 // detector entry points and introspection for the parity tests.
 #include "common.hpp"
+#include "u8_strips.hpp"
 #include "detmath.hpp"
 #include "ransac_host.hpp"
 #include "f_laf.hpp"
@@ -459,7 +460,7 @@ static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, in
                    c->dsp_scales < 2;
   if (!can) { mods::dev_state_changed(c); return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc); }
   mods_ctx::DdKey key;
-  key.img = img_dev; key.img_u8 = c->img_u8_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
+  key.img = img_dev; key.img_u8 = c->img_u8_dev; key.img_strips = c->img_strip_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
   key.par_hash = fnv1a(desc, sizeof(*desc), fnv1a(det, sizeof(*det), 1469598103934665603ull)) ^ (unsigned long long)c->pyr_streams;
   key.epoch = c->dev_state_epoch;
   // A recording is made, and replayed, only right behind a call with the SAME arguments: tables that live on the device and are
@@ -520,8 +521,9 @@ int mods_ctx_graphs(mods_ctx *c, int on) {
 }
 long mods_ctx_graph_replays(const mods_ctx *c) { return c ? c->dd_replays : 0; }
 long mods_ctx_u8_source_calls(const mods_ctx *c) { return c ? c->u8_source_calls : 0; }
+long mods_ctx_u8_strip_calls(const mods_ctx *c) { return c ? c->u8_strip_calls : 0; }
 int mods_ctx_u8_kernels(mods_ctx *c, int mask) {
-  if (!c || mask > 15) { set_error("u8_kernels: bad argument"); return MODS_E_ARG; }
+  if (!c || mask > 255) { set_error("u8_kernels: bad argument"); return MODS_E_ARG; }
   c->u8_kernels = mask < 0 ? -1 : mask;
   mods::dev_state_changed(c);            // (a recorded detect + describe graph holds the other form's launches)
   return MODS_OK;
@@ -559,7 +561,7 @@ int mods_detect_describe_dev(mods_ctx *c, const float *img_dev, int n_img, int w
   if (n_img < 1 || n_img > c->batch) { set_error("detect_describe: %d images, context batch %d", n_img, c->batch); return MODS_E_ARG; }
   if (stride < w) { set_error("detect_describe: stride %d < width %d", stride, w); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  c->img_u8_dev = nullptr;
+  c->img_u8_dev = c->img_strip_dev = nullptr;
   return dd_call(c, img_dev, n_img, w, h, stride, det, desc, n_detected_host, n_regions_host);
 }
 
@@ -576,12 +578,51 @@ int mods_detect_describe_dev_u8(mods_ctx *c, const unsigned char *img_u8_dev, in
   if (stride < w) { set_error("detect_describe_u8: stride %d < width %d", stride, w); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
   int rc;
-  if ((rc = mods::u8_to_f32_launch(c, img_u8_dev, n_img, w, h, stride, c->input_dev))) return rc;
-  c->img_u8_dev = (stride == w && det->detectorType != MODS_DET_MSER) ? img_u8_dev : nullptr;
+  const bool twin = stride == w && det->detectorType != MODS_DET_MSER, strips = twin && mods::u8_strips_wanted(c, w, h, stride);
+  if ((rc = mods::u8_to_f32_launch(c, img_u8_dev, n_img, w, h, stride, c->input_dev, strips))) return rc;
+  c->img_u8_dev = twin ? img_u8_dev : nullptr;
+  c->img_strip_dev = strips ? c->u8_strip_dev.get() : nullptr;
   if (c->img_u8_dev) c->u8_source_calls++;
+  if (c->img_strip_dev) c->u8_strip_calls++;
   rc = dd_call(c, c->input_dev, n_img, w, h, w, det, desc, n_detected_host, n_regions_host);
-  c->img_u8_dev = nullptr;
+  c->img_u8_dev = c->img_strip_dev = nullptr;
   return rc;
+}
+
+// ---- the strip layout of the 8-bit twin, for the tests: the header's functions as they are (no device), and the twin of a batch as the
+// conversion launch makes it
+int mods_u8_strips_layout(int w, int h, unsigned *max_width, unsigned *n_strips, unsigned *pitch, size_t *image_bytes) {
+  if (max_width) *max_width = mods::kStripMaxW;
+  if (!mods::strip_layout_ok(w, h)) { set_error("u8_strips_layout: %d x %d is outside the layout", w, h); return MODS_E_ARG; }
+  if (n_strips) *n_strips = mods::strip_count(w);
+  if (pitch) *pitch = mods::strip_pitch(h);
+  if (image_bytes) *image_bytes = mods::strip_image_bytes(w, h);
+  return MODS_OK;
+}
+// strip_of(x) for x = 0 .. n - 1
+void mods_u8_strips_strip_of(unsigned n, unsigned *out) { for (unsigned x = 0; x < n; x++) out[x] = mods::strip_of(x); }
+// strip_offset of every pair start of a w x h image: out[(h - 1)][(w - 1)], x <= w - 2, y <= h - 2
+int mods_u8_strips_offsets(int w, int h, unsigned *out) {
+  if (!out || !mods::strip_layout_ok(w, h)) { set_error("u8_strips_offsets: bad argument"); return MODS_E_ARG; }
+  const unsigned pitch = mods::strip_pitch(h);
+  for (int y = 0; y <= h - 2; y++)
+    for (int x = 0; x <= w - 2; x++) out[(size_t)y * (w - 1) + x] = mods::strip_offset((unsigned)x, (unsigned)y, pitch);
+  return MODS_OK;
+}
+// the batch [n_img][h][w] is staged `src_offset` (0 .. 15) bytes into the context's staging area, converted, and the twin that the
+// conversion launch made is copied to out (n_img * strip_image_bytes)
+int mods_u8_strips_fetch(mods_ctx *c, const unsigned char *img_u8_host, int n_img, int w, int h, int src_offset, unsigned char *out) {
+  if (!c || !img_u8_host || !out) { set_error("u8_strips_fetch: null argument"); return MODS_E_ARG; }
+  if (n_img < 1 || n_img > c->batch || src_offset < 0 || src_offset > 15) { set_error("u8_strips_fetch: bad argument"); return MODS_E_ARG; }
+  if (w <= 0 || h <= 0 || (size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("u8_strips_fetch: image larger than the context"); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  int rc;
+  if ((rc = mods::u8_stage_ensure(c))) return rc;
+  const size_t n = (size_t)n_img * w * h;
+  MODS_HIP_CHECK(mods::copy_wait(c->stream, c->u8_stage_dev + src_offset, img_u8_host, n, hipMemcpyHostToDevice));
+  if ((rc = mods::u8_to_f32_launch(c, c->u8_stage_dev + src_offset, n_img, w, h, w, c->input_dev, true))) return rc;
+  MODS_HIP_CHECK(mods::copy_wait(c->stream, out, c->u8_strip_dev.get(), mods::strip_image_bytes(w, h) * n_img, hipMemcpyDeviceToHost));
+  return MODS_OK;
 }
 
 // Route the description of every following call through `fn` (NULL: back to the built-in RootSIFT).  The patches are
@@ -726,11 +767,14 @@ int mods_orient_describe_u8(mods_ctx *c, const unsigned char *img_u8, int w, int
   MODS_HIP_CHECK(hipMemcpyAsync(c->keys_dev, keys, sizeof(mods_affkey) * n_keys, hipMemcpyHostToDevice, c->stream));
   MODS_HIP_CHECK(hipMemcpyAsync(c->cand_count + 2 * c->batch, &n_keys, sizeof(int), hipMemcpyHostToDevice, c->stream));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));   // n_keys is a stack variable
-  if ((rc = mods::u8_to_f32_launch(c, c->u8_stage_dev, 1, w, h, w, c->input_dev))) return rc;
+  const bool strips = mods::u8_strips_wanted(c, w, h, w);
+  if ((rc = mods::u8_to_f32_launch(c, c->u8_stage_dev, 1, w, h, w, c->input_dev, strips))) return rc;
   c->img_u8_dev = c->u8_stage_dev;
+  c->img_strip_dev = strips ? c->u8_strip_dev.get() : nullptr;
   c->u8_source_calls++;
+  if (c->img_strip_dev) c->u8_strip_calls++;
   rc = describe_run(c, c->input_dev, 1, w, h, par);
-  c->img_u8_dev = nullptr;
+  c->img_u8_dev = c->img_strip_dev = nullptr;
   if (rc) return rc;
   if ((rc = mods_regions_fetch(c, 0, out, max_out, n_out))) return rc;
   return check_desc_err(c);

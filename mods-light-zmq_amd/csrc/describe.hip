@@ -194,7 +194,7 @@ __global__ __launch_bounds__(64, ORIENT_WAVES) void orient_kernel(const PX *__re
   float *s_hist = (float *)(s_bin + ori_key_bytes(ps) * nv);
   const int lane = threadIdx.x;
   const int b = blockIdx.y;
-  const PX *img = img_all + (size_t)k.w * k.h * b;
+  const PX *img = batch_image(img_all, k.w, k.h, b);
   const mods_affkey *keys = keys_all + (size_t)b * k.max_cand;
   OriOut *ori = ori_all + (size_t)b * k.max_cand;
   int n = key_count[b];
@@ -796,6 +796,10 @@ static void invert3_cv(const double *S, double *t) {
 // The same for a synthesised view: H (original -> view, 9 doubles) and the original image size; the
 // regions come out in the original frame (reproj_kp).  H == nullptr or HIsEye(H) (synth-detection.cpp:
 // 144-149): identity view.  det_copy_dev (optional): receives the described regions in the view frame.
+bool u8_strips_wanted(const mods_ctx *c, int w, int h, int stride) {
+  return (u8_kernel_mask(c) >> U8K_STRIPS_SHIFT) != 0 && stride == w && strip_layout_ok(w, h);
+}
+
 int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev) {
   int rc = dsp_check(ctx, par);
@@ -835,6 +839,7 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
   // sample from it; views and the external / network paths have fp32 only
   const bool hooks = external || ctx->shape_fn || ctx->shape_net || ctx->ori_fn || ctx->ori_net;
   const unsigned char *img_u8 = (!H && !hooks) ? ctx->img_u8_dev : nullptr;
+  const unsigned char *img_strips = img_u8 ? ctx->img_strip_dev : nullptr;
   if (external && par->fastExtraction) { set_error("FastPatchExtraction with an external descriptor is not supported"); return MODS_E_ARG; }
   if (external) { k.desc_mr = ctx->ext_mr; k.desc_ps = ctx->ext_ps; k.photo = 0; k.patch_rule = 1; }
   int *key_count = ctx->cand_count + 2 * ctx->batch;
@@ -853,7 +858,10 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
       const size_t need = sizeof(OriOut) * (size_t)k.ori_cap * ctx->max_cand * ctx->batch;
       MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->ori_multi_dev, need, need));
     }
-    if (img_u8 && kernel_from_u8(ctx, U8K_ORIENT))
+    if (img_strips && kernel_from_strips(ctx, U8K_ORIENT))
+      hipLaunchKernelGGL(orient_kernel<StripPx>, dim3(8192, n_img), dim3(64), lds, ctx->stream, (const StripPx *)img_strips, k, ctx->keys_dev,
+                         key_count, orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
+    else if (img_u8 && kernel_from_u8(ctx, U8K_ORIENT))
       hipLaunchKernelGGL(orient_kernel<unsigned char>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_u8, k, ctx->keys_dev, key_count,
                          orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
     else
@@ -876,13 +884,13 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
     for (int s = 0; s < K; s++) {
       DescConst ks = k;
       ks.desc_mr = par->desc_mrSize * (ctx->dsp_start + s * ((ctx->dsp_end - ctx->dsp_start) / (K - 1)));
-      if ((rc = launch_extract_and_sift(ctx, img_dev, n_img, ks, dmask, tab, false, img_u8))) return rc;
+      if ((rc = launch_extract_and_sift(ctx, img_dev, n_img, ks, dmask, tab, false, img_u8, img_strips))) return rc;
       if ((rc = launch_dsp_accumulate(ctx, n_img, ks, dmask, tab, s == 0))) return rc;
     }
     if ((rc = launch_dsp_finish(ctx, n_img, k, par->halfDesc != 0))) return rc;
     ctx->have_half = par->halfDesc != 0;
   } else {
-    rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8);
+    rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8, img_strips);
     if (rc) return rc;
     ctx->have_half = false;
     if (par->halfDesc && !external) {

@@ -2,7 +2,9 @@
 // several kernels share.  fp32, one rounding per operation (-ffp-contract=off).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "atan_lut_data.h"
+#include "u8_strips.hpp"
 
 namespace mods {
 
@@ -88,6 +90,24 @@ __device__ __forceinline__ void pix_pair(const unsigned char *__restrict__ p, fl
   const PixPairU8 q = *(const PixPairU8 *)p;
   a = (float)q.a; b = (float)q.b;
 }
+// Third pixel source: the 8-bit twin in 16-byte column strips (u8_strips.hpp).  A pointer to StripPx is the base of one image's
+// strips; the pixel (x, y) is the byte at strip_offset(x, y, strip_pitch(h)), its right neighbour the next byte and the pair of the
+// row below 16 bytes on - for every pair a tap path can ask for (x <= w - 2, y <= h - 2), so the loads are those of the row-major
+// 8-bit form and only the address differs: three integer instructions more per tap, about a third of the cache lines per gather.
+struct StripPx { unsigned char v; };
+__device__ __forceinline__ void pix_pair(const StripPx *__restrict__ p, float &a, float &b) { pix_pair((const unsigned char *)p, a, b); }
+template <class PX> constexpr bool kStripSource = std::is_same<PX, StripPx>::value;
+// image b of a batch of w x h images
+template <class PX> __device__ __forceinline__ const PX *batch_image(const PX *__restrict__ all, int w, int h, int b) {
+  if constexpr (kStripSource<PX>) return all + strip_image_bytes(w, h) * b;
+  else return all + (size_t)w * h * b;
+}
+// element index of pixel (x, y) of an image, and the distance to the same column of the next row
+template <class PX> __device__ __forceinline__ unsigned pix_index(int w, int h, int x, int y) {
+  if constexpr (kStripSource<PX>) return strip_offset((unsigned)x, (unsigned)y, strip_pitch(h));
+  else return (unsigned)(__mul24(y, w) + x);
+}
+template <class PX> __device__ __forceinline__ int pix_row_step(int w) { return kStripSource<PX> ? kStripRowBytes : w; }
 
 // The four pixels of one bilinear tap, loaded without combining them (lets a caller issue the loads
 // of several taps before the first use).  valid = false: the tap is 0 (checked branch, outside).
@@ -101,8 +121,8 @@ __device__ __forceinline__ TapLoads tap_load(const PX *__restrict__ im, int w, i
   t.wx = WX - (float)x;
   t.wy = WY - (float)y;
   if (t.valid) {
-    const PX *Row0 = im + (size_t)y * w + x;
-    pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + w, t.r10, t.r11);
+    const PX *Row0 = kStripSource<PX> ? im + pix_index<PX>(w, h, x, y) : im + (size_t)y * w + x;
+    pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + pix_row_step<PX>(w), t.r10, t.r11);
   } else { t.r00 = t.r01 = t.r10 = t.r11 = 0.f; }
   return t;
 }
@@ -119,8 +139,8 @@ __device__ __forceinline__ TapLoads tap_load_bf(const PX *__restrict__ im, int w
   t.wx = WX - (float)x;
   t.wy = WY - (float)y;
   const int xc = min(max(x, 0), w - 2), yc = min(max(y, 0), h - 2);
-  const PX *Row0 = im + (unsigned)(__mul24(yc, w) + xc);
-  pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + w, t.r10, t.r11);
+  const PX *Row0 = im + pix_index<PX>(w, h, xc, yc);
+  pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + pix_row_step<PX>(w), t.r10, t.r11);
   return t;
 }
 __device__ __forceinline__ float tap_combine(const TapLoads &t) {
@@ -133,21 +153,27 @@ __device__ __forceinline__ float tap_combine(const TapLoads &t) {
 // no border test, no clamp).  That covers the window's own samples only: a lane of a partly filled tile whose sample lies beyond
 // the window's edge (`inwin` false; its value is never stored) reads pixel 0 instead.  A third of the VALU work of the checked form
 // (tap_load_bf: two floors, four clamps, four compares - all half-rate instructions on gfx950 - go away).
+// (h: the strip source's pitch follows from it; a row-major image does not need it)
 template <class PX>
-__device__ __forceinline__ TapLoads tap_load_inside(const PX *__restrict__ im, int w, float WX, float WY, bool inwin) {
+__device__ __forceinline__ TapLoads tap_load_inside(const PX *__restrict__ im, int w, int h, float WX, float WY, bool inwin) {
   TapLoads t;
   const int x = (int)WX, y = (int)WY;
   t.valid = true;
   t.wx = WX - (float)x;
   t.wy = WY - (float)y;
-  const PX *Row0 = im + (inwin ? (unsigned)(__mul24(y, w) + x) : 0u);
-  pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + w, t.r10, t.r11);
+  const PX *Row0 = im + (inwin ? pix_index<PX>(w, h, x, y) : 0u);
+  pix_pair(Row0, t.r00, t.r01); pix_pair(Row0 + pix_row_step<PX>(w), t.r10, t.r11);
   return t;
+}
+template <class PX>
+__device__ __forceinline__ TapLoads tap_load_inside(const PX *__restrict__ im, int w, float WX, float WY, bool inwin) {
+  static_assert(!kStripSource<PX>, "the strip source needs the image height");
+  return tap_load_inside(im, w, 0, WX, WY, inwin);
 }
 template <bool TOUCH, class PX>
 __device__ __forceinline__ TapLoads tap_load_t(const PX *__restrict__ im, int w, int h, float WX, float WY, bool inwin) {
   if (TOUCH) return tap_load_bf(im, w, h, WX, WY, true);
-  return tap_load_inside(im, w, WX, WY, inwin);
+  return tap_load_inside(im, w, h, WX, WY, inwin);
 }
 template <bool TOUCH> __device__ __forceinline__ float tap_combine_t(const TapLoads &t) {
   const float I1 = t.wx * (t.r01 - t.r00) + t.r00;
@@ -164,7 +190,7 @@ template <bool TOUCH> __device__ __forceinline__ float tap_combine_t(const TapLo
 // store(row, col, value) is called for every sample of the window.
 // The rows [row_begin, row_end) of the window are sampled (all columns).  TOUCH = whether the window touches the image border
 // (interpolateCheckBorders): the same for every lane, so the two forms of the tap are two instantiations behind one scalar branch.
-// PX = float or unsigned char: the pixel type of the image (pix_pair).
+// PX = float, unsigned char or StripPx: the pixel source (pix_pair, pix_index).
 template <bool WIDE, bool TOUCH, class PX, class Store>
 __device__ __forceinline__ void sample_tiles_rows_t(const PX *__restrict__ img, int w, int h, float fx, float fy, float a11, float a12,
                                                     float a21, float a22, int n, int row_begin, int row_end, int wv, int nw, Store store) {

@@ -2,6 +2,7 @@
 // mods_hmatrix_filter, mods_ctx_warmup) and the two halves the pair pipeline overlaps across pairs (pipeline.hip): the GPU half -
 // detect, describe, match, DuplicateFiltering on the device - and the host-driven half - verification of the tentative list.
 #include "common.hpp"
+#include "u8_strips.hpp"
 #include "../../include/mods_degensac.h"
 #include <algorithm>
 #include <cmath>
@@ -27,15 +28,45 @@ static DupJob single_pair_dup_job(mods_ctx *c) {
 
 constexpr size_t kPinArena = (size_t)24 << 20;   // pinned staging of a batch's tentative lists
 
+// The strip twin (u8_strips.hpp) of n_img packed w x h images: a lane makes one 16-byte row of a strip - the pixels 15 s ... 15 s + 15
+// of image row y by one 16-byte load at any alignment, or byte by byte where the row ends inside them - and writes zeros where the
+// layout pads (rows h ... h8 - 1, columns w ... of the last strip), so every byte of the twin is written.  A wave takes 8 rows of 8
+// neighbouring strips: it reads 8 runs of 121 bytes and writes 8 whole 128-byte lines.
+struct __attribute__((packed, aligned(1))) StripRowBytes { unsigned v[4]; };
+__device__ __forceinline__ void u8_strip_rows(const unsigned char *__restrict__ src, unsigned char *__restrict__ strips, int n_img, int w, int h) {
+  const unsigned ns = mods::strip_count(w), bands = ((unsigned)h + 7u) >> 3, pitch = mods::strip_pitch(h), groups = (ns + 7u) >> 3;
+  const size_t items = (size_t)n_img * groups * bands;
+  const unsigned lane = threadIdx.x & 63, yl = lane & 7, sl = lane >> 3;
+  for (size_t it = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += (size_t)gridDim.x * 4) {
+    const unsigned band = (unsigned)(it % bands), g = (unsigned)((it / bands) % groups), b = (unsigned)(it / ((size_t)bands * groups));
+    const unsigned s = 8 * g + sl, y = 8 * band + yl, x0 = mods::kStripCols * s;
+    if (s >= ns) continue;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (y < (unsigned)h) {
+      const unsigned char *p = src + ((size_t)b * h + y) * w + x0;
+      if (x0 + 16 <= (unsigned)w) { const StripRowBytes r = *(const StripRowBytes *)p; v = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]); }
+      else {
+        unsigned q[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 16; j++)
+          if (x0 + j < (unsigned)w) q[j >> 2] |= (unsigned)p[j] << (8 * (j & 3));
+        v = make_uint4(q[0], q[1], q[2], q[3]);
+      }
+    }
+    *(uint4 *)(strips + (size_t)b * ns * pitch + (size_t)s * pitch + mods::kStripRowBytes * y) = v;
+  }
+}
 // 8-bit grey -> float (the ImageRepresentation constructor's convertTo(CV_32F), imagerepresentation.cpp:293-302): exact
-// n4 groups of four pixels (src 4-byte, dst 16-byte aligned), then the pixels 4 n4 .. n - 1 one by one
+// n4 groups of four pixels (src 4-byte, dst 16-byte aligned), then the pixels 4 n4 .. n - 1 one by one.  strips != nullptr: the
+// n = n_img * w * h pixels are packed images, and the launch lays them out in strips as well while it has them in the caches
 extern "C" __global__ __launch_bounds__(256) void u8_to_f32_kernel(const unsigned char *__restrict__ src, float *__restrict__ dst, size_t n4,
-                                                                   size_t n) {
+                                                                   size_t n, unsigned char *__restrict__ strips, int n_img, int w, int h) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
     const uchar4 v = ((const uchar4 *)src)[i];
     ((float4 *)dst)[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
   }
   for (size_t i = 4 * n4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = (float)src[i];
+  if (strips) u8_strip_rows(src, strips, n_img, w, h);
 }
 // the same for rows of w pixels `stride` bytes apart, packed on the way
 extern "C" __global__ __launch_bounds__(256) void u8_rows_to_f32_kernel(const unsigned char *__restrict__ src, size_t stride, size_t w, size_t rows,
@@ -45,16 +76,27 @@ extern "C" __global__ __launch_bounds__(256) void u8_rows_to_f32_kernel(const un
 // the context's staging area for 8-bit host images, allocated at its first use
 int mods::u8_stage_ensure(mods_ctx *c) {
   MODS_HIP_CHECK(c->u8_stage_dev.reserve((size_t)c->max_w * c->max_h * c->batch + 16));
+  if (mods::u8_strips_wanted(c, c->max_w, c->max_h, c->max_w))     // (a mask that is given later reserves at its first call)
+    MODS_HIP_CHECK(c->u8_strip_dev.reserve(mods::strip_image_bytes(c->max_w, c->max_h) * c->batch));
   return MODS_OK;
 }
 // images [n_img][h][stride] of 8-bit grey in HBM -> fp32 [n_img][h][w]; any size, any alignment of src
-int mods::u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst) {
+int mods::u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst, bool strips) {
   const size_t n = (size_t)n_img * w * h;
+  if (strips) {
+    if (stride != w || !mods::strip_layout_ok(w, h)) { set_error("u8_to_f32: no strip twin for %d x %d images, stride %d", w, h, stride); return MODS_E_ARG; }
+    // (reserved with the staging area for the context's largest images: only a call ahead of that, or an image of the context's
+    // area with more columns or rows than max_w x max_h, allocates here)
+    bool moved = false;
+    MODS_HIP_CHECK(c->u8_strip_dev.reserve(mods::strip_image_bytes(w, h) * n_img, std::max(mods::strip_image_bytes(w, h) * n_img, mods::strip_image_bytes(c->max_w, c->max_h) * c->batch), &moved));
+    if (moved) mods::dev_pool_reallocated(c);
+  }
   if (stride != w)
     hipLaunchKernelGGL(u8_rows_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, (size_t)stride, (size_t)w, (size_t)n_img * h, dst);
   else {
     const bool vec = (((uintptr_t)src & 3) | ((uintptr_t)dst & 15)) == 0;
-    hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, dst, vec ? n / 4 : (size_t)0, n);
+    hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, dst, vec ? n / 4 : (size_t)0, n,
+                       strips ? c->u8_strip_dev.get() : (unsigned char *)nullptr, n_img, w, h);
   }
   MODS_HIP_CHECK(hipGetLastError());
   return MODS_OK;
@@ -136,7 +178,7 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
       // pairs/s, the kernel's waves sit on PCIe reads; the copy engine path stays)
       MODS_HIP_CHECK(hipMemcpyAsync(st, img[i], plane2, hipMemcpyHostToDevice, c->stream));
       const unsigned char *src = st;
-      if (!clahe && !all_u8) hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, c->input_dev + plane2 * i, plane2 / 4, plane2);
+      if (!clahe && !all_u8) hipLaunchKernelGGL(u8_to_f32_kernel, dim3(1024), dim3(256), 0, c->stream, src, c->input_dev + plane2 * i, plane2 / 4, plane2, (unsigned char *)nullptr, 0, 0, 0);
     } else {
       MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev + plane2 * i, img[i], sizeof(float) * plane2,
                                     kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));

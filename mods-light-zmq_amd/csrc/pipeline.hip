@@ -209,6 +209,26 @@ int mods_pipeline_match_mutual(mods_pipeline *p, int mode) {
   return MODS_OK;
 }
 
+// which kernels of every description sample from which form of a batch's 8-bit images (mods_ctx_u8_kernels on the workers' contexts;
+// a mask with strip bits reserves the strip copy here, ahead of the first batch)
+int mods_pipeline_u8_kernels(mods_pipeline *p, int mask) {
+  if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: u8_kernels after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) {
+    int rc = mods_ctx_u8_kernels(c, mask);
+    if (rc) return rc;
+    MODS_HIP_CHECK(hipSetDevice(c->device));
+    if ((rc = mods::u8_stage_ensure(c))) return rc;
+  }
+  return MODS_OK;
+}
+long mods_pipeline_u8_strip_calls(mods_pipeline *p) {
+  long n = 0;
+  if (p) for (auto *c : p->ctxs) n += mods_ctx_u8_strip_calls(c);
+  return n;
+}
+
 // domain-size pooling of every description of the pipeline (mods_ctx_domain_pooling on the workers' contexts)
 int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCoef, double endCoef) {
   if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256, ES_MINB) void extract_small_kernel(const PX *_
 #endif
   for (int it = blockIdx.x; it < n; it += gridDim.x) {
     const int code = items[it], b = code >> 17, ri = code & 0x1ffff;
-    const PX *img = img_all + (size_t)k.w * k.h * b;
+    const PX *img = batch_image(img_all, k.w, k.h, b);
     const RegionGeom g = region_geom(reg_all[(size_t)b * k.max_reg + ri], k.desc_mr, ps, k.patch_rule);
     float *out = patches + ((size_t)b * k.reg_cap + ri) * pp;
     __syncthreads();
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(256) void big_sample_kernel(const PX *__restrict__ 
     const int2 item = sitems[it];
     const BigRegion br = regions[item.x];
     const RegionGeom g = region_geom(reg_all[(size_t)br.img * k.max_reg + br.ri], k.desc_mr, k.desc_ps, k.patch_rule);
-    const PX *img = img_all + (size_t)k.w * k.h * br.img;
+    const PX *img = batch_image(img_all, k.w, k.h, br.img);
     const int P2 = br.P2, P2r = br.P2r, half = P2 / 2, w = k.w, h = k.h;
     const int row = item.y + 4 * (lane >> 4) + (lane & 3), s = (lane >> 2) & 3;
     if (row >= P2) continue;
@@ -631,9 +631,9 @@ __global__ __launch_bounds__(256) void big_sample_kernel(const PX *__restrict__ 
           wx[u] = WX - (float)x;
           wy[u] = WY - (float)y;
           if (ok[u]) {
-            const PX *Row0 = img + (size_t)y * w + x;
+            const PX *Row0 = kStripSource<PX> ? img + pix_index<PX>(w, h, x, y) : img + (size_t)y * w + x;
             pix_pair(Row0, a0[u], b0[u]);
-            pix_pair(Row0 + w, a1[u], b1[u]);
+            pix_pair(Row0 + pix_row_step<PX>(w), a1[u], b1[u]);
           }
           WX += g.f11; WY += g.f21; WX += g.f11; WY += g.f21; WX += g.f11; WY += g.f21; WX += g.f11; WY += g.f21;
         }
@@ -780,7 +780,7 @@ __global__ __launch_bounds__(256) void big_fused_kernel(const PX *__restrict__ i
     const int2 item = fitems[it];
     const BigRegion br = regions[item.x];
     const RegionGeom g = region_geom(reg_all[(size_t)br.img * k.max_reg + br.ri], k.desc_mr, ps, k.patch_rule);
-    const PX *img = img_all + (size_t)k.w * k.h * br.img;
+    const PX *img = batch_image(img_all, k.w, k.h, br.img);
     const int P2 = br.P2, w = k.w, h = k.h;
     const int R = big_fuse_rows(P2), r0 = item.y;
     __syncthreads();   // the previous item's row pass is done with the tile
@@ -1648,7 +1648,7 @@ static int sift_col_span(int ps) {
 
 // ---------------------------------------------------------------------------------------
 int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool run_sift,
-                            const unsigned char *img_u8) {
+                            const unsigned char *img_u8, const unsigned char *img_strips) {
   StageScope ts(ctx, MODS_STAGE_DESCRIBE);
   const int ps = k.desc_ps, ps2 = 2 * ps, pp = ps * ps;
   // HBM layout of the description scratch: patch store [n_img][reg_cap][ps*ps] | big-tier bookkeeping | slab pool
@@ -1691,7 +1691,11 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
       kt.p2_lo = tiers[t]; kt.p2_hi = tiers[t + 1];
       const size_t capS = kt.p2_hi > 4 ? kt.p2_hi : 4;
       const size_t ldsS = sizeof(float) * (capS * odd4((int)capS) + capS * ((capS + 3) & ~(size_t)3) + 2 * ps2 + 32) + 32;
-      if (img_u8 && kernel_from_u8(ctx, U8K_EXTRACT_SMALL))
+      if (img_strips && kernel_from_strips(ctx, U8K_EXTRACT_SMALL))
+        hipLaunchKernelGGL(extract_small_kernel<StripPx>, dim3(4096), dim3(256), ldsS, ctx->stream, (const StripPx *)img_strips, kt, ctx->regions_dev,
+                           small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
+                           (const float *)ctx->blur_table_dev);
+      else if (img_u8 && kernel_from_u8(ctx, U8K_EXTRACT_SMALL))
         hipLaunchKernelGGL(extract_small_kernel<unsigned char>, dim3(4096), dim3(256), ldsS, ctx->stream, img_u8, kt, ctx->regions_dev,
                            small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
                            (const float *)ctx->blur_table_dev);
@@ -1703,13 +1707,19 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
   }
   const size_t ldsH = sizeof(float) * (k.tap_cap + 4 * ps2) + 32;
   hipLaunchKernelGGL(big_setup_kernel, dim3(1024), dim3(256), ldsH, ctx->stream, k, bl, bregs, max_big, pool, ctx->desc_err_dev);
-  if (img_u8 && kernel_from_u8(ctx, U8K_BIG_FUSED))
+  if (img_strips && kernel_from_strips(ctx, U8K_BIG_FUSED))
+    hipLaunchKernelGGL(big_fused_kernel<StripPx>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, (const StripPx *)img_strips, k, bl, bregs,
+                       fitems, max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
+  else if (img_u8 && kernel_from_u8(ctx, U8K_BIG_FUSED))
     hipLaunchKernelGGL(big_fused_kernel<unsigned char>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_u8, k, bl, bregs, fitems,
                        max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
   else
     hipLaunchKernelGGL(big_fused_kernel<float>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_dev, k, bl, bregs, fitems,
                        max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
-  if (img_u8 && kernel_from_u8(ctx, U8K_BIG_SAMPLE))
+  if (img_strips && kernel_from_strips(ctx, U8K_BIG_SAMPLE))
+    hipLaunchKernelGGL(big_sample_kernel<StripPx>, dim3(4096), dim3(256), 0, ctx->stream, (const StripPx *)img_strips, k, bl, bregs, sitems,
+                       max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
+  else if (img_u8 && kernel_from_u8(ctx, U8K_BIG_SAMPLE))
     hipLaunchKernelGGL(big_sample_kernel<unsigned char>, dim3(4096), dim3(256), 0, ctx->stream, img_u8, k, bl, bregs, sitems, max_items,
                        ctx->regions_dev, pool, ctx->desc_err_dev);
   else
