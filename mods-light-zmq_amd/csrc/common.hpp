@@ -401,6 +401,7 @@ int clahe_launch(mods_ctx *ctx, const unsigned char *src, int n_img, int w, int 
 
 // detect.hip
 int detect_run(mods_ctx *ctx);       // NMS -> localise -> dedup -> Baumberg -> sort, for the configured batch
+size_t nms_octave_mask_words(int w, int h, int border, int n_scales);   // ballot words of one image's NMS over one octave
 
 // mser.hip
 int detect_any(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *par, double tilt,

@@ -1094,6 +1094,16 @@ __global__ __launch_bounds__(256) void select_keys_kernel(int max_cand, const mo
 }
 
 // ---------------------------------------------------------------------------------------
+// Ballot words one image's NMS writes for an octave (detect_run_stages lays the octaves out with the same arithmetic; 0: the
+// border leaves the octave no interior)
+size_t nms_octave_mask_words(int w, int h, int border, int n_scales) {
+  const int iw = w - 2 * border, ih = h - 2 * border;
+  if (iw <= 0 || ih <= 0) return 0;
+  const bool wide = (w & 3) == 0 && w >= 8;
+  const int nblk = wide ? (w + NMS4_COLS - 1) / NMS4_COLS : (iw + NMS_COLS - 1) / NMS_COLS;
+  return (size_t)n_scales * ih * (wide ? 4 * nblk : nblk);
+}
+
 static int detect_run_stages(mods_ctx *ctx);
 int detect_run(mods_ctx *ctx) {
   const int rc = detect_run_stages(ctx);
@@ -1168,7 +1178,7 @@ static int detect_run_stages(mods_ctx *ctx) {
       pl.mask_off[pl.n] = mask_words;
       pl.blk_begin[pl.n + 1] = pl.blk_begin[pl.n] + nblk * nby;
       pl.n++;
-      const int total = par.numberOfScales * ih * words;
+      const int total = (int)nms_octave_mask_words(o.w, o.h, par.border, par.numberOfScales);   // numberOfScales * ih * words
       comp_pl.oi[comp_pl.n] = oi; comp_pl.nbx[comp_pl.n] = nblk; comp_pl.w[comp_pl.n] = o.w; comp_pl.h[comp_pl.n] = o.h;
       comp_pl.words[comp_pl.n] = words; comp_pl.wide[comp_pl.n] = wide ? 1 : 0; comp_pl.mask_off[comp_pl.n] = mask_words;
       comp_pl.blk_begin[comp_pl.n + 1] = comp_pl.blk_begin[comp_pl.n] + (total + 256 * NMS_CW - 1) / (256 * NMS_CW);

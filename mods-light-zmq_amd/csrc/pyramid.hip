@@ -1033,7 +1033,7 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
   const int minSize = 2 * par->border + 2;
   int cw = w, ch = h;
   float pd = 1.0f;
-  size_t plane_elems = 0, omap_elems = 0;
+  size_t plane_elems = 0, omap_elems = 0, mask_words = 0;
   const float sigmaStep = det_pow2f(1.0f / (float)par->numberOfScales);
   while (ch > minSize && cw > minSize) {
     if (P.n_oct >= kMaxOctaves) break;
@@ -1043,6 +1043,7 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
     for (int l = 0; l < n_levels; l++) { o.sigma[l] = cur; cur *= sigmaStep; }
     plane_elems += (size_t)cw * ch * n_img * 2 * n_levels;
     omap_elems += (size_t)cw * ch * n_img;
+    mask_words += nms_octave_mask_words(cw, ch, par->border, par->numberOfScales) * n_img;
     int nw, nh;
     resize_half_dims(cw, ch, &nw, &nh);
     cw = nw; ch = nh;
@@ -1051,6 +1052,9 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
   MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->plane_pool, plane_elems, plane_elems));
   if (omap_elems > ctx->omap_pool.capacity()) ctx->omap_dirty = true;
   MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->omap_pool, omap_elems, omap_elems));
+  // the NMS ballot words: the context's allocation covers the default schedule of an image of its size; more scales, or a
+  // narrow plane whose last 248-column block is nearly empty, need more (every word is written before it is read)
+  MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->nms_mask, mask_words, mask_words));
   float *pp = ctx->plane_pool;
   unsigned int *mp = ctx->omap_pool;
   for (int oi = 0; oi < P.n_oct; oi++) {

@@ -16,10 +16,31 @@ def _assert_keys_equal(got, want):
         assert np.array_equal(got[f], want[f]), "field %s differs" % f
 
 
-@pytest.mark.parametrize("w,h", [(64, 48), (135, 67), (257, 130), (33, 200), (640, 480)])
-@pytest.mark.parametrize("sigma", [0.8, 1.2263, 1.5199, 2.4525, 4.9])
-def test_gauss_blur_bitexact(gpu_ctx, w, h, sigma):
-    img = synth.texture(w, h, seed=w * 7 + h)
+# The sigmas of the default schedule and its neighbours, then one sigma per odd kernel size 3 .. 33 (radius 1 .. 8: the register-
+# blocked kernel, 9 .. 16: the generic one) and one of 35 taps, which no kernel has.
+BLUR_KSIZE_OF_SIGMA = {0.8: 5, 1.2263: 9, 1.5199: 11, 2.4525: 15, 4.9: 31,
+                       0.4167: 3, 0.75: 5, 1.0833: 7, 1.4167: 9, 1.75: 11, 2.0833: 13, 2.4167: 15, 2.75: 17, 3.0833: 19, 3.4167: 21,
+                       3.75: 23, 4.0833: 25, 4.4167: 27, 4.75: 29, 5.0833: 31, 5.4167: 33, 5.75: 35}
+BLUR_SIGMAS = list(BLUR_KSIZE_OF_SIGMA)
+# (3, 9): narrower than a float4, the generic kernel at every radius; (4, 4), (5, 3), (7, 1): narrower than the radius, every tap
+# clamped by the replicate border; (129, 17), (253, 33): one tile seam in x, 16-row seams in y, a ragged right edge;
+# (133, 12230): 2 x 192 = 384 tiles of 128 x 64, the fewest that select the large-tile instantiation (kernel sizes 3 .. 17 only)
+BLUR_CASES = [(s, w, h) for s in BLUR_SIGMAS[:5] for (w, h) in ((64, 48), (135, 67), (257, 130), (33, 200), (640, 480))]
+BLUR_CASES += [(s, w, h) for s in BLUR_SIGMAS[5:] for (w, h) in ((3, 9), (4, 4), (5, 3), (7, 1), (129, 17), (253, 33))]
+BLUR_CASES += [(s, 133, 12230) for s in BLUR_SIGMAS[5:] if BLUR_KSIZE_OF_SIGMA[s] <= 17]
+_blur_images = {}     # one image per shape, shared by its sigmas
+
+
+@pytest.mark.parametrize("sigma,w,h", BLUR_CASES)
+def test_gauss_blur_bitexact(gpu_ctx, pkg, w, h, sigma):
+    if (w, h) not in _blur_images:
+        _blur_images[(w, h)] = synth.texture(max(w, 8), max(h, 8), seed=w * 7 + h)[:h, :w].copy()
+    img = _blur_images[(w, h)]
+    assert orc.gauss_ksize(sigma) == BLUR_KSIZE_OF_SIGMA[sigma]
+    if BLUR_KSIZE_OF_SIGMA[sigma] > 33:
+        with pytest.raises(pkg.ModsError, match="gaussian kernel too wide.*ksize=35"):
+            gpu_ctx.gauss_blur(img, sigma)
+        return
     assert np.array_equal(gpu_ctx.gauss_blur(img, sigma), orc.gauss_blur(img, sigma))
 
 
