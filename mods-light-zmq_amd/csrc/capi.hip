@@ -418,12 +418,12 @@ static int check_desc_err(mods_ctx *c) {
 
 // The launches of one detect + describe call: scale space, NMS, localisation, Baumberg, order, orientation, extraction, SIFT and the
 // read-back of the batch's counters (pinned host words) - ~70 dispatches for a 1080p batch, no host round trip between them.
-static int dd_enqueue(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
+static int dd_enqueue(mods_ctx *c, const PixelSources &img, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
                       const mods_describe_params *desc) {
   int rc;
-  if ((rc = detect_any(c, img_dev, n_img, w, h, stride, det, 1.0, 1.0))) return rc;
-  const float *planes = img_dev;
-  if (stride != w) planes = c->tmp_dev;   // pyramid_build repacked the batch there
+  if ((rc = detect_any(c, img.f32, n_img, w, h, stride, det, 1.0, 1.0))) return rc;
+  PixelSources planes = img;
+  if (stride != w) planes.f32 = c->tmp_dev;   // pyramid_build repacked the batch there (such a call has no 8-bit source)
   if ((rc = describe_run(c, planes, n_img, w, h, desc))) return rc;
   // every count and the error flag of the batch in one round trip (pinned host words)
   int *hc = c->host_counts;
@@ -453,14 +453,14 @@ static unsigned long long fnv1a(const void *p, size_t n, unsigned long long h) {
 // DEBUG_CLR_GRAPH_PACKET_CAPTURE=0, the switch for the runtime's replay of pre-built AQL packets, which linear kernel chains
 // take; profiles/r05_graph_replay_matrix*.log).  That switch is read when the runtime starts, out of a library's reach, so calls
 // whose scale space does not fork (small images, small batches, mods_ctx_pyramid_streams(1)) stay eager.
-static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
+static int dd_run(mods_ctx *c, const PixelSources &img, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
                   const mods_describe_params *desc) {
   // (domain-size pooling: the chain runs eagerly - K extractions are K times the launches, and no recording of it has been tried)
   const bool can = c->dd_graphs && c->timing_mask == 0 && !mods::has_hooks(c) && !mods::has_nets(c) && det->detectorType != MODS_DET_MSER &&
                    c->dsp_scales < 2;
-  if (!can) { mods::dev_state_changed(c); return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc); }
+  if (!can) { mods::dev_state_changed(c); return dd_enqueue(c, img, n_img, w, h, stride, det, desc); }
   mods_ctx::DdKey key;
-  key.img = img_dev; key.img_u8 = c->img_u8_dev; key.img_strips = c->img_strip_dev; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
+  key.img = img; key.n_img = n_img; key.w = w; key.h = h; key.stride = stride;
   key.par_hash = fnv1a(desc, sizeof(*desc), fnv1a(det, sizeof(*det), 1469598103934665603ull)) ^ (unsigned long long)c->pyr_streams;
   key.epoch = c->dev_state_epoch;
   // A recording is made, and replayed, only right behind a call with the SAME arguments: tables that live on the device and are
@@ -470,7 +470,7 @@ static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, in
   if (c->dd_stale) { dd_graph_drop(c); c->dd_linear.clear(); c->dd_stale = false; }
   const bool repeat = key == c->dd_prev;
   c->dd_prev = key;
-  if (!repeat) return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc);
+  if (!repeat) return dd_enqueue(c, img, n_img, w, h, stride, det, desc);
   for (auto &e : c->dd_cache)
     if (e.first == key) {
       MODS_HIP_CHECK(hipGraphLaunch(e.second, c->stream));
@@ -478,14 +478,14 @@ static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, in
       return MODS_OK;
     }
   for (const auto &k2 : c->dd_linear)
-    if (k2 == key) return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc);
+    if (k2 == key) return dd_enqueue(c, img, n_img, w, h, stride, det, desc);
   hipStream_t s = c->stream;
   if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     (void)hipGetLastError();
     c->dd_graphs = false;
-    return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc);
+    return dd_enqueue(c, img, n_img, w, h, stride, det, desc);
   }
-  const int rc = dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc);
+  const int rc = dd_enqueue(c, img, n_img, w, h, stride, det, desc);
   hipGraph_t g = nullptr;
   const hipError_t e_end = hipStreamEndCapture(s, &g);
   hipGraphExec_t ex = nullptr;
@@ -493,7 +493,7 @@ static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, in
     (void)hipGraphDestroy(g);
     if (c->dd_linear.size() >= 16) c->dd_linear.erase(c->dd_linear.begin());
     c->dd_linear.push_back(key);
-    return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc);
+    return dd_enqueue(c, img, n_img, w, h, stride, det, desc);
   }
   if (rc == MODS_OK && e_end == hipSuccess && g && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess) {
     (void)hipGraphDestroy(g);
@@ -509,7 +509,7 @@ static int dd_run(mods_ctx *c, const float *img_dev, int n_img, int w, int h, in
   c->pyr_side = false;                    // (a fork recorded into the dead capture)
   c->dd_graphs = false;
   c->omap_dirty = true;
-  return dd_enqueue(c, img_dev, n_img, w, h, stride, det, desc);
+  return dd_enqueue(c, img, n_img, w, h, stride, det, desc);
 }
 
 int mods_ctx_graphs(mods_ctx *c, int on) {
@@ -529,12 +529,12 @@ int mods_ctx_u8_kernels(mods_ctx *c, int mask) {
   return MODS_OK;
 }
 
-// the call behind both detect + describe entry points; c->img_u8_dev: the 8-bit twin of img_dev for this call, or nullptr
-static int dd_call(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
+// the call behind both detect + describe entry points
+static int dd_call(mods_ctx *c, const PixelSources &img, int n_img, int w, int h, int stride, const mods_hessaff_params *det,
                    const mods_describe_params *desc, int *n_detected_host, int *n_regions_host) {
   int rc;
   if ((rc = mods::dsp_check(c, desc))) return rc;      // (before the detector's launches)
-  if ((rc = dd_run(c, img_dev, n_img, w, h, stride, det, desc))) return rc;
+  if ((rc = dd_run(c, img, n_img, w, h, stride, det, desc))) return rc;
   int *hc = c->host_counts;
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   for (int b = 0; b < n_img; b++) {
@@ -561,32 +561,25 @@ int mods_detect_describe_dev(mods_ctx *c, const float *img_dev, int n_img, int w
   if (n_img < 1 || n_img > c->batch) { set_error("detect_describe: %d images, context batch %d", n_img, c->batch); return MODS_E_ARG; }
   if (stride < w) { set_error("detect_describe: stride %d < width %d", stride, w); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  c->img_u8_dev = c->img_strip_dev = nullptr;
-  return dd_call(c, img_dev, n_img, w, h, stride, det, desc, n_detected_host, n_regions_host);
+  return dd_call(c, {img_dev}, n_img, w, h, stride, det, desc, n_detected_host, n_regions_host);
 }
 
 // 8-bit grey in HBM: converted (exactly) into input_dev, from which the scale space is built and the keypoints are detected as in
-// mods_detect_describe_dev; orientation and description sample from the 8-bit images themselves in the kernels whose switch is on
-// (describe_common.hpp) - (float)u8 at the load gives the fp32 copy's values, so the regions are the same to the bit.
+// mods_detect_describe_dev; orientation and description sample from the 8-bit images themselves in the kernels whose mask bit is on
+// (pixel_sources.hpp) - (float)u8 at the load gives the fp32 copy's values, so the regions are the same to the bit.
 // Rows that are not packed (stride != w) and the MSER detector take the fp32 copy throughout.
-int mods_detect_describe_dev_u8(mods_ctx *c, const unsigned char *img_u8_dev, int n_img, int w, int h, int stride,
+int mods_detect_describe_dev_u8(mods_ctx *c, const unsigned char *img_u8, int n_img, int w, int h, int stride,
                                 const mods_hessaff_params *det, const mods_describe_params *desc, int *n_detected_host,
                                 int *n_regions_host) {
-  if (!c || !img_u8_dev || !det || !desc) { set_error("detect_describe_u8: null argument"); return MODS_E_ARG; }
+  if (!c || !img_u8 || !det || !desc) { set_error("detect_describe_u8: null argument"); return MODS_E_ARG; }
   if (w <= 0 || h <= 0 || (size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("detect_describe_u8: image larger than the context"); return MODS_E_ARG; }
   if (n_img < 1 || n_img > c->batch) { set_error("detect_describe_u8: %d images, context batch %d", n_img, c->batch); return MODS_E_ARG; }
   if (stride < w) { set_error("detect_describe_u8: stride %d < width %d", stride, w); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  int rc;
-  const bool twin = stride == w && det->detectorType != MODS_DET_MSER, strips = twin && mods::u8_strips_wanted(c, w, h, stride);
-  if ((rc = mods::u8_to_f32_launch(c, img_u8_dev, n_img, w, h, stride, c->input_dev, strips))) return rc;
-  c->img_u8_dev = twin ? img_u8_dev : nullptr;
-  c->img_strip_dev = strips ? c->u8_strip_dev.get() : nullptr;
-  if (c->img_u8_dev) c->u8_source_calls++;
-  if (c->img_strip_dev) c->u8_strip_calls++;
-  rc = dd_call(c, c->input_dev, n_img, w, h, w, det, desc, n_detected_host, n_regions_host);
-  c->img_u8_dev = c->img_strip_dev = nullptr;
-  return rc;
+  PixelSources img;
+  const int rc = mods::u8_sources_launch(c, img_u8, n_img, w, h, stride, det->detectorType != MODS_DET_MSER, &img);
+  if (rc) return rc;
+  return dd_call(c, img, n_img, w, h, w, det, desc, n_detected_host, n_regions_host);
 }
 
 // ---- the strip layout of the 8-bit twin, for the tests: the header's functions as they are (no device), and the twin of a batch as the
@@ -741,14 +734,14 @@ int mods_orient_describe(mods_ctx *c, const float *img, int w, int h, int stride
   MODS_HIP_CHECK(hipMemcpyAsync(c->keys_dev, keys, sizeof(mods_affkey) * n_keys, hipMemcpyHostToDevice, c->stream));
   MODS_HIP_CHECK(hipMemcpyAsync(c->cand_count + 2 * c->batch, &n_keys, sizeof(int), hipMemcpyHostToDevice, c->stream));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));   // n_keys is a stack variable
-  int rc = describe_run(c, c->input_dev, 1, w, h, par);
+  int rc = describe_run(c, {c->input_dev}, 1, w, h, par);
   if (rc) return rc;
   if ((rc = mods_regions_fetch(c, 0, out, max_out, n_out))) return rc;
   return check_desc_err(c);
 }
 
 // mods_orient_describe for an 8-bit grey host image: staged packed in u8_stage_dev, converted (exactly) into input_dev, and the 8-bit
-// copy is the call's sampling source in the kernels whose switch is on (mods_ctx_u8_kernels) - the given keypoints reach every size
+// copy is the call's sampling source in the kernels whose mask bit is on (mods_ctx_u8_kernels) - the given keypoints reach every size
 // class of those kernels, which the detector's own keypoints on an affordable image do not.  Everything that does not need the
 // context is checked first, so that a bad call is refused without a device.
 int mods_orient_describe_u8(mods_ctx *c, const unsigned char *img_u8, int w, int h, int stride, const mods_affkey *keys, int n_keys,
@@ -767,15 +760,9 @@ int mods_orient_describe_u8(mods_ctx *c, const unsigned char *img_u8, int w, int
   MODS_HIP_CHECK(hipMemcpyAsync(c->keys_dev, keys, sizeof(mods_affkey) * n_keys, hipMemcpyHostToDevice, c->stream));
   MODS_HIP_CHECK(hipMemcpyAsync(c->cand_count + 2 * c->batch, &n_keys, sizeof(int), hipMemcpyHostToDevice, c->stream));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));   // n_keys is a stack variable
-  const bool strips = mods::u8_strips_wanted(c, w, h, w);
-  if ((rc = mods::u8_to_f32_launch(c, c->u8_stage_dev, 1, w, h, w, c->input_dev, strips))) return rc;
-  c->img_u8_dev = c->u8_stage_dev;
-  c->img_strip_dev = strips ? c->u8_strip_dev.get() : nullptr;
-  c->u8_source_calls++;
-  if (c->img_strip_dev) c->u8_strip_calls++;
-  rc = describe_run(c, c->input_dev, 1, w, h, par);
-  c->img_u8_dev = c->img_strip_dev = nullptr;
-  if (rc) return rc;
+  PixelSources img;
+  if ((rc = mods::u8_sources_launch(c, c->u8_stage_dev, 1, w, h, w, true, &img))) return rc;
+  if ((rc = describe_run(c, img, 1, w, h, par))) return rc;
   if ((rc = mods_regions_fetch(c, 0, out, max_out, n_out))) return rc;
   return check_desc_err(c);
 }

@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/mods_hip.h"
 #include "buffer.hpp"
+#include "pixel_sources.hpp"
 
 namespace mods {
 
@@ -221,17 +222,13 @@ struct mods_ctx {
   mods::Buf<unsigned long long> nms_mask;   // ballot words of one octave's NMS
   mods::PinnedBuf<int> host_counts;
   mods::Buf<unsigned char> u8_stage_dev;   // [batch][max_h][max_w] staging of 8-bit host images (pair pipeline), lazily allocated
-  // the 8-bit twin [n_img][h][w] of the fp32 images of the detect + describe call in progress (mods_detect_describe_dev_u8), read by
-  // describe_run_view; nullptr outside such a call
-  const unsigned char *img_u8_dev = nullptr;
-  // the same images once more in 16-byte column strips (u8_strips.hpp), made by the conversion launch of such a call when a kernel
-  // of the mask samples from strips: [n_img][strip_count(w)][h rounded up to 8][16].  The library makes it, reads it and forgets it
-  // with the call; img_strip_dev: the call's, or nullptr
+  // the images of an 8-bit call once more in 16-byte column strips (u8_strips.hpp), made by the conversion launch of such a call
+  // when a kernel of the mask samples from strips: [n_img][strip_count(w)][h rounded up to 8][16].  The library makes it, reads it
+  // and forgets it with the call (u8_sources_launch hands it to the call as PixelSources::strips)
   mods::Buf<unsigned char> u8_strip_dev;
-  const unsigned char *img_strip_dev = nullptr;
   long u8_strip_calls = 0;               // calls that had one (mods_ctx_u8_strip_calls)
-  int u8_kernels = -1;                   // which kernels sample from the twin: -1 = the build's choice (describe_common.hpp), else a mask
-  long u8_source_calls = 0;              // detect + describe calls that had such a twin (mods_ctx_u8_source_calls)
+  int u8_kernels = -1;                   // which kernels sample from the 8-bit copies: -1 = the default (pixel_sources.hpp), else a mask
+  long u8_source_calls = 0;              // calls whose 8-bit images were a sampling source (mods_ctx_u8_source_calls)
   // CLAHE (clahe.hip): LUT scratch [n_img][tiles_y * tiles_x][256] (clahe_reserve); clahe_on: the pair pipeline's 8-bit batches are
   // equalised with clahe_par on their way to fp32 (mods_pipeline_create_clahe)
   mods::Buf<unsigned char> clahe_lut;
@@ -336,10 +333,9 @@ struct mods_ctx {
   bool dd_graphs = false;
   // `epoch` = dev_state_epoch when the call was made: every host-side change of device tables or pools bumps that counter
   // (mods::dev_state_changed / dev_pool_reallocated), so a call behind such a change is never taken for a repeat of the one before it
-  struct DdKey { const float *img = nullptr; const unsigned char *img_u8 = nullptr;     // img_u8: the call's 8-bit sampling source, or nullptr
-                 const unsigned char *img_strips = nullptr;                              // and its strip twin (its layout follows from w, h)
+  struct DdKey { mods::PixelSources img;      // the call's images: fp32, and its 8-bit sampling sources (the strip twin's layout follows from w, h)
                  int n_img = 0, w = 0, h = 0, stride = 0; unsigned long long par_hash = 0, epoch = ~0ull;
-                 bool operator==(const DdKey &o) const { return img == o.img && img_u8 == o.img_u8 && img_strips == o.img_strips && n_img == o.n_img && w == o.w && h == o.h && stride == o.stride && par_hash == o.par_hash && epoch == o.epoch; } };
+                 bool operator==(const DdKey &o) const { return img == o.img && n_img == o.n_img && w == o.w && h == o.h && stride == o.stride && par_hash == o.par_hash && epoch == o.epoch; } };
   unsigned long long dev_state_epoch = 0;
   std::vector<std::pair<DdKey, hipGraphExec_t>> dd_cache;   // recorded calls (a worker sees a few batch sizes), oldest first
   bool dd_stale = false;                                    // a pool the recordings point into was reallocated: they are dropped
@@ -428,14 +424,16 @@ bool ransac_profile_on();     // MODS_RANSAC_PROF: per-call breakdown of the ver
 int ransac_profile_mode();    // 0 off, 1 wall time, 2 the calling thread's CPU time (MODS_RANSAC_PROF=cpu)
 
 // describe.hip
-int describe_run(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par);
+// img: the call's copies of the images (pixel_sources.hpp); a view (H given) and a context with hooks or networks sample from fp32 only
+int describe_run(mods_ctx *ctx, const PixelSources &img, int n_img, int w, int h, const mods_describe_params *par);
 // pair.hip.  strips: the same launch lays the images out in c->u8_strip_dev as well (packed rows only: u8_strips_wanted)
 int u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, float *dst, bool strips = false);
+// ... into c->input_dev, for a call that came in as 8-bit: *img = what the call samples from.  The 8-bit images themselves are a
+// source when `twin` allows it and their rows are packed, the strip twin is made and is one when u8_strips_wanted on top of that;
+// counts both (u8_source_calls, u8_strip_calls)
+int u8_sources_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, bool twin, PixelSources *img);
 int u8_stage_ensure(mods_ctx *c);          // pair.hip: c->u8_stage_dev and c->u8_strip_dev allocated (a full batch of the context's largest images)
-// describe.hip: whether a call with these 8-bit images gets a strip twin - a kernel of the context's mask samples from strips, the
-// rows are packed and the size is one the layout's address arithmetic covers (strip_layout_ok)
-bool u8_strips_wanted(const mods_ctx *c, int w, int h, int stride);
-int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par, const double *H,
+int describe_run_view(mods_ctx *ctx, const PixelSources &img, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev);
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par);
 int launch_dominant_angle_test(mods_ctx *ctx, const float *patch_dev, int ps, double th, float *out_dev);

@@ -554,9 +554,9 @@ int describe_configure(mods_ctx *ctx, const mods_describe_params *par) {
 }
 
 // Orientation + compaction + description of the keypoints in ctx->keys_dev (as left by detect_run
-// or uploaded by mods_orient_describe) for images `img_dev` [n_img][h][w].
-int describe_run(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par) {
-  return describe_run_view(ctx, img_dev, n_img, w, h, par, nullptr, 0, 0, nullptr);
+// or uploaded by mods_orient_describe) for images `img` [n_img][h][w].
+int describe_run(mods_ctx *ctx, const PixelSources &img, int n_img, int w, int h, const mods_describe_params *par) {
+  return describe_run_view(ctx, img, n_img, w, h, par, nullptr, 0, 0, nullptr);
 }
 
 // Descriptors from outside the library (the ZMQ daemon of the reference's "ZMQ" descriptor, imagerepresentation.cpp:992-1006):
@@ -614,7 +614,7 @@ static int net_patches(mods_ctx *ctx, const float *img_dev, int n_img, DescConst
   MODS_HIP_CHECK(hipMemcpyAsync(ctx->region_count, counts.data(), sizeof(int) * n_img, hipMemcpyHostToDevice, ctx->stream));
   MODS_HIP_CHECK(mods::stream_wait(ctx->stream));   // (the host vectors above are pageable)
   k.desc_mr = mr; k.desc_ps = ps; k.patch_rule = 1; k.photo = 0;
-  int rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, false);
+  int rc = launch_extract_and_sift(ctx, {img_dev}, n_img, k, dmask, tab, false);
   if (rc) return rc;
   if (!patches) return MODS_OK;
   MODS_HIP_CHECK(mods::stream_wait(ctx->stream));
@@ -796,11 +796,7 @@ static void invert3_cv(const double *S, double *t) {
 // The same for a synthesised view: H (original -> view, 9 doubles) and the original image size; the
 // regions come out in the original frame (reproj_kp).  H == nullptr or HIsEye(H) (synth-detection.cpp:
 // 144-149): identity view.  det_copy_dev (optional): receives the described regions in the view frame.
-bool u8_strips_wanted(const mods_ctx *c, int w, int h, int stride) {
-  return (u8_kernel_mask(c) >> U8K_STRIPS_SHIFT) != 0 && stride == w && strip_layout_ok(w, h);
-}
-
-int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, const mods_describe_params *par, const double *H,
+int describe_run_view(mods_ctx *ctx, const PixelSources &img_all, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev) {
   int rc = dsp_check(ctx, par);
   if (rc) return rc;
@@ -835,11 +831,10 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
   k.max_bin = par->maxBinValue;
   k.patch_rule = par->fastExtraction ? 2 : 0;
   const bool external = ctx->ext_fn != nullptr || ctx->ext_net != nullptr;
-  // the call's 8-bit twin of img_dev (mods_detect_describe_dev_u8): the built-in orientation and description of an identity view
-  // sample from it; views and the external / network paths have fp32 only
-  const bool hooks = external || ctx->shape_fn || ctx->shape_net || ctx->ori_fn || ctx->ori_net;
-  const unsigned char *img_u8 = (!H && !hooks) ? ctx->img_u8_dev : nullptr;
-  const unsigned char *img_strips = img_u8 ? ctx->img_strip_dev : nullptr;
+  // the call's 8-bit copies of the images: the built-in orientation and description of an identity view sample from them; views and
+  // the external / network paths have fp32 only
+  const PixelSources img = (H || has_hooks(ctx) || has_nets(ctx)) ? img_all.fp32_only() : img_all;
+  const float *img_dev = img.f32;
   if (external && par->fastExtraction) { set_error("FastPatchExtraction with an external descriptor is not supported"); return MODS_E_ARG; }
   if (external) { k.desc_mr = ctx->ext_mr; k.desc_ps = ctx->ext_ps; k.photo = 0; k.patch_rule = 1; }
   int *key_count = ctx->cand_count + 2 * ctx->batch;
@@ -858,15 +853,10 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
       const size_t need = sizeof(OriOut) * (size_t)k.ori_cap * ctx->max_cand * ctx->batch;
       MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->ori_multi_dev, need, need));
     }
-    if (img_strips && kernel_from_strips(ctx, U8K_ORIENT))
-      hipLaunchKernelGGL(orient_kernel<StripPx>, dim3(8192, n_img), dim3(64), lds, ctx->stream, (const StripPx *)img_strips, k, ctx->keys_dev,
-                         key_count, orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
-    else if (img_u8 && kernel_from_u8(ctx, U8K_ORIENT))
-      hipLaunchKernelGGL(orient_kernel<unsigned char>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_u8, k, ctx->keys_dev, key_count,
+    with_pixel_source(ctx->u8_kernels, img, U8K_ORIENT, [&](auto *px) {
+      hipLaunchKernelGGL(orient_kernel<PixelOf<decltype(px)>>, dim3(8192, n_img), dim3(64), lds, ctx->stream, px, k, ctx->keys_dev, key_count,
                          orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
-    else
-      hipLaunchKernelGGL(orient_kernel<float>, dim3(8192, n_img), dim3(64), lds, ctx->stream, img_dev, k, ctx->keys_dev, key_count,
-                         orimask, (OriOut *)ctx->ori_dev.get(), (OriOut *)ctx->ori_multi_dev.get());
+    });
     if (k.ori_cap > 1)
       hipLaunchKernelGGL(compact_regions_multi_kernel, dim3(1, n_img), dim3(1024), 0, ctx->stream, k, ctx->keys_dev, key_count,
                          (const OriOut *)ctx->ori_dev.get(), (const OriOut *)ctx->ori_multi_dev.get(), ctx->regions_dev, ctx->region_count, ctx->inside_count);
@@ -884,13 +874,13 @@ int describe_run_view(mods_ctx *ctx, const float *img_dev, int n_img, int w, int
     for (int s = 0; s < K; s++) {
       DescConst ks = k;
       ks.desc_mr = par->desc_mrSize * (ctx->dsp_start + s * ((ctx->dsp_end - ctx->dsp_start) / (K - 1)));
-      if ((rc = launch_extract_and_sift(ctx, img_dev, n_img, ks, dmask, tab, false, img_u8, img_strips))) return rc;
+      if ((rc = launch_extract_and_sift(ctx, img, n_img, ks, dmask, tab, false))) return rc;
       if ((rc = launch_dsp_accumulate(ctx, n_img, ks, dmask, tab, s == 0))) return rc;
     }
     if ((rc = launch_dsp_finish(ctx, n_img, k, par->halfDesc != 0))) return rc;
     ctx->have_half = par->halfDesc != 0;
   } else {
-    rc = launch_extract_and_sift(ctx, img_dev, n_img, k, dmask, tab, !external, img_u8, img_strips);
+    rc = launch_extract_and_sift(ctx, img, n_img, k, dmask, tab, !external);
     if (rc) return rc;
     ctx->have_half = false;
     if (par->halfDesc && !external) {

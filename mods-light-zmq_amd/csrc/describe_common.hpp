@@ -39,52 +39,9 @@ struct SiftTab {           // precomputeBinsAndWeights, siftdesc.cpp:22-71 (host
   float w0[64], w1[64];    // stored as double in the reference but float valued
 };
 
-// The kernels that gather from the input image (orient_kernel, extract_small_kernel, big_fused_kernel, big_sample_kernel) exist for
-// fp32 and for 8-bit pixels.  A call that has the batch as 8-bit grey in HBM as well (mods_detect_describe_dev_u8) samples from that
-// copy in the kernels whose switch is 1: the same values from a quarter of the bytes.  Each kernel keeps the form that was faster at
-// the benchmark's 32-image batch ("Sampling from the 8-bit twin"; profiles/u8_sampling_*); times per batch:
-#ifndef ORIENT_FROM_U8
-#define ORIENT_FROM_U8 0          // 1.853 against 1.861 ms, run-to-run deviation 0.067: no gain, stays on fp32
-#endif
-#ifndef EXTRACT_SMALL_FROM_U8
-#define EXTRACT_SMALL_FROM_U8 1   // 3 x 0.985 against 3 x 1.036 ms
-#endif
-#ifndef BIG_FUSED_FROM_U8
-#define BIG_FUSED_FROM_U8 1       // 2.67 against 2.88 ms
-#endif
-#ifndef BIG_SAMPLE_FROM_U8
-#define BIG_SAMPLE_FROM_U8 0      // no region of the benchmark's images reaches this kernel (P2 > 1024): not measured, stays on fp32
-#endif
-// The strip layout of the twin (u8_strips.hpp) is the third form of each: 1 = the kernel samples from the strips when the call has
-// them, whatever its switch above says (the strip columns of the same table; profiles/strip_u8_*).  Times per
-// batch against the kernel's form above:
-#ifndef ORIENT_FROM_STRIPS
-#define ORIENT_FROM_STRIPS 1          // 1.759 against 1.867 ms (fp32)
-#endif
-#ifndef EXTRACT_SMALL_FROM_STRIPS
-#define EXTRACT_SMALL_FROM_STRIPS 1   // 3 x 0.942 against 3 x 0.991 ms (row-major 8-bit)
-#endif
-#ifndef BIG_FUSED_FROM_STRIPS
-#define BIG_FUSED_FROM_STRIPS 1       // 2.36 against 2.68 ms (row-major 8-bit)
-#endif
-#ifndef BIG_SAMPLE_FROM_STRIPS
-#define BIG_SAMPLE_FROM_STRIPS 0      // not measured, as above: stays on fp32
-#endif
-// the same choice as a mask, and the one a context was given for its calls instead (mods_ctx_u8_kernels: the tests run the forms that
-// the defaults leave out)
-// bits 4-7: the same kernel samples from the strip twin of the 8-bit images (u8_strips.hpp) when the call has one; it goes before bits 0-3
-enum { U8K_ORIENT = 1, U8K_EXTRACT_SMALL = 2, U8K_BIG_FUSED = 4, U8K_BIG_SAMPLE = 8, U8K_STRIPS_SHIFT = 4, U8K_ALL = 255 };
-constexpr int kU8KernelsDefault = (ORIENT_FROM_U8 ? U8K_ORIENT : 0) | (EXTRACT_SMALL_FROM_U8 ? U8K_EXTRACT_SMALL : 0) |
-                                  (BIG_FUSED_FROM_U8 ? U8K_BIG_FUSED : 0) | (BIG_SAMPLE_FROM_U8 ? U8K_BIG_SAMPLE : 0) |
-                                  ((ORIENT_FROM_STRIPS ? U8K_ORIENT : 0) | (EXTRACT_SMALL_FROM_STRIPS ? U8K_EXTRACT_SMALL : 0) |
-                                   (BIG_FUSED_FROM_STRIPS ? U8K_BIG_FUSED : 0) | (BIG_SAMPLE_FROM_STRIPS ? U8K_BIG_SAMPLE : 0)) << U8K_STRIPS_SHIFT;
-inline int u8_kernel_mask(const mods_ctx *ctx) { return ctx->u8_kernels < 0 ? kU8KernelsDefault : ctx->u8_kernels; }
-inline bool kernel_from_u8(const mods_ctx *ctx, int kernel) { return (u8_kernel_mask(ctx) & kernel) != 0; }
-inline bool kernel_from_strips(const mods_ctx *ctx, int kernel) { return (u8_kernel_mask(ctx) & (kernel << U8K_STRIPS_SHIFT)) != 0; }
-
-// sift.hip.  img_u8: the same images [n_img][h][w] as 8-bit grey, or nullptr; img_strips: those in column strips, or nullptr
-int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab,
-                            bool run_sift = true, const unsigned char *img_u8 = nullptr, const unsigned char *img_strips = nullptr);
+// sift.hip.  img: the call's copies of the images [n_img][h][w] (pixel_sources.hpp chooses among them, kernel by kernel)
+int launch_extract_and_sift(mods_ctx *ctx, const PixelSources &img, int n_img, DescConst k, const float *dmask, const SiftTab *tab,
+                            bool run_sift = true);
 // HalfRootSIFT twins of the described regions: copies regions_dev to regions_half_dev and overwrites the descriptors from the
 // patch store left by launch_extract_and_sift (block-per-region SIFT kernel)
 int launch_half_sift(mods_ctx *ctx, int n_img, DescConst k, const float *dmask, const SiftTab *tab);

@@ -1094,14 +1094,38 @@ __global__ __launch_bounds__(256) void select_keys_kernel(int max_cand, const mo
 }
 
 // ---------------------------------------------------------------------------------------
-// Ballot words one image's NMS writes for an octave (detect_run_stages lays the octaves out with the same arithmetic; 0: the
-// border leaves the octave no interior)
-size_t nms_octave_mask_words(int w, int h, int border, int n_scales) {
+// How one octave's NMS is cut into blocks and its ballot words are laid out: the one place that knows it (the context sizes the
+// mask from it, detect_run_stages plans the launches from it).  ih == 0: the border leaves the octave no interior
+struct NmsLayout {
+  bool wide;       // rows are 16-byte aligned float4s: nms4_kernel, four words per block; else nms_kernel, one
+  int nbx;         // blocks per block-row
+  int words;       // ballot words per interior row
+  int ih;          // interior rows
+  int nby;         // block rows
+};
+static NmsLayout nms_octave_layout(int w, int h, int border) {
   const int iw = w - 2 * border, ih = h - 2 * border;
-  if (iw <= 0 || ih <= 0) return 0;
+  if (iw <= 0 || ih <= 0) return {false, 0, 0, 0, 0};
   const bool wide = (w & 3) == 0 && w >= 8;
-  const int nblk = wide ? (w + NMS4_COLS - 1) / NMS4_COLS : (iw + NMS_COLS - 1) / NMS_COLS;
-  return (size_t)n_scales * ih * (wide ? 4 * nblk : nblk);
+  const int nbx = wide ? (w + NMS4_COLS - 1) / NMS4_COLS : (iw + NMS_COLS - 1) / NMS_COLS;
+  return {wide, nbx, wide ? 4 * nbx : nbx, ih, (ih + 4 * NMS_ROWS - 1) / (4 * NMS_ROWS)};
+}
+// Ballot words one image's NMS writes for an octave
+size_t nms_octave_mask_words(int w, int h, int border, int n_scales) {
+  const NmsLayout L = nms_octave_layout(w, h, border);
+  return (size_t)n_scales * L.ih * L.words;
+}
+
+// The two ways an NmsPlan grows: by an octave (n_blocks: the blocks its launch gives the octave), and by entry e of another plan
+static void nms_plan_add(NmsPlan &pl, int oi, int w, int h, const NmsLayout &L, size_t mask_off, int n_blocks) {
+  const int i = pl.n++;
+  pl.oi[i] = oi; pl.nbx[i] = L.nbx; pl.w[i] = w; pl.h[i] = h; pl.words[i] = L.words; pl.wide[i] = L.wide ? 1 : 0;
+  pl.mask_off[i] = mask_off;
+  pl.blk_begin[i + 1] = pl.blk_begin[i] + n_blocks;
+}
+static void nms_plan_add(NmsPlan &pl, const NmsPlan &src, int e) {
+  const NmsLayout L = {src.wide[e] != 0, src.nbx[e], src.words[e], 0, 0};     // (a plan keeps no interior height or block rows)
+  nms_plan_add(pl, src.oi[e], src.w[e], src.h[e], L, src.mask_off[e], src.blk_begin[e + 1] - src.blk_begin[e]);
 }
 
 static int detect_run_stages(mods_ctx *ctx);
@@ -1167,34 +1191,18 @@ static int detect_run_stages(mods_ctx *ctx) {
     size_t mask_words = 0;
     for (int oi = 0; oi < P.n_oct; oi++) {
       const OctaveDev &o = P.oct[oi];
-      const int iw = o.w - 2 * par.border, ih = o.h - 2 * par.border;
-      if (iw <= 0 || ih <= 0) continue;
-      const bool wide = (o.w & 3) == 0 && o.w >= 8;
-      const int nblk = wide ? (o.w + NMS4_COLS - 1) / NMS4_COLS : (iw + NMS_COLS - 1) / NMS_COLS;
-      const int words = wide ? 4 * nblk : nblk;
-      const int nby = (ih + 4 * NMS_ROWS - 1) / (4 * NMS_ROWS);
-      NmsPlan &pl = wide ? wide_pl : narrow_pl;
-      pl.oi[pl.n] = oi; pl.nbx[pl.n] = nblk; pl.w[pl.n] = o.w; pl.h[pl.n] = o.h; pl.words[pl.n] = words; pl.wide[pl.n] = wide ? 1 : 0;
-      pl.mask_off[pl.n] = mask_words;
-      pl.blk_begin[pl.n + 1] = pl.blk_begin[pl.n] + nblk * nby;
-      pl.n++;
+      const NmsLayout L = nms_octave_layout(o.w, o.h, par.border);
+      if (L.ih == 0) continue;
+      nms_plan_add(L.wide ? wide_pl : narrow_pl, oi, o.w, o.h, L, mask_words, L.nbx * L.nby);
       const int total = (int)nms_octave_mask_words(o.w, o.h, par.border, par.numberOfScales);   // numberOfScales * ih * words
-      comp_pl.oi[comp_pl.n] = oi; comp_pl.nbx[comp_pl.n] = nblk; comp_pl.w[comp_pl.n] = o.w; comp_pl.h[comp_pl.n] = o.h;
-      comp_pl.words[comp_pl.n] = words; comp_pl.wide[comp_pl.n] = wide ? 1 : 0; comp_pl.mask_off[comp_pl.n] = mask_words;
-      comp_pl.blk_begin[comp_pl.n + 1] = comp_pl.blk_begin[comp_pl.n] + (total + 256 * NMS_CW - 1) / (256 * NMS_CW);
-      comp_pl.n++;
+      nms_plan_add(comp_pl, oi, o.w, o.h, L, mask_words, (total + 256 * NMS_CW - 1) / (256 * NMS_CW));
       mask_words += (size_t)n_img * total;
     }
     if (mask_words > ctx->nms_mask.capacity()) { set_error("nms mask buffer too small"); return MODS_E_CAPACITY; }
     unsigned long long *mask = (unsigned long long *)ctx->nms_mask;
     if (wide_pl.n && narrow_pl.n && narrow_pl.blk_begin[narrow_pl.n] <= 64 && wide_pl.n + narrow_pl.n <= kMaxOctaves) {
-      for (int e = 0; e < narrow_pl.n; e++) {      // the tail octaves (30 x 17 pixels ...): not worth a launch of their own
-        const int d = wide_pl.n;
-        wide_pl.oi[d] = narrow_pl.oi[e]; wide_pl.nbx[d] = narrow_pl.nbx[e]; wide_pl.w[d] = narrow_pl.w[e]; wide_pl.h[d] = narrow_pl.h[e];
-        wide_pl.words[d] = narrow_pl.words[e]; wide_pl.wide[d] = 0; wide_pl.mask_off[d] = narrow_pl.mask_off[e];
-        wide_pl.blk_begin[d + 1] = wide_pl.blk_begin[d] + (narrow_pl.blk_begin[e + 1] - narrow_pl.blk_begin[e]);
-        wide_pl.n++;
-      }
+      // the tail octaves (30 x 17 pixels ...): not worth a launch of their own (their entries keep wide = 0)
+      for (int e = 0; e < narrow_pl.n; e++) nms_plan_add(wide_pl, narrow_pl, e);
       narrow_pl.n = 0;
     }
     if (ctx->pyr_side) {
@@ -1202,14 +1210,7 @@ static int detect_run_stages(mods_ctx *ctx) {
       // planes, the compaction waits for both
       auto split = [&](const NmsPlan &pl, NmsPlan &first, NmsPlan &rest) {
         first.n = rest.n = 0; first.blk_begin[0] = rest.blk_begin[0] = 0;
-        for (int e = 0; e < pl.n; e++) {
-          NmsPlan &d = pl.oi[e] < ctx->pyr_side_first ? first : rest;
-          const int i = d.n;
-          d.oi[i] = pl.oi[e]; d.nbx[i] = pl.nbx[e]; d.w[i] = pl.w[e]; d.h[i] = pl.h[e]; d.words[i] = pl.words[e]; d.wide[i] = pl.wide[e];
-          d.mask_off[i] = pl.mask_off[e];
-          d.blk_begin[i + 1] = d.blk_begin[i] + (pl.blk_begin[e + 1] - pl.blk_begin[e]);
-          d.n++;
-        }
+        for (int e = 0; e < pl.n; e++) nms_plan_add(pl.oi[e] < ctx->pyr_side_first ? first : rest, pl, e);
       };
       NmsPlan w0, w1, n0, n1;
       split(wide_pl, w0, w1); split(narrow_pl, n0, n1);

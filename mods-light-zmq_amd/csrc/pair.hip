@@ -76,7 +76,7 @@ extern "C" __global__ __launch_bounds__(256) void u8_rows_to_f32_kernel(const un
 // the context's staging area for 8-bit host images, allocated at its first use
 int mods::u8_stage_ensure(mods_ctx *c) {
   MODS_HIP_CHECK(c->u8_stage_dev.reserve((size_t)c->max_w * c->max_h * c->batch + 16));
-  if (mods::u8_strips_wanted(c, c->max_w, c->max_h, c->max_w))     // (a mask that is given later reserves at its first call)
+  if (mods::u8_strips_wanted(c->u8_kernels, c->max_w, c->max_h, c->max_w))     // (a mask that is given later reserves at its first call)
     MODS_HIP_CHECK(c->u8_strip_dev.reserve(mods::strip_image_bytes(c->max_w, c->max_h) * c->batch));
   return MODS_OK;
 }
@@ -99,6 +99,16 @@ int mods::u8_to_f32_launch(mods_ctx *c, const unsigned char *src, int n_img, int
                        strips ? c->u8_strip_dev.get() : (unsigned char *)nullptr, n_img, w, h);
   }
   MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
+}
+int mods::u8_sources_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, int h, int stride, bool twin, PixelSources *img) {
+  twin = twin && stride == w;
+  const bool strips = twin && mods::u8_strips_wanted(c->u8_kernels, w, h, stride);
+  const int rc = mods::u8_to_f32_launch(c, src, n_img, w, h, stride, c->input_dev, strips);
+  if (rc) return rc;
+  *img = {c->input_dev, twin ? src : nullptr, strips ? c->u8_strip_dev.get() : nullptr};
+  if (img->u8) c->u8_source_calls++;
+  if (img->strips) c->u8_strip_calls++;
   return MODS_OK;
 }
 

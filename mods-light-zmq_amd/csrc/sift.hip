@@ -1647,8 +1647,7 @@ static int sift_col_span(int ps) {
 }
 
 // ---------------------------------------------------------------------------------------
-int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool run_sift,
-                            const unsigned char *img_u8, const unsigned char *img_strips) {
+int launch_extract_and_sift(mods_ctx *ctx, const PixelSources &img, int n_img, DescConst k, const float *dmask, const SiftTab *tab, bool run_sift) {
   StageScope ts(ctx, MODS_STAGE_DESCRIBE);
   const int ps = k.desc_ps, ps2 = 2 * ps, pp = ps * ps;
   // HBM layout of the description scratch: patch store [n_img][reg_cap][ps*ps] | big-tier bookkeeping | slab pool
@@ -1691,40 +1690,23 @@ int launch_extract_and_sift(mods_ctx *ctx, const float *img_dev, int n_img, Desc
       kt.p2_lo = tiers[t]; kt.p2_hi = tiers[t + 1];
       const size_t capS = kt.p2_hi > 4 ? kt.p2_hi : 4;
       const size_t ldsS = sizeof(float) * (capS * odd4((int)capS) + capS * ((capS + 3) & ~(size_t)3) + 2 * ps2 + 32) + 32;
-      if (img_strips && kernel_from_strips(ctx, U8K_EXTRACT_SMALL))
-        hipLaunchKernelGGL(extract_small_kernel<StripPx>, dim3(4096), dim3(256), ldsS, ctx->stream, (const StripPx *)img_strips, kt, ctx->regions_dev,
+      with_pixel_source(ctx->u8_kernels, img, U8K_EXTRACT_SMALL, [&](auto *px) {
+        hipLaunchKernelGGL(extract_small_kernel<PixelOf<decltype(px)>>, dim3(4096), dim3(256), ldsS, ctx->stream, px, kt, ctx->regions_dev,
                            small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
                            (const float *)ctx->blur_table_dev);
-      else if (img_u8 && kernel_from_u8(ctx, U8K_EXTRACT_SMALL))
-        hipLaunchKernelGGL(extract_small_kernel<unsigned char>, dim3(4096), dim3(256), ldsS, ctx->stream, img_u8, kt, ctx->regions_dev,
-                           small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
-                           (const float *)ctx->blur_table_dev);
-      else
-        hipLaunchKernelGGL(extract_small_kernel<float>, dim3(4096), dim3(256), ldsS, ctx->stream, img_dev, kt, ctx->regions_dev,
-                           small_items + (size_t)t * small_cap_items, &bl->n_small[t], small_cap_items, patches,
-                           (const float *)ctx->blur_table_dev);
+      });
     }
   }
   const size_t ldsH = sizeof(float) * (k.tap_cap + 4 * ps2) + 32;
   hipLaunchKernelGGL(big_setup_kernel, dim3(1024), dim3(256), ldsH, ctx->stream, k, bl, bregs, max_big, pool, ctx->desc_err_dev);
-  if (img_strips && kernel_from_strips(ctx, U8K_BIG_FUSED))
-    hipLaunchKernelGGL(big_fused_kernel<StripPx>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, (const StripPx *)img_strips, k, bl, bregs,
-                       fitems, max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
-  else if (img_u8 && kernel_from_u8(ctx, U8K_BIG_FUSED))
-    hipLaunchKernelGGL(big_fused_kernel<unsigned char>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_u8, k, bl, bregs, fitems,
+  with_pixel_source(ctx->u8_kernels, img, U8K_BIG_FUSED, [&](auto *px) {
+    hipLaunchKernelGGL(big_fused_kernel<PixelOf<decltype(px)>>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, px, k, bl, bregs, fitems,
                        max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
-  else
-    hipLaunchKernelGGL(big_fused_kernel<float>, dim3(8192), dim3(256), BIG_FUSE_KB * 1024, ctx->stream, img_dev, k, bl, bregs, fitems,
-                       max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
-  if (img_strips && kernel_from_strips(ctx, U8K_BIG_SAMPLE))
-    hipLaunchKernelGGL(big_sample_kernel<StripPx>, dim3(4096), dim3(256), 0, ctx->stream, (const StripPx *)img_strips, k, bl, bregs, sitems,
-                       max_items, ctx->regions_dev, pool, ctx->desc_err_dev);
-  else if (img_u8 && kernel_from_u8(ctx, U8K_BIG_SAMPLE))
-    hipLaunchKernelGGL(big_sample_kernel<unsigned char>, dim3(4096), dim3(256), 0, ctx->stream, img_u8, k, bl, bregs, sitems, max_items,
+  });
+  with_pixel_source(ctx->u8_kernels, img, U8K_BIG_SAMPLE, [&](auto *px) {
+    hipLaunchKernelGGL(big_sample_kernel<PixelOf<decltype(px)>>, dim3(4096), dim3(256), 0, ctx->stream, px, k, bl, bregs, sitems, max_items,
                        ctx->regions_dev, pool, ctx->desc_err_dev);
-  else
-    hipLaunchKernelGGL(big_sample_kernel<float>, dim3(4096), dim3(256), 0, ctx->stream, img_dev, k, bl, bregs, sitems, max_items,
-                       ctx->regions_dev, pool, ctx->desc_err_dev);
+  });
   hipLaunchKernelGGL(big_rowpass_kernel, dim3(4096), dim3(256), 0, ctx->stream, k, bl, bregs, ritems, max_items, pool,
                      ctx->desc_err_dev);
   hipLaunchKernelGGL(big_colres_kernel, dim3(4096), dim3(256), 0, ctx->stream, k, bl, bregs, max_big, pool, patches, ctx->desc_err_dev);

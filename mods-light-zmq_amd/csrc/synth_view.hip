@@ -289,7 +289,7 @@ static int view_detect_describe(mods_ctx *c, const float *const *src_dev, int n_
     if ((rc = mods_synth_view_dev(c, src_dev[i], w, h, stride, &g, doBlur, c->view_dev + i * vpx))) return rc;
   // DetectAffineKeypoints / DetectMSERs scale regionsNumber by the SynthImage fields |tilt|, zoom (scale-space-detector.cpp:20-21, extrema.cpp:201-202)
   if ((rc = detect_any(c, c->view_dev, n_src, g.w_new, g.h_new, g.w_new, det, g.tilt, g.zoom))) return rc;
-  if ((rc = describe_run_view(c, c->view_dev, n_src, g.w_new, g.h_new, desc, g.H, w, h, nullptr))) return rc;
+  if ((rc = describe_run_view(c, {c->view_dev}, n_src, g.w_new, g.h_new, desc, g.H, w, h, nullptr))) return rc;
   // every count and the error flag of the view in ONE round trip (pinned host words; three synchronisations before)
   int *hc = c->host_counts;
   MODS_HIP_CHECK(hipMemcpyAsync(hc, c->cand_count, sizeof(int) * 3 * c->batch, hipMemcpyDeviceToHost, c->stream));

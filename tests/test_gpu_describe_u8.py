@@ -107,6 +107,42 @@ def test_u8_entry_point_repeated_calls(pkg):
         ctx.close()
 
 
+def test_fp32_calls_after_u8_call_sample_their_own_images(pkg):
+    """An 8-bit call of pair A with every kernel on the 8-bit copies (mask 255: the strip twin is made), then two fp32 calls of ANOTHER
+    pair B through the same context - detect_describe_dev of the batch and orient_describe of B's first image with its keys - with A's
+    8-bit device tensor overwritten in between.  A call that still sampled from the earlier call's 8-bit images or strips would give
+    other regions: both results must be the bytes that a context which never saw an 8-bit image gives, and the counters say that
+    one call had the 8-bit sources."""
+    import torch
+    w, h = 320, 240
+    A = np.stack(synth.pair(w, h, seed=7)[:2])
+    B = np.stack(synth.pair(w, h, seed=11)[:2])
+    assert not np.array_equal(A, B)
+    tB = torch.from_numpy(B).cuda()
+    t8 = torch.from_numpy(A.astype(np.uint8)).cuda()
+    torch.cuda.synchronize()
+    fresh, ctx = pkg.Context(0, w, h, 2), pkg.Context(0, w, h, 2)
+    try:
+        fresh.detect_describe_dev(tB.data_ptr(), 2, w, h)
+        want_dd = [fresh.regions_fetch(i).tobytes() for i in range(2)]
+        keys = fresh.detect_hessian_affine(B[0])
+        want_od = fresh.orient_describe(B[0], keys).tobytes()
+        assert len(want_dd[0]) > 0 and len(want_dd[1]) > 0 and len(keys) > 100 and len(want_od) > 0
+        assert fresh.u8_source_calls() == 0 and fresh.u8_strip_calls() == 0
+
+        ctx.set_u8_kernels(255)
+        _, nrA = ctx.detect_describe_dev_u8(t8.data_ptr(), 2, w, h)
+        assert min(nrA) > 0 and [ctx.regions_fetch(i).tobytes() for i in range(2)] != want_dd
+        t8.zero_()
+        torch.cuda.synchronize()
+        ctx.detect_describe_dev(tB.data_ptr(), 2, w, h)
+        assert [ctx.regions_fetch(i).tobytes() for i in range(2)] == want_dd
+        assert ctx.orient_describe(B[0], keys).tobytes() == want_od
+        assert ctx.u8_source_calls() == 1 and ctx.u8_strip_calls() == 1
+    finally:
+        fresh.close(); ctx.close()
+
+
 RES_FIELDS = ("n_tentatives", "n_unique", "n_inliers", "ransac_samples", "ransac_lo", "ransac_rejects")
 
 
