@@ -139,6 +139,8 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_GUIDED,       /* a guided search (mods_match_guided[_reps]): pack, both gate sweeps, accept, compaction and emit */
        MODS_STAGE_MATCH_MUTUAL, /* the mutual check of a search alone (mods_ctx_match_mutual: list + sweep), inside MODS_STAGE_MATCH */
        MODS_STAGE_OVERLAP,      /* an overlap search (mods_match_overlap[_reps]): pack, the sweep, accept, compaction and emit */
+       MODS_STAGE_OVERLAP_AREA, /* an area-overlap search (mods_match_overlap_area[_reps]): pack, both gate sweeps, the lattice walk,
+                                 * accept, compaction and emit - in two scopes, the host reads the length of the pair list between them */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -847,7 +849,8 @@ int mods_match_guided_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgre
  * the pair.  The reference reads [OverlapMatching] doOverlapMatch / overlapError (io_mods.cpp:685-687) and prints "Overlap
  * matches with E <" (mods.cpp:522-523); the error is the linearised one of ellipseOverlapH / ellipseOverlapHPrep
  * (matching/matching.hpp:170-253) with linH (synth-detection.cpp:1498) and rectifyAffineTransformationUpIsUp
- * (detectors/helpers.cpp:401), not the area of intersection of Mikolajczyk et al.  No descriptor takes part.  csrc/overlap.hip.
+ * (detectors/helpers.cpp:401), not the area of intersection of Mikolajczyk et al. (that measure: mods_match_overlap_area below).
+ * No descriptor takes part.  csrc/overlap.hip.
  *
  * fp64 throughout, one rounding per operation as written; sqrt and / are the correctly rounded ones.  H is row-major, image 1 ->
  * image 2, as mods_ransac_params.gtH holds it; Hi = H[i].  A region is (x, y, s, a11, a12, a21, a22); k = 3.0.
@@ -905,6 +908,66 @@ int mods_match_overlap_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgr
                             const mods_overlap_params *par, mods_overlap_match *out, int max_out, int *n_out,
                             mods_overlap_counts *counts);             /* HBM-resident banks */
 int mods_ctx_overlap_splits(mods_ctx *ctx, int splits);
+
+/* ---- area-overlap matching of two region lists (the repeatability measure of Mikolajczyk et al., IJCV 2005) --------------
+ * The same question as mods_match_overlap, scored with the customary measure: eps = 1 - |A n B| / |A u B| of the two ellipses, the
+ * pair first rescaled so that the image-1 region has the area of a circle of radius 30, accepted below 0.4, regions assigned one
+ * to one greedily by increasing error.  The areas are counted on the integer lattice, so the contract is exact integers.  No
+ * counterpart in the reference; VGG's c_eoverlap is not in its tree, so parity with it is UNPINNED: the contract is this
+ * restatement.  csrc/overlap_area.hip.
+ *
+ * The arithmetic regime of the overlap contract above: fp64 throughout, one rounding per operation in the order written; sqrt and /
+ * are the correctly rounded ones; every comparison with NaN fails.  min(a, b) is a < b ? a : b, max(a, b) is a > b ? a : b.
+ *   Query record: px, py, C11 .. C22 exactly as above (projected centre, C = linH(x) * (3.0*s) * A).
+ *   Train record: x2, y2, Mij = (3.0*s)*aij.
+ *   Common area: the test and its counts are the rule above, unchanged.
+ *   Pair (q, t), set-up:
+ *     detC = C11*C22 - C12*C21, f = 30.0 / sqrt(fabs(detC)), Qij = f*Cij, Tij = f*Mij, dx = f*(px - x2), dy = f*(py - y2);
+ *     qex = sqrt(Q11*Q11 + Q12*Q12), qey = sqrt(Q21*Q21 + Q22*Q22), tex and tey the same from T;
+ *     at = fabs(T11*T22 - T12*T21), g = 0.9*(1.0 - max_error);
+ *     x0 = floor(min(dx - qex, -tex)), x1 = ceil(max(dx + qex, tex)), y0 = floor(min(dy - qey, -tey)), y1 = ceil(max(dy + qey, tey)).
+ *   The pair is evaluated only when all of these hold:
+ *     at >= g*900.0, 900.0 >= g*at, fabs(dx) <= qex + tex, fabs(dy) <= qey + tey,
+ *     -x0 <= 256.0, x1 <= 256.0, -y0 <= 256.0, y1 <= 256.0.
+ *   The area gate only removes pairs whose analytic error is at least max_error, with 10 % of slack; the box gate removes disjoint
+ *   pairs; the cap bounds the work - a normalised ellipse longer than 256 matches nothing.  A pair that is not evaluated never
+ *   matches.
+ *   Evaluated pair:
+ *     dq = 1.0/(Q11*Q22 - Q12*Q21), QI11 = Q22*dq, QI12 = -(Q12*dq), QI21 = -(Q21*dq), QI22 = Q11*dq; TI the same from T.
+ *     For every integer lattice point (X, Y), x0 <= X <= x1, y0 <= Y <= y1 (the origin is the train's centre):
+ *       a = X - dx, b = Y - dy, u = QI11*a + QI12*b, v = QI21*a + QI22*b, inQ = (u*u + v*v <= 1.0);
+ *       u2 = TI11*X + TI12*Y, v2 = TI21*X + TI22*Y, inT = (u2*u2 + v2*v2 <= 1.0).
+ *     n_q_px, n_t_px, n_both count inQ, inT and both - plain integers, so no summation order exists.
+ *     uni = n_q_px + n_t_px - n_both; with uni == 0 the pair does not match, otherwise E = 1.0 - (double)n_both / (double)uni.
+ *     Every lattice point is decided by the expression as written; an implementation may skip points only where it has proved in
+ *     the same arithmetic that the expression is false (this one skips none).
+ *   Acceptance: E < max_error (strict).
+ *   Assignment, one_to_one:
+ *     0: per query the smallest (E, t).
+ *     1: the rule of mods_match_overlap - of the queries that chose one train the smallest (E, q) stays, the others are dropped.
+ *     2: greedy, the customary protocol - all accepted pairs sorted by (E, q, t) and taken in that order when neither region is
+ *        used yet.  The device produces the compact list of accepted pairs; the sort and the greedy pass over that short list
+ *        run on the host.
+ *   Output in query order in every mode; counts and repeatability as mods_overlap_counts above.  The result does not depend on
+ *   launch geometry, train splits or the arrival order of atomics.
+ * MODS_E_ARG with a mods_last_error text starting "match_overlap_area: ", before the context is looked at and before any device
+ * call: the refusals of mods_match_overlap, and max_error outside (0, 1] or one_to_one outside 0 .. 2.  A result longer than
+ * max_out: *n_out = the full length, MODS_E_CAPACITY, the counts are filled and nothing is copied.  The search has buffers of its
+ * own: it leaves the matcher's "last search", the guided and the linearised overlap buffers alone.  mods_ctx_overlap_splits also
+ * sets the train splits of its gate sweeps. */
+typedef struct mods_overlap_area_params {
+  double H[9];
+  double max_error;      /* 0.4 is the customary bound */
+  int one_to_one;        /* 0, 1, 2 */
+  int w1, h1, w2, h2;    /* image sizes for the common-area test; any 0: no test */
+} mods_overlap_area_params;
+typedef struct mods_overlap_area_match { int q, t; double E; int n_q_px, n_t_px, n_both, pad; } mods_overlap_area_match;
+int mods_match_overlap_area(mods_ctx *ctx, const mods_region *q, int n_q, const mods_region *t, int n_t,
+                            const mods_overlap_area_params *par, mods_overlap_area_match *out, int max_out, int *n_out,
+                            mods_overlap_counts *counts);             /* host lists, the testing seam */
+int mods_match_overlap_area_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgrep *t,
+                                 const mods_overlap_area_params *par, mods_overlap_area_match *out, int max_out, int *n_out,
+                                 mods_overlap_counts *counts);        /* HBM-resident banks */
 
 /* ---- mutual nearest-neighbour check of the FGINN matcher ----------------------------------------------
  * No counterpart in the reference, whose matcher is one-directional: a query's tentative goes to the verification even when its

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("MODS_LIB") or os.path.join(PKG_DIR, "libmodsgpu.so")
 MODS_OK = 0
 STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "orient", "describe", "match",
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
-          "overlap"]
+          "overlap", "overlap_area"]
 
 
 class ModsError(RuntimeError):
@@ -688,8 +688,20 @@ class Context:
                                         C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(counts)))
         return out[:n.value].copy(), counts
 
+    def match_overlap_area(self, q, t, params):
+        """mods_match_overlap_area: area-overlap matching (1 - intersection over union on the lattice) of two host region lists
+        (OverlapAreaParams); returns (matches as OVERLAP_AREA_DTYPE rows in query order, OverlapCounts)."""
+        q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
+        cap = max(len(q), 1)
+        out = np.zeros(cap, OVERLAP_AREA_DTYPE)
+        n = C.c_int()
+        counts = OverlapCounts()
+        _check(lib().mods_match_overlap_area(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
+                                             C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(counts)))
+        return out[:n.value].copy(), counts
+
     def overlap_splits(self, splits):
-        """mods_ctx_overlap_splits: train splits of the overlap sweep (0 = automatic); the result does not depend on it."""
+        """mods_ctx_overlap_splits: train splits of the overlap sweeps (0 = automatic); the result does not depend on it."""
         _check(lib().mods_ctx_overlap_splits(self.h, int(splits)))
 
     def clahe(self, img_u8, clip_limit=4.0, tiles=(8, 8)):
@@ -1150,6 +1162,36 @@ def match_overlap_reps(ctx, rep_q, rep_t, params, cap=None):
     counts = OverlapCounts()
     _check(lib().mods_match_overlap_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
                                          C.byref(counts)))
+    return out[:n.value].copy(), counts
+
+
+OVERLAP_AREA_DTYPE = np.dtype([("q", "i4"), ("t", "i4"), ("E", "f8"), ("n_q_px", "i4"), ("n_t_px", "i4"), ("n_both", "i4"), ("pad", "i4")])
+
+
+class OverlapAreaParams(C.Structure):
+    """mods_overlap_area_params: area-overlap matching, the repeatability measure of Mikolajczyk et al."""
+    _fields_ = [("H", C.c_double * 9), ("max_error", C.c_double), ("one_to_one", C.c_int),
+                ("w1", C.c_int), ("h1", C.c_int), ("w2", C.c_int), ("h2", C.c_int)]
+
+    @staticmethod
+    def default(H=None, max_error=0.4, one_to_one=2, w1=0, h1=0, w2=0, h2=0):
+        """the customary protocol: error below 0.4, greedy one-to-one assignment (one_to_one = 2; 0: per query the best train,
+        1: the rule of OverlapParams); H: 9 values row-major, image 1 -> image 2; sizes 0: no common-area test"""
+        p = OverlapAreaParams((C.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1), max_error, one_to_one, w1, h1, w2, h2)
+        if H is not None:
+            p.H = (C.c_double * 9)(*[float(v) for v in np.asarray(H, np.float64).reshape(9)])
+        return p
+
+
+def match_overlap_area_reps(ctx, rep_q, rep_t, params, cap=None):
+    """mods_match_overlap_area_reps: area-overlap matching of ImgRep rep_q against ImgRep rep_t (HBM resident); returns (matches,
+    counts).  cap: room for that many matches (default: one per query, which always suffices)."""
+    cap = max(len(rep_q), 1) if cap is None else cap
+    out = np.zeros(max(cap, 1), OVERLAP_AREA_DTYPE)
+    n = C.c_int()
+    counts = OverlapCounts()
+    _check(lib().mods_match_overlap_area_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
+                                              C.byref(counts)))
     return out[:n.value].copy(), counts
 
 

@@ -71,6 +71,10 @@ struct Config {
   // banks go through mods_match_overlap_reps under the ground-truth H and the count is printed as mods.cpp:522-523 does
   int overlap = 0, overlap_oriented = 1;
   double overlap_error = 0.09;
+  // overlapMeasure = linear | area and overlapAreaError (ours): with `area` the banks go through mods_match_overlap_area_reps instead -
+  // intersection over union of the ellipses, greedy one-to-one assignment, the measure published repeatability figures use
+  int overlap_area = 0;
+  double overlap_area_error = 0.4;
   // [zmqDescriptor] (io_mods.cpp:395-407): used when a step asks for the "ZMQ" descriptor instead of RootSIFT
   bool use_zmq = false;
   std::string zmq_port = "tcp://localhost:5555";
@@ -219,6 +223,11 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   if (cfg->overlap != 0 && cfg->overlap != 1) { std::cerr << "[OverlapMatching] doOverlapMatch must be 0 or 1" << std::endl; return 1; }
   if (!std::isfinite(cfg->overlap_error) || !(cfg->overlap_error > 0)) { std::cerr << "[OverlapMatching] overlapError must be a positive number, not " << cfg->overlap_error << std::endl; return 1; }
   if (cfg->overlap_oriented != 0 && cfg->overlap_oriented != 1) { std::cerr << "[OverlapMatching] matchOriented must be 0 or 1" << std::endl; return 1; }
+  const std::string om = ini.Has("OverlapMatching", "overlapMeasure") ? ini.GetString("OverlapMatching", "overlapMeasure", "") : std::string("linear");
+  if (om != "linear" && om != "area") { std::cerr << "[OverlapMatching] overlapMeasure must be linear or area, not " << om << std::endl; return 1; }
+  cfg->overlap_area = om == "area";
+  cfg->overlap_area_error = ini.GetDouble("OverlapMatching", "overlapAreaError", 0.4);
+  if (!(cfg->overlap_area_error > 0 && cfg->overlap_area_error <= 1)) { std::cerr << "[OverlapMatching] overlapAreaError must lie in (0, 1], not " << cfg->overlap_area_error << std::endl; return 1; }
   // [TextOutput], [Computing]
   cfg->time_log = (int)ini.GetInteger("TextOutput", "timeLog", 0);
   cfg->write_keypoints = (int)ini.GetInteger("TextOutput", "writeKeypoints", 1);
@@ -907,7 +916,28 @@ int main(int argc, char **argv) {
   // [OverlapMatching] doOverlapMatch = 1 (mods.cpp:522-523): the banks of every detector under the ground-truth homography, one to one
   if (cfg.overlap && ver_type != 1) std::cerr << "Note: doOverlapMatch needs the ground truth homography (verification type 1), skipped" << std::endl;
   else if (cfg.overlap && multi) std::cerr << "Note: doOverlapMatch is not run with MODS_DEVICES" << std::endl;
-  else if (cfg.overlap) {
+  else if (cfg.overlap && cfg.overlap_area) {   // overlapMeasure = area: intersection over union, greedy one-to-one assignment
+    mods_overlap_area_params op;
+    memset(&op, 0, sizeof(op));
+    for (int i = 0; i < 9; i++) op.H[i] = cfg.pair.ransac.gtH[i];
+    op.max_error = cfg.overlap_area_error; op.one_to_one = 2;
+    op.w1 = img1.w; op.h1 = img1.h; op.w2 = img2.w; op.h2 = img2.h;
+    long n_overlap = 0;
+    std::vector<mods_overlap_counts> oc((size_t)n_det);
+    std::vector<mods_overlap_area_match> om;
+    for (int d = 0; d < n_det; d++) {
+      const int cap = mods_imgrep_count(reps1[d]);
+      om.resize((size_t)std::max(cap, 1));
+      int m = 0;
+      if (mods_match_overlap_area_reps(ctx, reps1[d], reps2[d], &op, om.data(), cap, &m, &oc[d])) return fail("area overlap matching");
+      n_overlap += m;
+    }
+    std::cerr << "Area overlap matches with error < " << cfg.overlap_area_error << std::endl << n_overlap << std::endl;
+    if (cfg.verbose)
+      for (int d = 0; d < n_det; d++)
+        std::cerr << cfg.det_names[d] << ": " << oc[d].n_q_common << " | " << oc[d].n_t_common << " regions in the common area, repeatability "
+                  << oc[d].repeatability << std::endl;
+  } else if (cfg.overlap) {
     mods_overlap_params op;
     memset(&op, 0, sizeof(op));
     for (int i = 0; i < 9; i++) op.H[i] = cfg.pair.ransac.gtH[i];

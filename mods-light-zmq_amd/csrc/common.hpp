@@ -316,6 +316,19 @@ struct mods_ctx {
   mods::Buf<mods_region> o_regs;     // staging of host lists
   mods::PinnedBuf<int> o_count;
   int o_splits = 0;
+  // area-overlap matching (overlap_area.hip), its own buffers: the 48-byte records of both lists (queries first), the error keys
+  // (per train, per query, per listed pair), the integers (common counts, per-train owner, per-query pair, the sweep's block
+  // counts, per split and query the pair count and the list offset; oa_pair: the list's (q, t), its three pixel counts and the
+  // compaction's block counts), the matches, the staging of host lists and (items, common queries, common trains, listed pairs
+  // as two halves of 64 bits); oa_host: the accepted pairs of mode 2
+  mods::Buf<double> oa_rec;
+  mods::Buf<unsigned long long> oa_key;
+  mods::Buf<int> oa_int;
+  mods::Buf<int> oa_pair;            // what is sized by the pair list (its length is known between the two gate sweeps)
+  mods::Buf<mods_overlap_area_match> oa_out;
+  mods::Buf<mods_region> oa_regs;
+  mods::PinnedBuf<int> oa_count;
+  std::vector<mods_overlap_area_match> oa_host;
   // mutual check of the FGINN searches (mutual.hip; mods_ctx_match_mutual), reserved on the first search with a mode set: 16 counters
   // and the candidate lists (q, t, d1, D*) of the matcher's sets; the candidate counts again, pinned
   int mutual_mode = 0;

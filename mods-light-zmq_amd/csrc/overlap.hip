@@ -15,7 +15,7 @@
 // max_error), which cannot change a minimum because the shape term is never negative.  Train splits run in blockIdx.y; each
 // leaves its (E, t) per query in a table of its own and the accept kernel takes their minimum in split order, so no 96-bit
 // atomic is needed.  VALU only, no matrix cores.
-#include "common.hpp"
+#include "overlap_common.hpp"
 #include <cmath>
 
 namespace mods {
@@ -30,19 +30,9 @@ struct OverlapConst {
   int tiles_per_split;    // train tiles a block of the sweep walks (blockIdx.y = split)
 };
 
-// query: px py C11 C12 C21 C22     train: x2 y2 I11 I12 I21 I22
-struct OvRec { double a, b, m11, m12, m21, m22; };
-static_assert(sizeof(OvRec) == 48, "overlap record");
-
 constexpr int O_THREADS = 256;   // queries per block of the sweep, threads of every kernel here
 constexpr int O_TILE = 256;      // trains per LDS tile (12 KB of records)
 constexpr unsigned long long O_NONE = ~0ull;
-
-__device__ __forceinline__ OvRec overlap_nan_rec() {
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  OvRec r; r.a = r.b = r.m11 = r.m12 = r.m21 = r.m22 = nan;
-  return r;
-}
 
 // One list, a thread per region.  cnt[is_train] += the regions of the list that take part (all of them without the area test)
 __global__ __launch_bounds__(O_THREADS) void overlap_pack_kernel(OverlapConst k, const mods_region *__restrict__ reg, int n, int is_train,
@@ -50,37 +40,16 @@ __global__ __launch_bounds__(O_THREADS) void overlap_pack_kernel(OverlapConst k,
   const int i = blockIdx.x * O_THREADS + threadIdx.x;
   bool part = false;
   if (i < n) {
-    const double x = reg[i].x, y = reg[i].y, s = reg[i].s;
-    const double ks = 3.0 * s;
-    const double B11 = ks * reg[i].a11, B12 = ks * reg[i].a12, B21 = ks * reg[i].a21, B22 = ks * reg[i].a22;
+    const OvRec f = overlap_frame(reg[i]);
     OvRec r;
     if (!is_train) {
-      const double *H = k.H;
-      const double X = (H[0] * x + H[1] * y) + H[2];
-      const double Y = (H[3] * x + H[4] * y) + H[5];
-      const double den = (H[6] * x + H[7] * y) + H[8];
-      const double px = X / den, py = Y / den;
-      const double den2 = den * den;
-      const double n1 = X / den2, n2 = Y / den2;
-      const double L11 = H[0] / den - n1 * H[6], L12 = H[1] / den - n1 * H[7];
-      const double L21 = H[3] / den - n2 * H[6], L22 = H[4] / den - n2 * H[7];
-      r.a = px; r.b = py;
-      r.m11 = L11 * B11 + L12 * B21; r.m12 = L11 * B12 + L12 * B22;
-      r.m21 = L21 * B11 + L22 * B21; r.m22 = L21 * B12 + L22 * B22;
-      part = !k.area || (0. < px && px < k.w2 && 0. < py && py < k.h2);
-    } else {
-      const double d = 1.0 / (B11 * B22 - B12 * B21);
-      r.a = x; r.b = y;
-      r.m11 = B22 * d; r.m12 = -(B12 * d); r.m21 = -(B21 * d); r.m22 = B11 * d;
-      part = true;
-      if (k.area) {
-        const double *G = k.Hinv;
-        const double X = (G[0] * x + G[1] * y) + G[2];
-        const double Y = (G[3] * x + G[4] * y) + G[5];
-        const double W = (G[6] * x + G[7] * y) + G[8];
-        const double bx = X / W, by = Y / W;
-        part = 0. < bx && bx < k.w1 && 0. < by && by < k.h1;
-      }
+      r = overlap_query_rec(k.H, f);
+      part = !k.area || overlap_in_image(r.a, r.b, k.w2, k.h2);
+    } else {                                             // x2 y2 I11 I12 I21 I22: the inverse of the frame
+      const double d = 1.0 / (f.m11 * f.m22 - f.m12 * f.m21);
+      r.a = f.a; r.b = f.b;
+      r.m11 = f.m22 * d; r.m12 = -(f.m12 * d); r.m21 = -(f.m21 * d); r.m22 = f.m11 * d;
+      part = !k.area || overlap_maps_into(k.Hinv, f.a, f.b, k.w1, k.h1);
     }
     rec[i] = part ? r : overlap_nan_rec();
   }
