@@ -996,22 +996,24 @@ __device__ void sift_hist_from_patch(const float *s_patch, const float *__restri
   if (tid < 128) {
     const int br = tid >> 5, bc = (tid >> 3) & 3, bo = tid & 7;
     const float *wr = s_w + br * ps, *wc = s_w + bc * ps;
-    int rlo = ps, rhi = 0, clo = ps;
+    int rlo = ps, rhi = 0, clo = ps, chi = 0;
     for (int i = 0; i < ps; i++) {
       if (wr[i] > 0) { rlo = min(rlo, i); rhi = i + 1; }
-      if (wc[i] > 0) clo = min(clo, i);
+      if (wc[i] > 0) { clo = min(clo, i); chi = i + 1; }
     }
-    // fixed 18-pixel window per row (spatial bins span <= 18 pixel columns for ps <= 45): entries past
+    // 18-pixel window per row (spatial bins span <= 18 pixel columns for ps <= 47): entries past
     // the bin's columns carry weight 0 and add +0.0; their loads may run into the next row / the
-    // following LDS words, whose value is irrelevant.  s_wpad: the bin's column weights, zero padded.
+    // following LDS words, whose value is irrelevant.  Larger patches (this form takes ps > 45; a bin spans 19 columns at
+    // ps = 49, 25 at ps = 63) take the bin's own span: every term of the reference's sum, in its order.
     constexpr int CW = 18;
+    const int cw = max(CW, chi - clo);
     double acc = 0.0;
     for (int r = rlo; r < rhi; r++) {
       const float wrr = wr[r];
       const float2 *px = s_px + r * ps + clo;
       const unsigned char *bop = s_bo + r * ps + clo;
 #pragma unroll 6
-      for (int q = 0; q < CW; q++) {
+      for (int q = 0; q < cw; q++) {
         const float2 pv = px[q];
         const int bo0 = bop[q];
         const float wcq = (clo + q < ps) ? wc[clo + q] : 0.f;
@@ -1258,8 +1260,11 @@ constexpr int S2_BINS = 1024;                 // doubles per wave
 __device__ __forceinline__ int s2_bin(int g, int br, int bc) { return (g >> 2) * 64 + br * 16 + (g & 3) * 4 + bc; }   // + bo * 128
 __device__ __forceinline__ int s2_vec(int g, int i) { return (i & 7) * 128 + s2_bin(g, i >> 5, (i >> 3) & 3); }          // vec[i], i = (br*4 + bc)*8 + bo
 
+// float2 slots of a wave's pixel row.  The photometric chunk [SW_R][SW_G] floats aliases the row and is the larger of the two for
+// patch sizes below 32, where the row alone would let the chunk run over the wave's mean / factor / flag words and the next wave's bins
+__host__ __device__ constexpr int s2_row_slots(int ps) { return SW_R * ps + SW_CW + 2 > SW_R * SW_G / 2 ? SW_R * ps + SW_CW + 2 : SW_R * SW_G / 2; }
 static size_t sift_wave2_wave_bytes(int ps) {
-  return sizeof(double) * S2_BINS + sizeof(float2) * ((size_t)SW_R * ps + SW_CW + 2) + sizeof(float) * 3 * SW_R;
+  return sizeof(double) * S2_BINS + sizeof(float2) * (size_t)s2_row_slots(ps) + sizeof(float) * 3 * SW_R;
 }
 static size_t sift_wave2_lds_bytes(int ps) {
   const size_t ppa = ((size_t)ps * ps + 7) & ~(size_t)7;
@@ -1282,10 +1287,10 @@ __global__ __launch_bounds__(64 * S2_WAVES, 3) void sift_wave2_kernel(DescConst 
   float *s_w = s_ot + 2048;                         // [4][ps] spatial weights
   int *s_pref = (int *)(s_w + 4 * ps + 4);          // [n_img + 1] work units before image b; [68]: n_mask
   unsigned short *s_midx = (unsigned short *)(s_pref + 72);
-  unsigned char *wbase = (unsigned char *)(s_midx + ppa) + (size_t)wv * (sizeof(double) * S2_BINS + sizeof(float2) * (SW_R * ps + SW_CW + 2) + sizeof(float) * 3 * SW_R);
+  unsigned char *wbase = (unsigned char *)(s_midx + ppa) + (size_t)wv * (sizeof(double) * S2_BINS + sizeof(float2) * s2_row_slots(ps) + sizeof(float) * 3 * SW_R);
   double *acc = (double *)wbase;
   float2 *pxrow = (float2 *)(acc + S2_BINS);        // [8 * ps + pad]: (mask * |grad|, o) of the current pixel row
-  float *s_mean = (float *)(pxrow + SW_R * ps + SW_CW + 2), *s_fac = s_mean + SW_R;
+  float *s_mean = (float *)(pxrow + s2_row_slots(ps)), *s_fac = s_mean + SW_R;
   int *s_flag = (int *)(s_fac + SW_R);
   float *g = (float *)pxrow;                        // photometric chunk [8][SW_G], dead before the first pixel row is written
   const int rowf = SW_R * ps;

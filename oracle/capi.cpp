@@ -296,6 +296,22 @@ int orc_detect_orientation(const float *img, int w, int h, const orc_region *in,
   detect_orientation(v, o, wrap(img, w, h), mrSize, patchSize, maxAngles, th);
   return from_regions(o, out, max_out);
 }
+// the same with the two modes the entry point above leaves off: flags bit 0 = doHalfSIFT, bit 2 = addUpRight (the bits of
+// orc_detect_describe_ex)
+int orc_detect_orientation_ex(const float *img, int w, int h, const orc_region *in, int n, double mrSize, int patchSize,
+                              int maxAngles, double th, int flags, orc_region *out, int max_out) {
+  std::vector<Region> v, o; to_regions(in, n, v);
+  detect_orientation(v, o, wrap(img, w, h), mrSize, patchSize, maxAngles, th, (flags & 1) != 0, (flags & 4) != 0);
+  return from_regions(o, out, max_out);
+}
+// the fast_extraction branch of DescribeRegions (synth-detection.hpp:232-253) for one region
+void orc_extract_desc_patch_fast(const float *img, int w, int h, const orc_region *r, double mrSize, int patchSize,
+                                 int photoNorm, float *patch_out) {
+  std::vector<Region> v; to_regions(r, 1, v);
+  Img patch(patchSize, patchSize);
+  extract_desc_patch(v[0], wrap(img, w, h), mrSize, patchSize, photoNorm != 0, patch, false, true);
+  std::memcpy(patch_out, patch.d.data(), sizeof(float) * (size_t)patchSize * patchSize);
+}
 int orc_filter_centres_inside(orc_region *r, int n, int w, int h) {
   std::vector<Region> v; to_regions(r, n, v);
   filter_centres_inside(v, w, h);

@@ -275,22 +275,34 @@ def sift_desc(patch, rootsift=True, max_bin=0.2):
     return out
 
 
-def extract_desc_patch(img, region, mrsize=DESC_MRSIZE, ps=DESC_PATCH, photonorm=True):
-    a, p = _f(img)
-    r = np.ascontiguousarray(np.atleast_1d(region)[:1])
-    out = np.empty((ps, ps), np.float32)
-    lib().orc_extract_desc_patch(p, a.shape[1], a.shape[0], r.ctypes.data_as(C.c_void_p), C.c_double(mrsize), ps,
-                                 int(photonorm), out.ctypes.data_as(C.POINTER(C.c_float)))
+def half_rootsift_patch(patch, max_bin=0.2):
+    """HalfRootSIFT of one patch: 64 values, out[64:] = 0"""
+    a, p = _f(patch)
+    out = np.zeros(128, np.uint8)
+    lib().orc_half_rootsift_patch(p, a.shape[0], C.c_double(max_bin), out.ctypes.data_as(C.c_void_p))
     return out
 
 
-def detect_orientation(img, regions, mrsize=ORI_MRSIZE, ps=ORI_PATCH, max_angles=ORI_MAXANG, th=ORI_TH):
+def extract_desc_patch(img, region, mrsize=DESC_MRSIZE, ps=DESC_PATCH, photonorm=True, fast=False):
+    """the patch DescribeRegions hands to the descriptor; fast: its fast_extraction branch"""
+    a, p = _f(img)
+    r = np.ascontiguousarray(np.atleast_1d(region)[:1])
+    out = np.empty((ps, ps), np.float32)
+    fn = lib().orc_extract_desc_patch_fast if fast else lib().orc_extract_desc_patch
+    fn(p, a.shape[1], a.shape[0], r.ctypes.data_as(C.c_void_p), C.c_double(mrsize), ps, int(photonorm), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def detect_orientation(img, regions, mrsize=ORI_MRSIZE, ps=ORI_PATCH, max_angles=ORI_MAXANG, th=ORI_TH, half=False, add_upright=False):
+    """DetectOrientation; half: doHalfSIFT mode, add_upright: the unrotated copy behind a keypoint's oriented ones"""
     a, p = _f(img)
     r = np.ascontiguousarray(regions)
-    out = np.zeros(len(r) + 1, REGION_DTYPE)
-    n = lib().orc_detect_orientation(p, a.shape[1], a.shape[0], r.ctypes.data_as(C.c_void_p), len(r),
-                                     C.c_double(mrsize), ps, max_angles, C.c_double(th),
-                                     out.ctypes.data_as(C.c_void_p), len(out))
+    per_key = (max_angles if max_angles >= 0 else 18) + (1 if add_upright else 0)     # 36 bins hold 18 local maxima at the most
+    out = np.zeros(len(r) * per_key + 1, REGION_DTYPE)
+    n = lib().orc_detect_orientation_ex(p, a.shape[1], a.shape[0], r.ctypes.data_as(C.c_void_p), len(r),
+                                        C.c_double(mrsize), ps, max_angles, C.c_double(th), (1 if half else 0) | (4 if add_upright else 0),
+                                        out.ctypes.data_as(C.c_void_p), len(out))
+    assert n <= len(out)
     return out[:n].copy()
 
 

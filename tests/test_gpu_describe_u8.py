@@ -11,19 +11,20 @@ pytestmark = pytest.mark.gpu
 P2_CLASSES = ((0, 48), (48, 64), (64, 80), (80, 256), (256, 1 << 30))    # lo < P2 <= hi: the three LDS launches, the fused tier's two row counts
 
 
-def _p2(regions):
-    """side of the sampled window of DescribeRegions, blur margin included (region_geom, csrc/sift.hip)"""
-    return 2 * np.ceil(regions["s"] * orc.DESC_MRSIZE).astype(np.int64) + 1 + 2
+def _p2(regions, ps=orc.DESC_PATCH, mrsize=orc.DESC_MRSIZE):
+    """side of the sampled window of DescribeRegions, blur margin included (region_geom, csrc/sift.hip; no function of the patch
+    size ps, which decides only whether the window is blurred or the patch sampled directly: _window_touches)"""
+    return 2 * np.ceil(regions["s"] * mrsize).astype(np.int64) + 1 + 2
 
 
-def _window_touches(regions, w, h):
+def _window_touches(regions, w, h, ps=orc.DESC_PATCH, mrsize=orc.DESC_MRSIZE):
     """interpolateCheckBorders (helpers.cpp:527-549) for the window the description samples: the P2 x P2 window in the region's frame,
     or - regions of at most 0.4 image pixels per patch pixel, which are sampled directly - the patch in the frame times that scale"""
     f32 = np.float32
-    P2 = _p2(regions)
-    scale = (P2 - 2).astype(f32) / f32(orc.DESC_PATCH)
+    P2 = _p2(regions, ps, mrsize)
+    scale = (P2 - 2).astype(f32) / f32(ps)
     direct = scale.astype(np.float64) <= 0.4
-    n = np.where(direct, orc.DESC_PATCH, P2)
+    n = np.where(direct, ps, P2)
     k = np.where(direct, scale, f32(1)).astype(f32)
     fx, fy = regions["x"].astype(f32), regions["y"].astype(f32)
     a11, a12 = regions["a11"].astype(f32) * k, regions["a12"].astype(f32) * k

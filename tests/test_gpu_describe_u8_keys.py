@@ -27,8 +27,15 @@ def _sift_constants():
         assert len(m) == 1, pattern
         return int(m[0])
     k = dict(t_lo=one(r"#define EXTRACT_T_LO (\d+)"), t_mid=one(r"#define EXTRACT_T_MID (\d+)"), small_cap=one(r"constexpr int SMALL_CAP = (\d+);"),
-             fuse_p2=one(r"#define BIG_FUSE_P2_MAX (\d+)"), fuse_kb=one(r"#define BIG_FUSE_KB (\d+)"))
+             fuse_p2=one(r"#define BIG_FUSE_P2_MAX (\d+)"), fuse_kb=one(r"#define BIG_FUSE_KB (\d+)"),
+             fuse_taps=one(r"constexpr int BIG_FUSE_TAPS = (\d+);"), taps_lds=one(r"constexpr int TAPS_LDS = (\d+);"),
+             lds_taps=one(r"const bool lds_tier = have && g\.P2 <= k\.p2_hi && n_tap <= (\d+);"))
+    # the two launch sites that choose between the wave forms and the block-per-region form of the SIFT kernel
+    block = re.findall(r"if \((?:run_sift && )?ps > (\d+)\)", src)
+    assert len(block) == 2 and block[0] == block[1], block
+    k["sift_block_ps"] = int(block[0])
     assert re.search(r"int r = 64;\s*while \(r > 4 && r \* P2 > budget\) r >>= 1;", src), "big_fuse_rows (csrc/sift.hip) no longer reads as the loop this pattern expects: bring _fuse_rows below and this pattern in line with it"
+    assert len(re.findall(r"const int n_tap = [^;]*\(\(int\)\(2\.0 \* 3\.0 \* \(1\.5f \* g\.scale\) \+ 1\.0\)\) \| 1", src)) == 2, "the tap count (csrc/sift.hip) no longer reads as _n_tap below restates it"
     return k
 
 
@@ -40,15 +47,41 @@ def _fuse_rows(P2, kb):
     return r
 
 
-def _boundaries():
+def _n_tap(P2, ps):
+    """taps of the blur of a P2 wide window: ((int)(2.0 * 3.0 * (1.5f * scale) + 1.0)) | 1 with scale = float(P2 - 2) / float(ps)
+    (region_geom and the classification, csrc/sift.hip; cv::GaussianBlur's kernel size for sigma = 1.5f * scale)"""
+    f32 = np.float32
+    scale = f32(P2 - 2) / f32(ps)
+    return int(2.0 * 3.0 * float(f32(1.5) * scale) + 1.0) | 1
+
+
+def _tap_boundaries(ps):
+    """the last (odd) P2 whose blur has at most as many taps as each of the three tap limits of csrc/sift.hip allows: the LDS tier's
+    staged taps, the fused kernel's, the row pass's taps in LDS"""
+    k = _sift_constants()
+    out = []
+    for lim in (k["lds_taps"], k["fuse_taps"], k["taps_lds"]):
+        P2 = 3
+        while _n_tap(P2 + 2, ps) <= lim:
+            P2 += 2
+        out.append(P2)
+    return out
+
+
+def _boundaries(ps=orc.DESC_PATCH):
     """P2 limits between two paths of the extraction, ascending: the direct branch (the largest window DescribeRegions samples
     directly has P2 - 2 <= 0.4 * patch size), the three launches of extract_small_kernel, the row counts of big_fused_kernel, and
-    the limit between the fused kernel and big_sample_kernel."""
+    the limit between the fused kernel and big_sample_kernel.  At small patch sizes the tap limits come to lie among them: the
+    one that sends a window of the LDS tier's sizes to the HBM tier, the one that sends a window of the fused kernel's sizes to the
+    phase kernels (each where it falls below the size limit of the same decision; at the default patch size neither does)."""
     k = _sift_constants()
     f32 = np.float32
-    direct = max(P + 2 for P in range(1, 64, 2) if float(f32(P) / f32(orc.DESC_PATCH)) <= 0.4)
+    direct = max(P + 2 for P in range(1, 64, 2) if float(f32(P) / f32(ps)) <= 0.4)
     out = [direct + 1, k["t_lo"], k["t_mid"], k["small_cap"]]
     out += [P2 for P2 in range(k["small_cap"] + 1, k["fuse_p2"]) if _fuse_rows(P2, k["fuse_kb"]) != _fuse_rows(P2 + 1, k["fuse_kb"])]
+    taps = _tap_boundaries(ps)
+    out += [t for t, size_limit in zip(taps[:2], (k["small_cap"], k["fuse_p2"])) if t < size_limit]
+    out = sorted(set(out))
     out.append(k["fuse_p2"])
     assert out == sorted(set(out)) and len(out) >= 8, out
     return out
@@ -60,9 +93,9 @@ def _sizes_at(boundary):
     return last, last + 2
 
 
-def _s_of(P2):
+def _s_of(P2, mrsize=orc.DESC_MRSIZE):
     """a scale whose description window is P2 wide: P2 = 2 * ceil(s * mrSize) + 3"""
-    return ((P2 - 3) // 2 - 0.5) / orc.DESC_MRSIZE
+    return ((P2 - 3) // 2 - 0.5) / mrsize
 
 
 def _fits(boundary, w, h):
@@ -85,14 +118,15 @@ def _oracle(img, keys):
     return orc.describe_rootsift(img, orc.filter_touch_boundary(orc.detect_orientation(img, regs), w, h))
 
 
-def _border_key(img, base, s, side):
+def _border_key(img, base, s, side, ps=orc.DESC_PATCH, mrsize=orc.DESC_MRSIZE, ori=None):
     """An isotropic key of scale s next to one border of the image (side 0 left, 1 top, 2 right, 3 bottom) whose description window
     reaches over the border while the region passes the border filter: the window is 2 - 3 pixels wider than the filter's box, and
     how far either reaches depends on the orientation found at the place, so the place is searched - with the oracle's orientation
-    and border filter alone - in quarter-pixel steps away from the border."""
+    and border filter alone - in quarter-pixel steps away from the border.  ori: the orientation's mrsize and ps, where not the default."""
     h, w = img.shape
-    half = np.ceil(s * orc.DESC_MRSIZE)
-    d = np.arange(0.9 * half, 1.5 * half + 6, 0.25)
+    half = np.ceil(s * mrsize)
+    # (the border filter's box is DESC_MRSIZE * s wide whatever the description's mrSize: a wider window touches further inside)
+    d = np.arange(0.9 * np.ceil(s * min(mrsize, orc.DESC_MRSIZE)), 1.5 * half + 6, 0.25)
     if side == 0:
         x, y = d, np.full_like(d, h / 2 + 0.5)
     elif side == 1:
@@ -102,22 +136,23 @@ def _border_key(img, base, s, side):
     else:
         x, y = np.full_like(d, w / 2 + 0.5), h - 1 - d
     cand = np.concatenate([_iso_key(base, xi, yi, s) for xi, yi in zip(x, y)])
-    r = orc.filter_touch_boundary(orc.detect_orientation(img, orc.regions_from_keys(cand)), w, h)
-    touch, _ = _window_touches(r, w, h)
+    r = orc.filter_touch_boundary(orc.detect_orientation(img, orc.regions_from_keys(cand), **(ori or {})), w, h)
+    touch, _ = _window_touches(r, w, h, ps, mrsize)
     assert touch.any(), "no place next to border %d where a region of scale %g survives with a touching window" % (side, s)
     i = np.nonzero(touch)[0][0]
     return _iso_key(base, r["x"][i], r["y"][i], s)
 
 
-def _boundary_keys(img, base, boundaries):
-    """both sizes at every limit, once at the image centre and once next to a border (the four borders in turn)"""
+def _boundary_keys(img, base, boundaries, ps=orc.DESC_PATCH, mrsize=orc.DESC_MRSIZE, s_shift=0.0, ori=None):
+    """both sizes at every limit, once at the image centre and once next to a border (the four borders in turn); s_shift (below 0.5)
+    moves s * mrSize inside the interval that gives the same window size"""
     h, w = img.shape
     keys, sizes = [], []
     for b in boundaries:
         for P2 in _sizes_at(b):
-            s = _s_of(P2)
+            s = _s_of(P2, mrsize) + s_shift / mrsize
             keys.append(_iso_key(base, w / 2.0, h / 2.0, s))
-            keys.append(_border_key(img, base, s, len(sizes) % 4))
+            keys.append(_border_key(img, base, s, len(sizes) % 4, ps, mrsize, ori))
             sizes.append(P2)
     return np.concatenate(keys), sizes
 
