@@ -38,7 +38,7 @@ typedef struct mods_hessaff_params {
   int numberOfScales;          /* 3 */
   float initialSigma;          /* 1.6 */
   float threshold;             /* 5.33 */
-  float edgeEigenValueRatio;   /* 10 */
+  float edgeEigenValueRatio;   /* 10; PyramidParams keeps a double: a value no float holds (7.3) reaches the edge test as (double)(float)7.3 */
   int border;                  /* 5 */
   int maxIterations;           /* max_iter = 16 */
   float convergenceThreshold;  /* 0.05 */

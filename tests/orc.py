@@ -410,9 +410,23 @@ def synth_view(img, tilt, phi, zoom=1.0, init_sigma=0.2, do_blur=1):
     return out, g
 
 
+def view_params(params, tilt, zoom):
+    """A copy of `params` with regionsNumber as the detectors see it on a view whose SynthImage fields are (tilt, zoom) = ViewGeom's
+    (|tilt|, zoom): for tilt > 2 or zoom < 0.5 DetectAffineKeypoints takes floor(zoom * N / tilt) (scale-space-detector.cpp:20-21)
+    and DetectMSERs floor(zoom * 2 * N / tilt) (extrema.cpp:201-202); every other view keeps N."""
+    p = HessAffParams.from_buffer_copy(params or HessAffParams.default())
+    if tilt > 2.0 or zoom < 0.5:
+        if p.detectorType == 3:
+            p.regionsNumber = int(np.floor(zoom * 2.0 * p.regionsNumber / tilt))
+        else:
+            p.regionsNumber = int(np.floor(zoom * float(p.regionsNumber) / tilt))
+    return p
+
+
 def detect_describe_view(view, H, orig_w, orig_h, params=None, max_out=1 << 18, half_orientation=False, half_desc=False):
     """One synthesised view through detect/orient/reproject/describe; returns (regions in the original frame,
-    the same regions in the view frame, n_detected) [+ the HalfRootSIFT regions (original frame) with half_desc]."""
+    the same regions in the view frame, n_detected) [+ the HalfRootSIFT regions (original frame) with half_desc].
+    regionsNumber is used as given: a caller with a view's (tilt, zoom) passes view_params(params, tilt, zoom)."""
     params = params or HessAffParams.default()
     a, p = _f(view)
     Hc = np.ascontiguousarray(H, np.float64).ravel()

@@ -257,7 +257,7 @@ def view_schedule(tilts, phi_base, history, scales=(1.0,)):
 
 
 def match_ladder(img1, img2, steps, seed_time=12345, min_matches=15, init_sigma=0.2, ratio=0.8, half_orientation=False,
-                 ratio_half=0.0, detectors=None, groups=None, group_pos=0):
+                 ratio_half=0.0, detectors=None, groups=None, group_pos=0, params=None, view_rule=True):
     """mods.cpp:202-383: steps = [(tilts, phi_base), ...] for one HessianAffine detector, or `detectors` = a list (sorted by
     detector name, the bank's key order) of dicts {params, steps: [(tilts, phi_base) | None per step], ratio, ratio_half,
     half_orientation}.  half_orientation: the steps' descriptor lists name a Half* descriptor (DetectOrientation in doHalfSIFT
@@ -267,10 +267,13 @@ def match_ladder(img1, img2, steps, seed_time=12345, min_matches=15, init_sigma=
     detector (GetCorresponcesVector, :114-148).  A detector dict may carry dist > 0 = DistanceThreshold of RootSIFT.
     groups: per step None or dict(dets=[detector indices in the order named], ratio, ratio_half): grouped matching
     (correspondencebank.cpp:245-285) - the detectors' regions joined into one query / train list per descriptor, the result
-    kept as the bank's "Group" detector at position group_pos of the detector order."""
+    kept as the bank's "Group" detector at position group_pos of the detector order.
+    params: the one detector's parameters when `steps` is given.  Every view is detected with orc.view_params of its (tilt, zoom):
+    regionsNumber cut as DetectAffineKeypoints / DetectMSERs cut it for a strongly tilted or shrunk view (nothing changes in
+    FixedTh mode); view_rule = False leaves it as given, which no detector of the reference does - for tests of the rule."""
     h, w = img1.shape
     if detectors is None:
-        detectors = [dict(params=None, steps=list(steps), ratio=ratio, ratio_half=ratio_half, half_orientation=half_orientation)]
+        detectors = [dict(params=params, steps=list(steps), ratio=ratio, ratio_half=ratio_half, half_orientation=half_orientation)]
     n_steps = max(len(d["steps"]) for d in detectors)
     st = [dict(banks=[[], []], banks_h=[[], []], history=[], tc=None, tch=None) for _ in detectors]
     out = None
@@ -295,7 +298,8 @@ def match_ladder(img1, img2, steps, seed_time=12345, min_matches=15, init_sigma=
                 px, g = orc.synth_view(img, tilt, phi, zoom, sigma, 1)
                 if g.w_new < 16 or g.h_new < 16:
                     return None
-                r = orc.detect_describe_view(px, np.array(g.H), w, h, params=d.get("params"), half_orientation=half_ori, half_desc=want_half)
+                par = orc.view_params(d.get("params"), g.tilt, g.zoom) if view_rule else d.get("params")
+                r = orc.detect_describe_view(px, np.array(g.H), w, h, params=par, half_orientation=half_ori, half_desc=want_half)
                 return (r[0], r[3]) if want_half else (r[0], None)
             for im, img in enumerate((img1, img2)):
                 regs = pmap(one_view, [(img, v) for v in views])      # views are independent; banks keep the view order

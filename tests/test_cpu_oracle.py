@@ -201,3 +201,23 @@ def test_hessian_baumberg_differs_from_smm_and_is_area_preserving():
     assert np.allclose(det, 1.0, atol=1e-4)
     lam = np.array([np.linalg.svd(np.array([[r["a11"], r["a12"]], [r["a21"], r["a22"]]]), compute_uv=False) for r in k1])
     assert (lam[:, 0] / lam[:, 1] < 6.0 * 1.001).all()
+
+
+def test_view_params_scales_regions_number_as_the_detectors_do():
+    """orc.view_params, the oracle side of the view rule (scale-space-detector.cpp:20-21, extrema.cpp:201-202): strict bounds,
+    |tilt| as the SynthImage keeps it, the factor 2 of MSER, a copy; and the MSER oracle's own scaling gives the same list."""
+    p = orc.HessAffParams.default()
+    p.mode, p.regionsNumber = 2, 300
+    views = ((4.0, 1.0), (3.0, 1.0), (1.0, 0.25), (6.0, 0.5), (2.0, 1.0), (1.0, 0.5), (7.0, 1.0), (2.5, 0.4))
+    assert [orc.view_params(p, t, z).regionsNumber for t, z in views] == [75, 100, 75, 25, 300, 300, 42, 48]
+    assert p.regionsNumber == 300
+    g = orc.view_geometry(640, 480, -4.0, 0.0, 1.0, 0.2)
+    assert (g.tilt, g.zoom) == (4.0, 1.0) and orc.view_params(p, g.tilt, g.zoom).regionsNumber == 75
+    assert orc.view_params(None, 4.0, 1.0).mode == 0
+    m = orc.HessAffParams.mser(mode=2, reg_number=60)
+    assert orc.view_params(m, 4.0, 1.0).regionsNumber == 30 and orc.view_params(m, 2.0, 1.0).regionsNumber == 60
+    view, g = orc.synth_view(synth.texture(320, 240, seed=4), 4.0, 0.0, 1.0, 0.2, 1)
+    a = orc.detect_mser_view(view, m, g.tilt, g.zoom)
+    b = orc.detect_hessian_affine(view, orc.view_params(m, g.tilt, g.zoom))
+    assert 0 < len(a) <= 30 and a.tobytes() == b.tobytes()
+    assert len(orc.detect_hessian_affine(view, m)) > len(a)
