@@ -1032,6 +1032,98 @@ int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCo
 int mods_test_sift_pooled(mods_ctx *ctx, const float *patches, int K, int ps, int rootsift, int half, int photoNorm, double maxBinValue,
                           uint8_t *out128);
 
+/* ---- match and region images: an RGB canvas in HBM and a tile rasteriser ---------------------------------------
+ * The reference draws with OpenCV (DrawRegions / DrawMatches, matching.cpp:1046-1574, called at mods.cpp:452-505); OpenCV's
+ * rasterisers are not pinned, so this is a contract of its own, restated in integers and fp64 in tests/draw_ref.py and held to
+ * the byte.  A canvas is h x w x 3 bytes, R G B.  A pixel centre is an integer point.  A colour is 0xRRGGBB.
+ *
+ * Elements.  A draw call takes an ordered list; a later element (or polyline) is drawn over an earlier one; what lies outside the
+ * canvas is not written.  All arithmetic below is in 64-bit integers.
+ *   DISC  (ax, ay) centre, t radius >= 0: covers (x, y) iff (x-ax)^2 + (y-ay)^2 <= t^2.  Solid.  bx, by, group unused.
+ *   LINE  (ax, ay) -> (bx, by), one pixel wide, 8-connected, solid.  The major axis is x when |dx| >= |dy|, else y; the endpoints are
+ *         ordered so that the major delta D >= 0 (the image does not depend on the direction given).  D = 0: the single pixel.
+ *         Else for each major coordinate m in [a_m, b_m] the pixel with minor coordinate a_n + floor((2 (m - a_m) d_n + D) / (2 D)).
+ *   SEG   (ax, ay) -> (bx, by), thickness t (0 .. 255), anti-aliased.  A pixel has 4 x 4 subsamples at offsets -3, -1, 1, 3 eighths of
+ *         a pixel from its centre.  In eighths: p = 8 (x, y) + offset, A = 8 a, B = 8 b, h = 4 t, d = B - A, L2 = d.d, w = p - A,
+ *         s = w.d.  The subsample is inside iff  w.w <= h^2 when L2 = 0 or s <= 0;  |p - B|^2 <= h^2 when s >= L2;
+ *         cross(w, d)^2 <= h^2 L2 otherwise (a capsule with round caps).  A maximal run of consecutive SEG elements with one group
+ *         value and one colour is a polyline: c = the subsamples inside any of its capsules (a joint is not blended twice), and
+ *         the pixel is blended once, per channel out = (dst (16 - c) + col c + 8) >> 4.
+ * Dropping.  An element with a coordinate outside [-32767, 32767] is not drawn, nor is a SEG with |dx| or |dy| > 2047; when one
+ * member of a polyline is dropped the whole polyline is.  n_dropped = the elements not drawn for these reasons: never silent.  An
+ * unknown kind, a negative t, a SEG thicker than 255 or a DISC radius above 32767 is MODS_E_ARG.
+ * The image does not depend on the launch geometry: a workgroup owns a 16 x 16 tile and walks the list in order, no atomics.
+ *
+ * mods_canvas_draw_regions builds the contours of regions [begin, begin + count) of a bank on the device: for k = 0 .. 21 the point
+ *   ( floor((((3.0 s) a11) C[k] + ((3.0 s) a12) S[k]) + x) + dx),  floor((((3.0 s) a21) C[k] + ((3.0 s) a22) S[k]) + y) + dy) )
+ * every product and sum rounded once, in that order, in fp64; a floor outside [-32767, 32767] (or NaN) drops the polyline.  A region
+ * gives 22 points and 21 SEG of one group (its index in the call).  table = MODS_DRAW_TABLE_REGIONS: C[l] = cos(l pi / 10), S[l] =
+ * sin(l pi / 10), l = 0 .. 21 (DrawRegions, matching.cpp:1061-1064); MODS_DRAW_TABLE_MATCHES: the same for l = 0 .. 20 and C[21] =
+ * S[21] = 0, so the contour ends with a spoke to the centre (DrawMatches, :1172-1177).  The host computes the tables with libm
+ * (l * M_PI / 10 as written) and hands them to the kernel by value.  The bank belongs to the canvas's context.
+ * mods_canvas_regions_elems: the element list that call would draw (21 * count elements; a dropped polyline's members have kind
+ * MODS_DRAW_NONE and coordinates 0), for tests.
+ *
+ * mods_draw_matches composes DrawMatches' two images from the verified frames laf14 (n rows x1 y1 a11 a12 a21 a22 s | the same of
+ * image 2) and draws them; mods_draw_matches_elems returns the list of image `which` (0, 1) alone (host only).  colour1 = 0x0000ff,
+ * colour2 = 0x00ff00, epipolar lines 0x00ffff (the reference's BGR scalars on its BGR images).  (int)v and floor(v) saturate: a value
+ * that is NaN or outside [-40000, 40000] becomes 40000, which the drop rule then reports.  Host contours use the MATCHES table and
+ * the expression above.  Every polyline has a group of its own.
+ *   reproject_to_one_image = 0: out1 = white (w1 + w2 + 20) x max(h1, h2) with image 1 at (0, 0) and image 2 at (w1 + 20, 0); out2 =
+ *     white max(w1, w2) x (h1 + h2 + 20) with image 2 at (0, h1 + 20).  With (ox, oy) = image 2's place: unless draw_only_centers,
+ *     per match the contour of region 1 (thickness r1) and of region 2 at (ox, oy) (r2), both colour2; then per match DISC((int)x1,
+ *     (int)y1, r1 + 2) and DISC((int)((double)ox + x2), (int)((double)oy + y2), r1 + 2) in colour1, with draw_epipolar_lines the two
+ *     epipolar LINEs, and the LINE from the second centre to the first in colour2.
+ *     Epipolar lines (matching.cpp:156-169, 1514-1559), M = F: for a point pt = (px, py, 1) and a matrix G, l_j = (px G[j] + py G[3 + j])
+ *     + G[6 + j], xc = (-l_2) / l_0, b = (-l_2) / l_1, k = (0 - b) / (xc - 0).  (k, b) from (M, centre 2) gives the line of image 1,
+ *     from (M transposed, centre 1) that of image 2; line 1 runs (0, (int)b) -> (w1, (int)(k w1 + b)) clipped to image 1's rectangle,
+ *     line 2 (ox, (int)b2 + oy) -> (ox + w2, (int)(k2 w2 + b2) + oy) clipped to image 2's.  Clipping: when all four coordinates are
+ *     within +-32767 the line's pixels (rule above) inside the rectangle are found; none: no element; else the LINE from the first to
+ *     the last of them in major order.  Otherwise the LINE is emitted unclipped and the draw call drops and counts it.
+ *   reproject_to_one_image = 1, M = H (image 1 -> image 2), Hinv = the adjugate times the reciprocal of the determinant:
+ *       d = H0 (H4 H8 - H5 H7) - H1 (H3 H8 - H5 H6) + H2 (H3 H7 - H4 H6), r = 1 / d,
+ *       Hinv = r * [H4 H8 - H5 H7, H2 H7 - H1 H8, H1 H5 - H2 H4 | H5 H6 - H3 H8, H0 H8 - H2 H6, H2 H3 - H0 H5 |
+ *                   H3 H7 - H4 H6, H1 H6 - H0 H7, H0 H4 - H1 H3]     (d = 0 or not finite: MODS_E_ARG);
+ *     out1 = image 1, out2 = image 2.  For out1 (G = Hinv, own = region 1, other = region 2; out2: G = H, roles swapped): unless
+ *     draw_only_centers, per match the own contour in colour1 / r1 and the other's through G in colour2 / r2: with B = [A11 A12 x | A21
+ *     A22 y | 0 0 1] (A = (3.0 s) a), P[r][c] = (G[3r] B[0][c] + G[3r+1] B[1][c]) + G[3r+2] B[2][c], X[r] = (P[r][0] C[k] + P[r][1] S[k]) +
+ *     P[r][2] * 1.0, the point (floor(X[0] / X[2]), floor(X[1] / X[2])).  Then per match DISC(own centre, r1 + 2, colour1), DISC(((int)xa,
+ *     (int)ya), r2, colour2) with xa = ((G0 x + G1 y) + G2) / ((G6 x + G7 y) + G8), ya likewise with G3 G4 G5, of the other centre, and
+ *     the LINE from (xa, ya) to the own centre in colour2. */
+typedef struct mods_canvas mods_canvas;
+enum { MODS_DRAW_NONE = -1, MODS_DRAW_DISC = 0, MODS_DRAW_LINE = 1, MODS_DRAW_SEG = 2 };
+enum { MODS_DRAW_TABLE_REGIONS = 0, MODS_DRAW_TABLE_MATCHES = 1 };
+typedef struct mods_draw_elem { int kind, ax, ay, bx, by, t; unsigned rgb; int group; } mods_draw_elem;
+typedef struct mods_draw_matches_params {
+  int draw_only_centers, reproject_to_one_image, draw_epipolar_lines, r1, r2, pad;
+  double M[9];               /* row-major: H with reproject_to_one_image, F (as mods_pair_result.H holds it) with draw_epipolar_lines */
+} mods_draw_matches_params;
+int mods_canvas_create(mods_ctx *ctx, int w, int h, mods_canvas **out);   /* 1 <= w, h <= 16384; contents undefined until filled */
+void mods_canvas_destroy(mods_canvas *cv);
+int mods_canvas_width(const mods_canvas *cv);
+int mods_canvas_height(const mods_canvas *cv);
+int mods_canvas_fill(mods_canvas *cv, unsigned rgb);
+/* an 8-bit host image of 1 (grey, replicated) or 3 (R G B) channels with its corner at (x0, y0); clipped to the canvas */
+int mods_canvas_blit_u8(mods_canvas *cv, const unsigned char *img, int w, int h, int channels, int x0, int y0);
+/* an fp32 grey device image as (uint8)rint(min(max(px, 0), 255)), NaN as 0 */
+int mods_canvas_blit_f32_dev(mods_canvas *cv, const float *img_dev, int w, int h, int stride, int x0, int y0);
+int mods_canvas_blit_canvas(mods_canvas *cv, const mods_canvas *src, int x0, int y0);
+int mods_canvas_fetch(mods_canvas *cv, unsigned char *rgb_out);           /* h * w * 3 bytes */
+int mods_canvas_draw(mods_canvas *cv, const mods_draw_elem *elems, int n, int *n_dropped);
+int mods_canvas_draw_regions(mods_canvas *cv, const mods_imgrep *rep, int begin, int count, int dx, int dy, int thickness, unsigned rgb,
+                             int table, int *n_dropped);
+int mods_canvas_regions_elems(mods_canvas *cv, const mods_imgrep *rep, int begin, int count, int dx, int dy, int thickness, unsigned rgb,
+                              int table, mods_draw_elem *out, int *n_dropped);
+int mods_draw_matches_elems(int which, int w1, int h1, int w2, int h2, const double *laf14, int n, const mods_draw_matches_params *par,
+                            mods_draw_elem *out, int max_out, int *n_out);
+/* src1, src2: the two images as canvases; *out1, *out2: new canvases (the caller destroys them); n_dropped2[i]: of image i */
+int mods_draw_matches(mods_ctx *ctx, const mods_canvas *src1, const mods_canvas *src2, const double *laf14, int n,
+                      const mods_draw_matches_params *par, mods_canvas **out1, mods_canvas **out2, int *n_dropped2);
+/* The frames of the verified correspondences of the context's last mods_match_pair_dev / ladder / mods_match_verify_reps call, in the
+ * order of its matches_out: up to max rows x y a11 a12 a21 a22 s of region 1, then of region 2; *n = how many there are */
+int mods_ctx_verified_lafs(mods_ctx *ctx, double *laf14, int max, int *n);
+int mods_multi_verified_lafs(mods_multi *m, double *laf14, int max, int *n);
+
 #ifdef __cplusplus
 }
 #endif

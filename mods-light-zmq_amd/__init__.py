@@ -731,8 +731,13 @@ class Context:
         self.last_laf = laf[:n.value].copy()
         return out[:n.value].copy(), u6[:n.value].copy()
 
+    def verified_lafs(self):
+        """mods_ctx_verified_lafs: the frames [n][14] (x y a11 a12 a21 a22 s of region 1, then of region 2) of the verified
+        correspondences of the last pair / ladder / verify call, in the order of its matches"""
+        return _verified_lafs(lib().mods_ctx_verified_lafs, self.h)
 
-TENT_DTYPE = np.dtype([("q", "i4"), ("t", "i4"), ("t_bad", "i4"), ("t_2nd", "i4"), ("d1", "f4"), ("d2", "f4"),
+
+TENT_DTYPE =np.dtype([("q", "i4"), ("t", "i4"), ("t_bad", "i4"), ("t_2nd", "i4"), ("d1", "f4"), ("d2", "f4"),
                        ("d2nd", "f4"), ("pad", "f4"), ("ratio", "f8")])
 
 
@@ -1195,6 +1200,137 @@ def match_overlap_area_reps(ctx, rep_q, rep_t, params, cap=None):
     return out[:n.value].copy(), counts
 
 
+def _verified_lafs(fn, handle):
+    n = C.c_int()
+    _check(fn(handle, None, 0, C.byref(n)))
+    out = np.zeros((max(n.value, 1), 14), np.float64)
+    _check(fn(handle, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return out[:n.value].copy()
+
+
+# ---- match and region images (csrc/draw.hip) --------------------------------------------------------------------------
+DRAW_ELEM_DTYPE = np.dtype([("kind", "i4"), ("ax", "i4"), ("ay", "i4"), ("bx", "i4"), ("by", "i4"), ("t", "i4"), ("rgb", "u4"),
+                            ("group", "i4")])
+DRAW_NONE, DRAW_DISC, DRAW_LINE, DRAW_SEG = -1, 0, 1, 2
+DRAW_TABLE_REGIONS, DRAW_TABLE_MATCHES = 0, 1
+DRAW_COLOUR_REGIONS = 0xA0FFFF           # DrawRegions' Scalar(255, 255, 160), B G R, as 0xRRGGBB
+
+
+class DrawMatchesParams(C.Structure):
+    """mods_draw_matches_params; M: H (row-major, image 1 -> image 2) with reproject_to_one_image, F with draw_epipolar_lines"""
+    _fields_ = [("draw_only_centers", C.c_int), ("reproject_to_one_image", C.c_int), ("draw_epipolar_lines", C.c_int),
+                ("r1", C.c_int), ("r2", C.c_int), ("pad", C.c_int), ("M", C.c_double * 9)]
+
+    @staticmethod
+    def default(M=None, centers_only=0, reproject=0, epipolar=0, r1=5, r2=4):
+        """mods.cpp:461-465: r1 = 5, r2 = 4"""
+        p = DrawMatchesParams(int(centers_only), int(reproject), int(epipolar), int(r1), int(r2), 0)
+        m = np.eye(3) if M is None else np.asarray(M, np.float64)
+        p.M[:] = [float(v) for v in m.reshape(9)]
+        return p
+
+
+class Canvas:
+    """mods_canvas: an RGB8 image [h][w][3] in HBM that the tile rasteriser draws on"""
+
+    def __init__(self, ctx, w, h, handle=None):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        if handle is not None:
+            self.h = handle
+        else:
+            _check(lib().mods_canvas_create(ctx.h, int(w), int(h), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().mods_canvas_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def size(self):
+        """(w, h)"""
+        return lib().mods_canvas_width(self.h), lib().mods_canvas_height(self.h)
+
+    def fill(self, rgb=0xFFFFFF):
+        _check(lib().mods_canvas_fill(self.h, C.c_uint(rgb)))
+        return self
+
+    def blit(self, img_u8, x0=0, y0=0):
+        """an 8-bit host image [h][w] (grey, replicated) or [h][w][3] (R G B) with its corner at (x0, y0)"""
+        a = np.ascontiguousarray(img_u8, np.uint8)
+        ch = 1 if a.ndim == 2 else a.shape[2]
+        _check(lib().mods_canvas_blit_u8(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0], ch, int(x0), int(y0)))
+        return self
+
+    def blit_f32_dev(self, dev_ptr, w, h, stride=None, x0=0, y0=0):
+        """an fp32 grey image in HBM, rounded and clamped to 8 bits"""
+        _check(lib().mods_canvas_blit_f32_dev(self.h, C.c_void_p(dev_ptr), int(w), int(h), int(stride or w), int(x0), int(y0)))
+        return self
+
+    def blit_canvas(self, src, x0=0, y0=0):
+        _check(lib().mods_canvas_blit_canvas(self.h, src.h, int(x0), int(y0)))
+        return self
+
+    def fetch(self):
+        w, h = self.size
+        out = np.empty((h, w, 3), np.uint8)
+        _check(lib().mods_canvas_fetch(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def draw(self, elems):
+        """mods_canvas_draw: the elements (DRAW_ELEM_DTYPE rows) in order; returns n_dropped"""
+        e = np.ascontiguousarray(elems, DRAW_ELEM_DTYPE)
+        nd = C.c_int()
+        _check(lib().mods_canvas_draw(self.h, e.ctypes.data_as(C.c_void_p), len(e), C.byref(nd)))
+        return nd.value
+
+    def draw_regions(self, rep, begin=0, count=None, dx=0, dy=0, thickness=2, rgb=DRAW_COLOUR_REGIONS, table=DRAW_TABLE_REGIONS):
+        """mods_canvas_draw_regions: the contours of regions [begin, begin + count) of ImgRep rep, built on the device; returns
+        n_dropped"""
+        count = len(rep) - begin if count is None else count
+        nd = C.c_int()
+        _check(lib().mods_canvas_draw_regions(self.h, rep.h, int(begin), int(count), int(dx), int(dy), int(thickness), C.c_uint(rgb),
+                                              int(table), C.byref(nd)))
+        return nd.value
+
+    def regions_elems(self, rep, begin=0, count=None, dx=0, dy=0, thickness=2, rgb=DRAW_COLOUR_REGIONS, table=DRAW_TABLE_REGIONS):
+        """mods_canvas_regions_elems: (the element list draw_regions would draw, n_dropped); nothing is drawn"""
+        count = len(rep) - begin if count is None else count
+        out = np.zeros(max(21 * count, 1), DRAW_ELEM_DTYPE)
+        nd = C.c_int()
+        _check(lib().mods_canvas_regions_elems(self.h, rep.h, int(begin), int(count), int(dx), int(dy), int(thickness), C.c_uint(rgb),
+                                               int(table), out.ctypes.data_as(C.c_void_p), C.byref(nd)))
+        return out[:21 * count].copy(), nd.value
+
+
+def draw_matches_elems(which, w1, h1, w2, h2, laf14, params):
+    """mods_draw_matches_elems: the element list of image `which` (0, 1) of draw_matches (host only)"""
+    laf = np.ascontiguousarray(laf14, np.float64).reshape(-1, 14)
+    cap = 64 * len(laf) + 1
+    out = np.zeros(cap, DRAW_ELEM_DTYPE)
+    n = C.c_int()
+    _check(lib().mods_draw_matches_elems(int(which), int(w1), int(h1), int(w2), int(h2), laf.ctypes.data_as(C.c_void_p), len(laf),
+                                         C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+    return out[:n.value].copy()
+
+
+def draw_matches(ctx, src1, src2, laf14, params):
+    """mods_draw_matches: DrawMatches' two images of the verified frames laf14 [n][14] over the source canvases; returns
+    (Canvas out1, Canvas out2, [n_dropped of out1, of out2])"""
+    laf = np.ascontiguousarray(laf14, np.float64).reshape(-1, 14)
+    o1, o2 = C.c_void_p(), C.c_void_p()
+    nd = (C.c_int * 2)()
+    _check(lib().mods_draw_matches(ctx.h, src1.h, src2.h, laf.ctypes.data_as(C.c_void_p), len(laf), C.byref(params), C.byref(o1),
+                                   C.byref(o2), nd))
+    return Canvas(ctx, 0, 0, o1), Canvas(ctx, 0, 0, o2), [nd[0], nd[1]]
+
+
 def match_ladder_dev(ctx, img_ptr, w, h, steps, rep1, rep2, params=None, min_matches=15, max_matches=0, img2_ptr=None, w2=None, h2=None):
     """The step loop of mods.cpp:202-383 on one GPU; img_ptr: [2][h][w] fp32 in HBM (or two separate images)."""
     if img2_ptr is None:
@@ -1302,6 +1438,10 @@ class Multi:
         if n:
             _check(lib().mods_imgrep_fetch(hnd, 0, n, out.ctypes.data_as(C.c_void_p)))
         return out[:n].copy()
+
+    def verified_lafs(self):
+        """mods_multi_verified_lafs: the frames [n][14] of the last run's verified correspondences (its joint list)"""
+        return _verified_lafs(lib().mods_multi_verified_lafs, self.h)
 
     def close(self):
         if self.h:

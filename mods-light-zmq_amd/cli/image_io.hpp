@@ -1,4 +1,5 @@
-// Image input of the mods CLI: PNG (libpng), JPEG (libjpeg) and binary PGM/PPM, to a grey float image.
+// Image input of the mods CLI: PNG (libpng), JPEG (libjpeg) and binary PGM/PPM, to a grey float image (the decoded bytes are kept
+// next to it), and PNG output of an RGB image.
 //
 // Reference behaviour: cv::imread (mods.cpp:116-118).  With [Computing] LoadColor=1 a colour file stays
 // colour and GenerateSynthImageCorr averages it, (B + G + R) / 3.0 on float planes (synth-detection.cpp:343-354): a cv::MatExpr
@@ -19,7 +20,9 @@
 
 namespace modscli {
 
-struct GreyImage { int w = 0, h = 0; std::vector<float> px; };
+// px: the grey float image the detectors see; u8: the decoded bytes, [h][w][ch] with ch = 3 (R G B) for a file decoded as colour
+// and 1 otherwise - the surface the match and region images are drawn on
+struct GreyImage { int w = 0, h = 0; std::vector<float> px; int ch = 1; std::vector<unsigned char> u8; };
 
 static inline float grey_of(const unsigned char *rgb, bool average) {
   if (average) {
@@ -62,6 +65,7 @@ static bool read_pnm(const std::string &fn, bool average, GreyImage *out, std::s
     if (ch == 1) out->px[i] = (float)buf[i];
     else out->px[i] = grey_of(&buf[3 * i], average);
   }
+  out->ch = ch; out->u8 = std::move(buf);
   return true;
 }
 
@@ -81,6 +85,7 @@ static bool read_png(const std::string &fn, bool average, GreyImage *out, std::s
     if (!colour) out->px[i] = (float)buf[i];
     else out->px[i] = grey_of(&buf[3 * i], average);
   }
+  out->ch = colour ? 3 : 1; out->u8 = std::move(buf);
   return true;
 }
 
@@ -95,6 +100,7 @@ static bool read_jpeg(const std::string &fn, bool average, GreyImage *out, std::
   if (mods_jpeg_read(fn.c_str(), average ? 1 : 0, &buf, &w, &h, &ch, msg)) { *err = msg; return false; }
   out->w = w; out->h = h; out->px.resize((size_t)w * h);
   for (size_t i = 0; i < (size_t)w * h; i++) out->px[i] = ch == 1 ? (float)buf[i] : grey_of(&buf[3 * i], average);
+  out->ch = ch == 1 ? 1 : 3; out->u8.assign(buf, buf + (size_t)w * h * out->ch);
   mods_jpeg_free(buf);
   return true;
 }
@@ -111,6 +117,16 @@ static bool read_image(const std::string &fn, bool average, GreyImage *out, std:
   if (n >= 2 && sig[0] == 0xFF && sig[1] == 0xD8) return read_jpeg(fn, average, out, err);
   *err = fn + ": unknown image format (PNG, JPEG, binary PGM/PPM supported)";
   return false;
+}
+
+// an 8-bit R G B image [h][w][3] as a PNG file (libpng's simplified API)
+static bool write_png_rgb(const std::string &fn, const unsigned char *rgb, int w, int h, std::string *err) {
+  png_image img;
+  memset(&img, 0, sizeof(img));
+  img.version = PNG_IMAGE_VERSION;
+  img.width = (png_uint_32)w; img.height = (png_uint_32)h; img.format = PNG_FORMAT_RGB;
+  if (!png_image_write_to_file(&img, fn.c_str(), 0, rgb, 0, nullptr)) { *err = fn + ": " + img.message; return false; }
+  return true;
 }
 
 }  // namespace modscli

@@ -15,7 +15,8 @@
 //                      keypoint files (imagerepresentation.cpp:198-204, 1219-1255), H/F file (matching.cpp:2681-2686),
 //                      time.log (io_mods.cpp:67-99, mods.cpp:528-540); exit code 0 / 1
 // Detectors: HessianAffine, DoG, HarrisAffine (one scale-space detector, three responses) and MSER; ORB / FAST / ... steps of an
-// iterations file are skipped with a warning, match images (out1/out2) are not drawn.  Pre-extracted input
+// iterations file are skipped with a warning.  Match and region images (out1 / out2, mods.cpp:452-505) are drawn on the GPU when
+// [ImageOutput] writeImages / drawDetectedRegions ask for them (mods_draw_matches, mods_canvas_draw_regions).  Pre-extracted input
 // (read_pre_extracted = 1) is read from .npz or text keypoint files.  The vector matcher is always the exact (linear) search;
 // external (ZMQ) descriptor / AffNet / OriNet daemons are used when the configuration asks for them.
 #include "../../include/mods_hip.h"
@@ -87,6 +88,9 @@ struct Config {
   int aff_ps = 32, ori_ps = 32;
   // weights=FILE.npz in [AffNet] / [OriNet] / [zmqDescriptor]: the network runs in-process (mods_net_*), no daemon, no port
   std::string aff_weights, ori_weights, zmq_weights;
+  // [ImageOutput] (io_mods.cpp:647-652).  writeImages absent means 0 here (the reference: 1): a configuration without the section
+  // runs as it always did; the other keys keep the reference's defaults
+  int write_images = 0, draw_only_centers = 1, draw_reprojected = 1, draw_epipolar = 0, draw_regions = 0;
 };
 
 int read_config(const std::string &config_fn, const std::string &iters_fn, int ver_type, Config *cfg) {
@@ -235,6 +239,11 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->output_h = (int)ini.GetInteger("TextOutput", "outputEstimatedHorF", 0);
   if (ini.GetInteger("TextOutput", "outputAllTentatives", 0)) std::cerr << "Warning: outputAllTentatives is not supported, only verified matches are written" << std::endl;
   cfg->load_color = (int)ini.GetInteger("Computing", "LoadColor", 1);
+  cfg->write_images = (int)ini.GetInteger("ImageOutput", "writeImages", 0);
+  cfg->draw_only_centers = (int)ini.GetInteger("ImageOutput", "drawOnlyCenters", 1);
+  cfg->draw_reprojected = (int)ini.GetInteger("ImageOutput", "drawReprojected", 1);
+  cfg->draw_epipolar = (int)ini.GetInteger("ImageOutput", "drawEpipolarLines", 0);
+  cfg->draw_regions = ini.GetBoolean("ImageOutput", "drawDetectedRegions", false) ? 1 : 0;
   cfg->do_clahe = (int)ini.GetInteger("Matching", "doCLAHE", 0);
   cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
   if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
@@ -413,7 +422,7 @@ int usage() {
             << " ************************************************************************** " << std::endl
             << "Usage: mods img1 img2 out1 out2 k1 k2 matchings log [logOnly=1] [ver_type=0] [H/F file] [config.ini] [iters.ini]" << std::endl
             << "  img1, img2   PNG or binary PGM/PPM" << std::endl
-            << "  out1, out2   accepted for compatibility (match images are not drawn)" << std::endl
+            << "  out1, out2   match images (PNG), written with logOnly=0 when [ImageOutput] writeImages = 1" << std::endl
             << "  k1, k2       keypoint + descriptor files (text)" << std::endl
             << "  matchings    verified correspondences, x1 y1 x2 y2 per line" << std::endl
             << "  log          one line: time matches tentatives inlier% regions1 regions2 steps" << std::endl
@@ -425,6 +434,46 @@ bool load_grey(const std::string &fn, int load_color, GreyImage *img) {
   std::string err;
   if (!modscli::read_image(fn, load_color != 0, img, &err)) { std::cerr << err << std::endl; return false; }
   return true;
+}
+
+bool save_canvas(mods_canvas *cv, const std::string &fn) {
+  std::vector<unsigned char> rgb((size_t)mods_canvas_width(cv) * mods_canvas_height(cv) * 3);
+  if (mods_canvas_fetch(cv, rgb.data())) { std::cerr << "mods: " << fn << ": " << mods_last_error() << std::endl; return false; }
+  std::string err;
+  if (!modscli::write_png_rgb(fn, rgb.data(), mods_canvas_width(cv), mods_canvas_height(cv), &err)) { std::cerr << err << std::endl; return false; }
+  return true;
+}
+
+// The images of mods.cpp:452-505 over the decoded 8-bit images.  `regions`: the contours of the accumulated banks (one per described
+// region; the reference shows its unoriented list, which is not kept here) go under the matches.  fn1 / fn2 empty: no match images
+bool draw_outputs(mods_ctx *ctx, const GreyImage &img1, const GreyImage &img2, const std::vector<mods_imgrep *> &reps1,
+                  const std::vector<mods_imgrep *> &reps2, bool regions, int region_thickness, bool with_matches, const std::vector<double> &laf,
+                  const mods_draw_matches_params &par, const std::string &fn1, const std::string &fn2, bool verbose) {
+  mods_canvas *src[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
+  const GreyImage *img[2] = {&img1, &img2};
+  const std::vector<mods_imgrep *> *reps[2] = {&reps1, &reps2};
+  bool ok = true;
+  int dropped = 0;
+  for (int i = 0; i < 2 && ok; i++) {
+    ok = !mods_canvas_create(ctx, img[i]->w, img[i]->h, &src[i]) && !mods_canvas_blit_u8(src[i], img[i]->u8.data(), img[i]->w, img[i]->h, img[i]->ch, 0, 0);
+    if (regions)
+      for (size_t d = 0; d < reps[i]->size() && ok; d++) {
+        int nd = 0;
+        ok = !mods_canvas_draw_regions(src[i], (*reps[i])[d], 0, mods_imgrep_count((*reps[i])[d]), 0, 0, region_thickness, 0xa0ffffu,
+                                       MODS_DRAW_TABLE_REGIONS, &nd);
+        dropped += nd;
+      }
+  }
+  if (ok && with_matches) {
+    int nd[2] = {0, 0};
+    ok = !mods_draw_matches(ctx, src[0], src[1], laf.data(), (int)(laf.size() / 14), &par, &out[0], &out[1], nd);
+    dropped += nd[0] + nd[1];
+  }
+  if (!ok) std::cerr << "mods: drawing: " << mods_last_error() << std::endl;
+  if (ok) ok = save_canvas(with_matches ? out[0] : src[0], fn1) && save_canvas(with_matches ? out[1] : src[1], fn2);
+  if (ok && dropped && verbose) std::cerr << dropped << " drawing elements outside the coordinate range were left out" << std::endl;
+  for (int i = 0; i < 2; i++) { mods_canvas_destroy(src[i]); mods_canvas_destroy(out[i]); }
+  return ok;
 }
 
 // SaveRegions, imagerepresentation.cpp:1219-1255: the detectors in name order (the region map's key order), one descriptor list each
@@ -898,6 +947,45 @@ int main(int argc, char **argv) {
       else write_regions(k1_fn, reps1, cfg.det_names, cfg.use_zmq ? "ZMQ" : "RootSIFT");
       if (ends_with(k2_fn, ".npz")) write_regions_npz(k2_fn, reps2);
       else write_regions(k2_fn, reps2, cfg.det_names, cfg.use_zmq ? "ZMQ" : "RootSIFT");
+    }
+    if (cfg.write_images || cfg.draw_regions) {   // mods.cpp:452-505, over the verified list (not the guided one) and the banks
+      const std::string out1_fn = argv[3], out2_fn = argv[4];
+      std::vector<double> laf((size_t)14 * (size_t)std::max(res.n_inliers, 1));
+      int n_laf = 0;
+      if (multi ? mods_multi_verified_lafs(multi, laf.data(), res.n_inliers, &n_laf) : mods_ctx_verified_lafs(ctx, laf.data(), res.n_inliers, &n_laf))
+        return fail("verified frames");
+      laf.resize((size_t)14 * (size_t)std::min(n_laf, std::max(res.n_inliers, 0)));
+      mods_draw_matches_params dp;
+      memset(&dp, 0, sizeof(dp));
+      dp.draw_only_centers = cfg.draw_only_centers;
+      dp.reproject_to_one_image = !cfg.pair.ransac.useF && cfg.draw_reprojected;
+      dp.draw_epipolar_lines = cfg.pair.ransac.useF && cfg.draw_epipolar;
+      for (int i = 0; i < 9; i++) dp.M[i] = res.H[i];
+      {   // without a usable model (no verified match: H is all -1, singular) the centres are drawn side by side
+        const double *H = res.H;
+        const double det = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
+        if (dp.reproject_to_one_image && (det == 0. || !std::isfinite(det))) dp.reproject_to_one_image = 0;
+      }
+      if (const char *ff = getenv("MODS_DRAW_FRAMES")) {   // what the images are drawn from, to full precision: the model, then the frames
+        std::ofstream fr(ff);
+        fr << std::setprecision(17);
+        for (int i = 0; i < 9; i++) fr << dp.M[i] << (i == 8 ? "\n" : " ");
+        for (size_t i = 0; i < laf.size(); i++) fr << laf[i] << (i % 14 == 13 ? "\n" : " ");
+      }
+      if (cfg.write_images) {
+        std::cerr << " Writing images with matches...";
+        dp.r1 = 5; dp.r2 = 4;
+        if (!draw_outputs(ctx, img1, img2, reps1, reps2, false, 0, true, laf, dp, out1_fn, out2_fn, cfg.verbose != 0)) return 1;
+        std::cerr << " done" << std::endl;
+      }
+      if (cfg.draw_regions && multi) std::cerr << "Note: drawDetectedRegions is not run with MODS_DEVICES (the banks live in the devices' own contexts)" << std::endl;
+      else if (cfg.draw_regions) {
+        std::cerr << " Writing image with detected regions...";
+        dp.r1 = 3; dp.r2 = 2;
+        if (!draw_outputs(ctx, img1, img2, reps1, reps2, true, 2, false, laf, dp, out1_fn + "_reg.png", out2_fn + "_reg.png", cfg.verbose != 0)) return 1;
+        if (!draw_outputs(ctx, img1, img2, reps1, reps2, true, 1, true, laf, dp, out1_fn + ".png", out2_fn + ".png", cfg.verbose != 0)) return 1;
+        std::cerr << " done" << std::endl;
+      }
     }
   }
   std::cerr << "Image1: regions descriptors | Image2: regions descriptors " << std::endl;

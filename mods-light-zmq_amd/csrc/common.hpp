@@ -296,6 +296,7 @@ struct mods_ctx {
   mods::Buf<char> dd_buf; int dd_jobs = 0;   // duplicate filter on the device (dedup.hip): per list of a batch sorted coordinates, ranks, near lists
   mods::Buf<char> m_tent2;           // the filtered packed list of the last search (single-pair path)
   mods::TentList h_list;             // host copy for the sequential stages
+  int h_verified = 0;                // rows at the head of h_list that the last pair / ladder / verify call verified (mods_ctx_verified_lafs)
   std::vector<unsigned char> h_mask;
   // guided matching (guided.hip), its own buffers: gate records and dense descriptor rows of both lists (queries first), the
   // per-query (nearest, inconsistent second) and per-train keys, accept flags + block counts, the packed result and its length

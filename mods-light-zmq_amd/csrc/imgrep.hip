@@ -234,6 +234,7 @@ static int match_into(mods_ctx *c, mods_imgrep *q, mods_imgrep *t, double ratio,
 // detectors in the (name-sorted) order the caller listed them.  lists[desc][det], desc 0 = RootSIFT, 1 = HalfRootSIFT.
 static void gather_tentatives(mods_ctx *c, const std::vector<TentList> lists[2]) {
   c->h_list.clear();
+  c->h_verified = 0;
   for (int desc = 1; desc >= 0; desc--)
     for (const TentList &l : lists[desc]) c->h_list.append(l);
 }
@@ -569,6 +570,7 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
     curr_matches = stop_count(par, res);
     res->steps_done = step + 1;
   }
+  c->h_verified = res->n_inliers;
   c->h_list.copy_matches(res->n_inliers, matches_out, max_matches);   // the verification left the verified rows first
   return MODS_OK;
 }
@@ -599,6 +601,7 @@ int mods_match_verify_reps(mods_ctx *c, mods_imgrep *rep1, mods_imgrep *rep2, do
   const int rc = match_verify_banks(c, rep1, rep2, fginn_ratio, par, res);
   if (rc) return rc;
   res->steps_done = 1;
+  c->h_verified = res->n_inliers;
   c->h_list.copy_matches(res->n_inliers, matches_out, max_matches);   // the verification left the verified rows first
   return MODS_OK;
 }

@@ -46,6 +46,7 @@ struct mods_multi {
   int rep_cap = 0;
   size_t img_px = 0;                  // pixels the image buffer of a device holds (both images together)
   int side = 0;                       // side of the contexts' square canvas (>= the diagonal of the images given at creation)
+  std::vector<double> verified_laf;   // the frames of the last run's verified correspondences (mods_multi_verified_lafs)
 };
 
 namespace {
@@ -238,6 +239,7 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
   auto slot_of = [&](int d) { return groups && d >= group_pos ? d + 1 : d; };
   int curr_matches = 0;
   TentList joint;
+  m->verified_laf.clear();
   for (int step = 0; step < n_steps && curr_matches < min_matches; step++) {
     // ---- the step's view jobs in canonical order: detector, image, view (the order mods_match_ladder_groups_dev appends in)
     std::vector<Job> jobs;
@@ -428,6 +430,8 @@ int mods_match_ladder_groups_multi(mods_multi *m, const float *img1_host, int w1
     res->steps_done = step + 1;
   }
   joint.copy_matches(res->n_inliers, matches_out, max_matches);
+  const size_t n_ver = std::min((size_t)std::max(res->n_inliers, 0), joint.size());
+  m->verified_laf.assign(joint.laf.begin(), joint.laf.begin() + 14 * n_ver);
   return MODS_OK;
 }
 
@@ -438,6 +442,15 @@ int mods_match_ladder_multi(mods_multi *m, const float *img1_host, int w1, int h
   if (!par) { set_error("match_ladder_multi: null argument"); return MODS_E_ARG; }
   return mods_match_ladder_groups_multi(m, img1_host, w1, h1, img2_host, w2, h2, steps, &par->det, nullptr, 0, n_steps, 1, min_matches, par, res,
                                         matches_out, max_matches);
+}
+
+int mods_multi_verified_lafs(mods_multi *m, double *laf14, int max, int *n) {
+  if (!m || !n || max < 0 || (max > 0 && !laf14)) { set_error("multi_verified_lafs: null argument"); return MODS_E_ARG; }
+  const int have = (int)(m->verified_laf.size() / 14);
+  *n = have;
+  const int k = std::min(have, max);
+  if (k > 0) memcpy(laf14, m->verified_laf.data(), sizeof(double) * 14 * (size_t)k);
+  return MODS_OK;
 }
 
 }  // extern "C"

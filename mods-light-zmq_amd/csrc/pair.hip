@@ -508,9 +508,12 @@ int mods_verify_tentatives_ex(int device, const mods_pair_params *par, mods_tent
 int mods_match_pair_dev(mods_ctx *c, const float *img_dev, int w, int h, int stride, const mods_pair_params *par,
                         mods_pair_result *res, double *matches_out, int max_matches) {
   if (!c) { set_error("match_pair: null context"); return MODS_E_ARG; }
-  const int rc = pair_gpu_stage(c, img_dev, w, h, stride, par, res, &c->h_list);
+  c->h_verified = 0;
+  int rc = pair_gpu_stage(c, img_dev, w, h, stride, par, res, &c->h_list);
   if (rc) return rc;
-  return pair_verify_stage(c->device, par, res, &c->h_list, matches_out, max_matches, w, h);
+  rc = pair_verify_stage(c->device, par, res, &c->h_list, matches_out, max_matches, w, h);
+  if (!rc) c->h_verified = res->n_inliers;
+  return rc;
 }
 
 }  // extern "C"
