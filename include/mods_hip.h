@@ -141,6 +141,8 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_OVERLAP,      /* an overlap search (mods_match_overlap[_reps]): pack, the sweep, accept, compaction and emit */
        MODS_STAGE_OVERLAP_AREA, /* an area-overlap search (mods_match_overlap_area[_reps]): pack, both gate sweeps, the lattice walk,
                                  * accept, compaction and emit - in two scopes, the host reads the length of the pair list between them */
+       MODS_STAGE_LOCAL_AFFINE, /* the local affine consistency filter (mods_filter_local_affine, mods_ctx_local_affine): prep, both sweeps,
+                                   keep and compaction */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -1000,6 +1002,74 @@ int mods_match_overlap_area_reps(mods_ctx *ctx, const mods_imgrep *q, const mods
 int mods_ctx_match_mutual(mods_ctx *ctx, int mode);
 int mods_match_mutual_counts(mods_ctx *ctx, int *n_forward, int *n_kept);
 int mods_pipeline_match_mutual(mods_pipeline *p, int mode);
+
+/* ---- local affine consistency of neighbouring tentatives ----------------------------------------------
+ * No counterpart in the reference, which uses the local affine frames of a tentative only in the LAF checks on RANSAC's result.
+ * A correspondence of two affine-covariant regions predicts where its neighbours land, T = (s2 A2) (s1 A1)^-1; true
+ * correspondences on a locally smooth surface confirm each other's predictions, wrong ones are confirmed by nobody (Schmid and
+ * Mohr, PAMI 1997; Cavalli et al., AdaLAM, ECCV 2020).  csrc/local_affine.hip; restated in tests/local_affine_ref.py.  Off by default:
+ * with it off every entry point launches what it launches without this section.  The defaults come from a CPU prototype on
+ * synthetic homography scenes; the radius was then raised from 100 to 160 after graf1 / graf6 (profiles/local_affine_timing.txt): a
+ * list must be dense enough for a true tentative to have minSupport true neighbours inside the radius.
+ *
+ * Input: laf[n][14] = x1 y1 a11 a12 a21 a22 s1 | x2 y2 b11 b12 b21 b22 s2 per tentative, as mods_match_fginn writes it.  All arithmetic
+ * is fp64, one IEEE operation per written operation in the written order, no contraction; comparisons are written so that NaN fails.
+ *   per tentative i:
+ *     m00=s1*a11  m01=s1*a12  m10=s1*a21  m11=s1*a22        n00=s2*b11  n01=s2*b12  n10=s2*b21  n11=s2*b22
+ *     det = m00*m11 - m01*m10
+ *     i00 = m11/det   i01 = (-m01)/det   i10 = (-m10)/det   i11 = m00/det
+ *     t00 = n00*i00 + n01*i10   t01 = n00*i01 + n01*i11   t10 = n10*i00 + n11*i10   t11 = n10*i01 + n11*i11
+ *     dT  = t00*t11 - t01*t10
+ *     valid_i = t00, t01, t10, t11, dT all finite and dT != 0
+ *   per ordered pair (i, j), j != i, with R2=radius*radius, D2=minDist*minDist, A2=absTol*absTol, L2=relTol*relTol:
+ *     dx = x1_j - x1_i   dy = y1_j - y1_i   r2 = dx*dx + dy*dy
+ *     gx = x2_j - x2_i   gy = y2_j - y2_i   q2 = gx*gx + gy*gy
+ *     nb(i,j) = r2 <= R2 && r2 >= D2 && q2 >= D2
+ *     mx = t00_i*dx + t01_i*dy   my = t10_i*dx + t11_i*dy
+ *     ex = gx - mx   ey = gy - my   e2 = ex*ex + ey*ey   m2 = mx*mx + my*my
+ *     ok(i,j) = nb(i,j) && valid_i && e2 <= A2 + L2*m2
+ *               && (areaTol == 0 || (valid_j && dT_i*dT_j > 0 && min(|dT_i|,|dT_j|)*areaTol >= max(|dT_i|,|dT_j|)))
+ *   per tentative, as int32:
+ *     neighbours_i = #{j : nb(i,j)}     support_i = #{j : ok(i,j)}     strong_i = support_i >= minSupport
+ *     backed_j     = #{i : strong_i && ok(i,j)}
+ *     keep_i = strong_i || (rescue && backed_i > 0) || (keepSparse && neighbours_i < minSupport)
+ * Survivors stay in list order; every byte of mods_tentative, u6 and laf stays as it came in.  All outputs are integers and
+ * booleans: the result does not depend on launch geometry, on the grouping of lists or on the order of the traversal.
+ *
+ * MODS_E_ARG with a mods_last_error text starting "local_affine: ", before any device call and before the context is looked at: null
+ * parameters; radius not finite or <= 0; minDist, absTol, relTol or areaTol negative or NaN; minDist > radius; 0 < areaTol < 1;
+ * minSupport < 1; rescue or keepSparse outside 0 / 1; n < 0; then a null ctx, n_out or (n > 0) list pointer.
+ *
+ * mods_filter_local_affine: host lists in and out, compacted in place as mods_duplicate_filter_gpu does; keep_out[n] (bytes 0 / 1),
+ * neighbours_out[n], support_out[n], backed_out[n] are optional and indexed by input position.  n = 0 succeeds with no launch.  A
+ * list of any length: the context's scratch grows to it.  One host wait before the final copy of the survivors.
+ * mods_ctx_local_affine: a parameter set switches the filter on for the context, NULL switches it off.  While it is on, the list that
+ * goes to the verification is filtered: with doBeforeRANSAC = 1 after DuplicateFiltering - wherever that ran, also where the device
+ * filter hands the list to the host filter - otherwise directly after the search; in mods_match_pair_dev, mods_match_verify_reps,
+ * the single-GPU ladder entry points (every step) and a pipeline's batches (the lists of a batch in one grouped set of launches),
+ * also in ground-truth mode.  n_unique in their results is the count after the filter, n_tentatives is unchanged.
+ * mods_verify_tentatives*, which take no context, are untouched; the multi-GPU ladder (mods_match_ladder_multi) has no switch and is
+ * unfiltered, as it is unchecked by the mutual check.
+ * mods_local_affine_counts: the length of the last list the filter saw on the context and what it kept.
+ * mods_pipeline_local_affine: every GPU worker's context, before the first submit - later: MODS_E_ARG.
+ * mods_local_affine_grid: the rows of a sweep block and the columns of an LDS tile (for tests at the tile boundaries). */
+typedef struct mods_local_affine_params {
+  double radius;     /* 160  px in image 1: j is a neighbour of i when minDist^2 <= |x1_j - x1_i|^2 <= radius^2 ...      */
+  double minDist;    /* 3    ... and |x2_j - x2_i|^2 >= minDist^2 (several orientations / views of one region don't vote) */
+  double absTol;     /* 4    px */
+  double relTol;     /* 0.2  of the length of the mapped offset */
+  double areaTol;    /* 2    largest ratio of |det T_i|, |det T_j|; 0: no test */
+  int minSupport;    /* 3 */
+  int rescue;        /* 1: also keep what a strong seed confirms */
+  int keepSparse;    /* 1: keep tentatives with fewer than minSupport neighbours (cannot be judged) */
+} mods_local_affine_params;
+void mods_local_affine_defaults(mods_local_affine_params *par);
+int mods_filter_local_affine(mods_ctx *ctx, mods_tentative *tent, double *u6, double *laf, int n, const mods_local_affine_params *par,
+                             int *n_out, unsigned char *keep_out, int *neighbours_out, int *support_out, int *backed_out);
+int mods_ctx_local_affine(mods_ctx *ctx, const mods_local_affine_params *par_or_null);
+int mods_local_affine_counts(mods_ctx *ctx, int *n_in, int *n_kept);
+int mods_pipeline_local_affine(mods_pipeline *p, const mods_local_affine_params *par_or_null);
+void mods_local_affine_grid(int *rows, int *tile);
 
 /* ---- domain-size pooling of the SIFT descriptor (DSP-SIFT) -------------------------------------------
  * Dong and Soatto, "Domain-size pooling in local descriptors: DSP-SIFT", CVPR 2015.  The reference reads [SIFTDescriptor] numScales /

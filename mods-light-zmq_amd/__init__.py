@@ -19,6 +19,13 @@ MODS_OK = 0
 STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "orient", "describe", "match",
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
+# MODS_STAGE_* added after that list was pinned by its users: their indices follow it
+STAGES_LATER = ["local_affine"]
+
+
+def stage_index(name):
+    """MODS_STAGE_* of a stage name"""
+    return STAGES.index(name) if name in STAGES else len(STAGES) + STAGES_LATER.index(name)
 
 
 class ModsError(RuntimeError):
@@ -318,12 +325,12 @@ class Context:
     def timing_enable(self, stages):
         mask = 0
         for s in stages:
-            mask |= 1 << STAGES.index(s)
+            mask |= 1 << stage_index(s)
         _check(lib().mods_ctx_timing_enable(self.h, mask))
 
     def timing_read(self, stage):
         ms, n, by = C.c_double(), C.c_int(), C.c_double()
-        _check(lib().mods_ctx_timing_read(self.h, STAGES.index(stage), C.byref(ms), C.byref(n), C.byref(by)))
+        _check(lib().mods_ctx_timing_read(self.h, stage_index(stage), C.byref(ms), C.byref(n), C.byref(by)))
         return ms.value, n.value, by.value
 
     def baumberg_stats_enable(self, on=True):
@@ -491,6 +498,22 @@ class Context:
     def set_match_mutual(self, mode):
         """mods_ctx_match_mutual: 0 off, 1 every FGINN tentative must be its train's nearest query, 2 and pass the ratio test backwards"""
         _check(lib().mods_ctx_match_mutual(self.h, int(mode)))
+
+    def set_local_affine(self, params=None):
+        """mods_ctx_local_affine: a LocalAffineParams switches the filter on for every list of the context that goes to the
+        verification, None switches it off (the default)"""
+        _check(lib().mods_ctx_local_affine(self.h, C.byref(params) if params is not None else None))
+
+    def local_affine_counts(self):
+        """(tentatives in, tentatives kept) of the last list the local affine filter saw on this context"""
+        ni, nk = C.c_int(), C.c_int()
+        _check(lib().mods_local_affine_counts(self.h, C.byref(ni), C.byref(nk)))
+        return ni.value, nk.value
+
+    def filter_local_affine(self, tent, u6, laf, params=None):
+        """mods_filter_local_affine on copies of the three arrays: returns (tent, u6, laf) of the survivors in list order and a dict
+        of the per-input diagnostics keep (bool), neighbours, support, backed (int32)"""
+        return filter_local_affine(self, tent, u6, laf, params)
 
     def match_mutual_counts(self):
         """(forward tentatives, tentatives the mutual check kept) of the context's last single search"""
@@ -764,6 +787,48 @@ def duplicate_filter_gpu(ctx, tent, u6, laf, r=2.0, mode=1):
     _check(lib().mods_duplicate_filter_gpu(ctx.h, tent.ctypes.data_as(C.c_void_p), u6.ctypes.data_as(C.c_void_p),
                                            lf.ctypes.data_as(C.c_void_p), len(tent), C.c_double(r), mode, C.byref(n), C.byref(dev)))
     return tent[:n.value].copy(), u6[:n.value].copy(), lf[:n.value].copy(), bool(dev.value)
+
+
+class LocalAffineParams(C.Structure):
+    """mods_local_affine_params (include/mods_hip.h): the local affine consistency filter of a tentative list"""
+    _fields_ = [("radius", C.c_double), ("minDist", C.c_double), ("absTol", C.c_double), ("relTol", C.c_double),
+                ("areaTol", C.c_double), ("minSupport", C.c_int), ("rescue", C.c_int), ("keepSparse", C.c_int)]
+
+    @staticmethod
+    def default(**kw):
+        p = LocalAffineParams(160.0, 3.0, 4.0, 0.2, 2.0, 3, 1, 1)
+        for k, v in kw.items():
+            if k not in dict(LocalAffineParams._fields_):
+                raise TypeError("LocalAffineParams has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+
+def local_affine_grid():
+    """(rows of a sweep block, columns of an LDS tile) of csrc/local_affine.hip"""
+    r, t = C.c_int(), C.c_int()
+    lib().mods_local_affine_grid.restype = None
+    lib().mods_local_affine_grid(C.byref(r), C.byref(t))
+    return r.value, t.value
+
+
+def filter_local_affine(ctx, tent, u6, laf, params=None):
+    """mods_filter_local_affine; ctx: a Context (None reaches the argument checks only).  Returns (tent, u6, laf, diagnostics)."""
+    tent = np.ascontiguousarray(tent, TENT_DTYPE).copy()
+    u6 = np.ascontiguousarray(u6, np.float64).reshape(-1, 6).copy()
+    lf = np.ascontiguousarray(laf, np.float64).reshape(-1, 14).copy()
+    n = len(tent)
+    if len(u6) != n or len(lf) != n:
+        raise ValueError("filter_local_affine: %d tentatives, %d correspondences, %d frames" % (n, len(u6), len(lf)))
+    par = params if params is not None else LocalAffineParams.default()
+    keep = np.zeros(max(n, 1), np.uint8)
+    nb, sup, back = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+    m = C.c_int()
+    _check(lib().mods_filter_local_affine(ctx.h if ctx is not None else None, tent.ctypes.data_as(C.c_void_p), u6.ctypes.data_as(C.c_void_p),
+                                          lf.ctypes.data_as(C.c_void_p), n, C.byref(par), C.byref(m), keep.ctypes.data_as(C.c_void_p),
+                                          nb.ctypes.data_as(C.c_void_p), sup.ctypes.data_as(C.c_void_p), back.ctypes.data_as(C.c_void_p)))
+    diag = {"keep": keep[:n].astype(bool), "neighbours": nb[:n], "support": sup[:n], "backed": back[:n]}
+    return tent[:m.value].copy(), u6[:m.value].copy(), lf[:m.value].copy(), diag
 
 
 # ---- verification (degensac C ABI + LORANSACFiltering) ---------------------------------------------
@@ -1519,9 +1584,11 @@ class Pipeline:
     """mods_pipeline_*: GPU workers (detect/describe/match) overlapped with verify workers (duplicate
     filter + LO-RANSAC) across pairs; results in submission order."""
 
-    def __init__(self, device, w, h, params=None, gpu_workers=1, verify_workers=1, pairs_per_batch=1, clahe=None, mutual=0):
+    def __init__(self, device, w, h, params=None, gpu_workers=1, verify_workers=1, pairs_per_batch=1, clahe=None, mutual=0,
+                 local_affine=None):
         """clahe: a ClaheParams - 8-bit submissions are equalised with CLAHE on the GPU, fp32 submissions are refused; mutual: the
-        mutual check of every search (mods_pipeline_match_mutual: 0, 1 or 2)"""
+        mutual check of every search (mods_pipeline_match_mutual: 0, 1 or 2); local_affine: a LocalAffineParams - every list is
+        filtered by local affine consistency ahead of the verification (mods_pipeline_local_affine)"""
         self.params = params or PairParams.default()
         self.h = C.c_void_p()
         if clahe is not None:
@@ -1538,6 +1605,16 @@ class Pipeline:
             except ModsError:
                 self.close()
                 raise
+        if local_affine is not None:
+            try:
+                self.set_local_affine(local_affine)
+            except ModsError:
+                self.close()
+                raise
+
+    def set_local_affine(self, params=None):
+        """before the first submit; None switches the filter off"""
+        _check(lib().mods_pipeline_local_affine(self.h, C.byref(params) if params is not None else None))
 
     def set_match_mutual(self, mode):
         """before the first submit"""
@@ -1578,12 +1655,12 @@ class Pipeline:
     def timing_enable(self, stages):
         mask = 0
         for s in stages:
-            mask |= 1 << STAGES.index(s)
+            mask |= 1 << stage_index(s)
         _check(lib().mods_pipeline_timing_enable(self.h, mask))
 
     def timing_read(self, stage):
         ms, n, by = C.c_double(), C.c_int(), C.c_double()
-        _check(lib().mods_pipeline_timing_read(self.h, STAGES.index(stage), C.byref(ms), C.byref(n), C.byref(by)))
+        _check(lib().mods_pipeline_timing_read(self.h, stage_index(stage), C.byref(ms), C.byref(n), C.byref(by)))
         return ms.value, n.value, by.value
 
     def graph_replays(self):

@@ -63,6 +63,8 @@ struct Config {
   // endCoef (io_mods.cpp:431-433, parsed there and never used): mods_ctx_domain_pooling
   int dsp = 0, dsp_scales = 3;
   double dsp_start = 0.5, dsp_end = 1.5;
+  int local_affine = 0;            // [LocalAffineFiltering] doLocalAffineFiltering (no counterpart in the reference): mods_ctx_local_affine
+  mods_local_affine_params la_par;
   int verbose = 0, time_log = 1, write_keypoints = 1, write_matches = 1, output_h = 0;
   // [Matching] guidedMatching (no counterpart in the reference): behind the final verification every bank is searched again under
   // the verified model (mods_match_guided_reps) and the de-duplicated result is what the matches file holds
@@ -247,6 +249,19 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->do_clahe = (int)ini.GetInteger("Matching", "doCLAHE", 0);
   cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
   if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
+  // [LocalAffineFiltering]: the filter of the list that goes to the verification, its parameters under the names of mods_local_affine_params
+  // (the library checks them when the filter is switched on)
+  {
+    const char *sec = "LocalAffineFiltering";
+    mods_local_affine_defaults(&cfg->la_par);
+    cfg->local_affine = (int)ini.GetInteger(sec, "doLocalAffineFiltering", 0);
+    if (cfg->local_affine != 0 && cfg->local_affine != 1) { std::cerr << "[LocalAffineFiltering] doLocalAffineFiltering must be 0 or 1" << std::endl; return 1; }
+    mods_local_affine_params &q = cfg->la_par;
+    q.radius = ini.GetDouble(sec, "radius", q.radius); q.minDist = ini.GetDouble(sec, "minDist", q.minDist);
+    q.absTol = ini.GetDouble(sec, "absTol", q.absTol); q.relTol = ini.GetDouble(sec, "relTol", q.relTol);
+    q.areaTol = ini.GetDouble(sec, "areaTol", q.areaTol); q.minSupport = (int)ini.GetInteger(sec, "minSupport", q.minSupport);
+    q.rescue = (int)ini.GetInteger(sec, "rescue", q.rescue); q.keepSparse = (int)ini.GetInteger(sec, "keepSparse", q.keepSparse);
+  }
   if (ini.Has("zmqDescriptor", "port")) cfg->zmq_port = ini.GetString("zmqDescriptor", "port", "");
   cfg->zmq_mr = ini.GetDouble("zmqDescriptor", "mrSize", cfg->zmq_mr);
   cfg->zmq_ps = (int)ini.GetInteger("zmqDescriptor", "patchSize", cfg->zmq_ps);
@@ -731,6 +746,7 @@ int main(int argc, char **argv) {
   setenv("MODS_LADDER_WORKERS", "1", 0);
   if (mods_ctx_create(device, (int)diag, (int)diag, 2, &ctx)) return fail("context");
   if (cfg.mutual_check && mods_ctx_match_mutual(ctx, cfg.mutual_check)) return fail("mutualCheck");
+  if (cfg.local_affine && mods_ctx_local_affine(ctx, &cfg.la_par)) return fail("[LocalAffineFiltering]");
   if (cfg.dsp && cfg.use_zmq) { std::cerr << "[SIFTDescriptor] domainSizePooling = 1 pools SIFT histograms: it cannot be combined with the [zmqDescriptor] descriptor" << std::endl; return 1; }
   if (cfg.dsp && mods_ctx_domain_pooling(ctx, cfg.dsp_scales, cfg.dsp_start, cfg.dsp_end)) return fail("domainSizePooling");
   if (cfg.dsp && cfg.verbose) std::cerr << "Domain-size pooling: " << cfg.dsp_scales << " domains, " << cfg.dsp_start << " .. " << cfg.dsp_end << " x mrSize" << std::endl;
@@ -816,6 +832,7 @@ int main(int argc, char **argv) {
     else if (!devs.empty()) {
       if (mods_multi_create(devs.data(), (int)devs.size(), std::max(img1.w, img2.w), std::max(img1.h, img2.h), 1 << 20, &multi)) return fail("multi-GPU setup");
       if (cfg.mutual_check) std::cerr << "Note: [Matching] mutualCheck is ignored with MODS_DEVICES (the queries are sharded)" << std::endl;
+      if (cfg.local_affine) std::cerr << "Note: [LocalAffineFiltering] is ignored with MODS_DEVICES (the multi-GPU ladder is unfiltered)" << std::endl;
       if (cfg.dsp) std::cerr << "Note: [SIFTDescriptor] domainSizePooling is ignored with MODS_DEVICES (the devices' contexts describe unpooled)" << std::endl;
       if (cfg.verbose) std::cerr << devs.size() << " device(s), exchange over " << (mods_multi_uses_rccl(multi) ? "RCCL" : "device copies") << std::endl;
     }
@@ -893,6 +910,11 @@ int main(int argc, char **argv) {
   if (cfg.verbose) {
     std::cerr << res.n_views << " views synthesised, " << res.n_tentatives << " tentatives found." << std::endl;
     std::cerr << res.n_unique << " unique tentatives left" << std::endl;
+    if (cfg.local_affine && !multi) {
+      int la_in = 0, la_kept = 0;
+      if (mods_local_affine_counts(ctx, &la_in, &la_kept)) return fail("[LocalAffineFiltering]");
+      std::cerr << "Local affine filtering (radius " << cfg.la_par.radius << "): " << la_in << " tentatives in, " << la_kept << " kept" << std::endl;
+    }
     if (cfg.pair.ransac.groundTruth) {
       std::cerr << "Ground truth verification is used..." << std::endl
                 << res.gt_true << " true matches got with error threshold = " << cfg.pair.ransac.err_threshold << std::endl;

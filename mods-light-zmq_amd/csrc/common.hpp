@@ -336,6 +336,14 @@ struct mods_ctx {
   bool mu_last_checked = false;      // the last single search of the context went through the check
   mods::Buf<int4> mu_cand;
   mods::PinnedBuf<int> mu_count;
+  // local affine consistency filter (local_affine.hip; mods_ctx_local_affine): off by default.  la_buf: the SoA scratch, counters and
+  // places of the lists of one set of launches; la_io: source and kept list of the host-list entry point; la_count: list lengths in and
+  // out, pinned; the counts of the last filtered list
+  bool la_on = false;
+  mods_local_affine_params la_par = {160., 3., 4., 0.2, 2., 3, 1, 1};
+  mods::Buf<char> la_buf, la_io;
+  mods::PinnedBuf<int> la_count;
+  int la_n_in = 0, la_n_kept = 0;
   mods::MserState *mser = nullptr;   // MserState (mser.hip): buffers of the MSER detector, allocated on first use
   // the step loop spreads the views of a step over a few more contexts of the same GPU (imgrep.hip: run_view_jobs)
   std::vector<mods_ctx *> helpers;
@@ -432,6 +440,26 @@ struct DupJob { const char *src; char *dst; const int *n_src; int *n_dst; int *s
 int dup_filter_dev(mods_ctx *c, const DupJob *jobs, int n_jobs, int grid_n, double r, int mode);
 int dup_filter_reserve(mods_ctx *c, int n_jobs);
 static_assert(DUP_MAX_JOBS <= kCountSlots, "every job of the duplicate filter has its slots in m_count");
+// local_affine.hip
+constexpr int LA_MAX_JOBS = 64, LA_ROWS = 256, LA_TILE = 256;   // lists per set of launches; rows of a block = columns of an LDS tile
+struct LaConst { double R2, D2, A2, L2, areaTol; int minSupport, rescue, keepSparse; };
+struct LaJob { const char *src; char *dst; const int *n_src; int *n_dst; };
+struct LaBatch {
+  int n_jobs, max_n;                   // max_n: positions of a list's scratch, a multiple of LA_TILE
+  double *soa; size_t soa_stride;      // per list: x1 y1 x2 y2 t00 t01 t10 t11 dT valid, max_n doubles each
+  int *counters;                       // per list: neighbours[max_n] | support[max_n] | backed[max_n], contiguous over the lists (one fill)
+  int *slots, *res;                    // per list: places[max_n]; {kept, -}
+  LaConst k;
+  LaJob job[LA_MAX_JOBS];
+};
+__host__ __device__ inline int la_len(int n, int max_n) { return n < 0 || n > max_n ? 0 : n; }   // a list the launch was not sized for is left alone
+int la_check(const mods_local_affine_params *p, LaConst *k);
+int la_reserve(mods_ctx *c, int n_jobs, int grid_n);
+int la_filter_dev(mods_ctx *c, const LaJob *jobs, int n_jobs, int grid_n, const LaConst &k, const int **diag_counters = nullptr,
+                  const int **diag_slots = nullptr, int *diag_stride = nullptr);
+struct TentList;
+int local_affine_prefilter(mods_ctx *c, const mods_pair_params *par, TentList *list, bool deduped);
+static_assert(LA_MAX_JOBS >= kCountSlots - 1, "every pair of a batch has its slots in la_count");
 int launch_fast_sqrt_selftest(mods_ctx *ctx, unsigned long long *out5_host);   // describe.hip
 int launch_blur_table(mods_ctx *ctx, int ps);   // sift.hip
 bool ransac_profile_on();     // MODS_RANSAC_PROF: per-call breakdown of the verification on stderr (ransac.hip)

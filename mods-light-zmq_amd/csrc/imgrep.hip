@@ -242,8 +242,16 @@ static void gather_tentatives(mods_ctx *c, const std::vector<TentList> lists[2])
 // DuplicateFiltering + LORANSACFiltering (ORSAFiltering for useF = 2) of the gathered list (mods.cpp:278-383); w, h: the size
 // ORSA normalises by, ((w1 + w2) / 2, (h1 + h2) / 2) in the step loop (mods.cpp:347-350), 0 where the caller has none
 static int verify_gathered(mods_ctx *c, const mods_pair_params *par, mods_ladder_result *res, int w, int h) {
+  res->n_tentatives = (int)c->h_list.size();
+  mods_pair_params p2;
+  if (c->la_on) {          // mods_ctx_local_affine: DuplicateFiltering (when it runs ahead of RANSAC) and the filter here, the verification takes the list as it is
+    const double t0 = now_ms();
+    const int frc = local_affine_prefilter(c, par, &c->h_list, false);
+    if (frc) return frc;
+    res->ms_duplicates += now_ms() - t0;
+    if (par->dup_before_ransac) { p2 = *par; p2.dup_dist = 0; par = &p2; }
+  }
   const int n = (int)c->h_list.size();
-  res->n_tentatives = n;
   int stats[3] = {0, 0, 0};
   double ms_dup = 0, ms_ran = 0;
   int gt3[3] = {0, 0, 0};

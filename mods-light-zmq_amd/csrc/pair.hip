@@ -150,6 +150,10 @@ int mods::pair_gpu_stage(mods_ctx *c, const float *img_dev, int w, int h, int st
       list->unpack_from(stage.data(), (size_t)n);
     }
   } else if ((rc = mods_match_copy_out(c, n, list->tent.data(), list->u6.data(), list->laf.data()))) return rc;
+  if (c->la_on) {          // the local affine filter on the list that goes to the verification (behind DuplicateFiltering when that runs first)
+    if ((rc = local_affine_prefilter(c, par, list, filtered))) return rc;
+    if (par->dup_before_ransac) res->n_unique = (int)list->size();
+  }
   res->ms_match = now_ms() - t1;
   return MODS_OK;
 }
@@ -216,9 +220,15 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
   for (int i = 0; i < n_pairs; i++) seg[i + 1] = seg[i] + ((tent_bytes((size_t)std::max(nr[2 * i], 1)) + 255) & ~(size_t)255);
   if ((rc = match_ensure_buffers(c))) return rc;
   const bool dedup = dedup_on_device(par);
-  const bool direct = dedup && seg[n_pairs] <= c->pin_arena.capacity();
+  // the local affine filter (mods_ctx_local_affine) takes the batch's lists on the device where they are final there: behind the device
+  // duplicate filter, or behind the search when DuplicateFiltering follows RANSAC.  Its compaction then is the one that writes into the
+  // pinned arena (la_direct), or into a third run of segments when the arena is too small
+  const bool la_dev = c->la_on && (dedup || !par->dup_before_ransac);
+  const bool fits_arena = seg[n_pairs] <= c->pin_arena.capacity();
+  const bool direct = dedup && !la_dev && fits_arena, la_direct = la_dev && fits_arena;
   // (the second half of the arena takes the filtered lists of the device duplicate filter)
-  MODS_HIP_CHECK(mods::reserve_scratch(c, c->m_tent_batch, 2 * seg[n_pairs], 2 * seg[n_pairs] + seg[n_pairs] / 2));
+  const size_t seg_runs = la_dev && !la_direct ? 3 : 2;
+  MODS_HIP_CHECK(mods::reserve_scratch(c, c->m_tent_batch, seg_runs * seg[n_pairs], seg_runs * seg[n_pairs] + seg[n_pairs] / 2));
   const double tm0 = now_ms();
   // the searches of the batch's pairs in grouped launches (csrc/match.hip: match_run_group), up to 16 pairs per set of launches
   for (int i0 = 0; i0 < n_pairs; i0 += 16) {
@@ -253,9 +263,24 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     }
     if ((rc = dup_filter_dev(c, jobs.data(), n_pairs, grid_n, par->dup_dist, par->dup_mode))) return rc;
   }
+  if (la_dev) {    // the lists of the whole batch in one grouped set of launches (a list the duplicate filter left to the host arrives with length 0)
+    LaConst lk;
+    if ((rc = la_check(&c->la_par, &lk))) return rc;
+    std::vector<LaJob> jobs(n_pairs);
+    int grid_n = 1;
+    if ((rc = la_reserve(c, n_pairs, 1))) return rc;     // (the pinned counters exist before the jobs point at them)
+    for (int i = 0; i < n_pairs; i++) {
+      const char *src = dedup ? c->m_tent_batch + seg[n_pairs] + seg[i] : c->m_tent_batch + seg[i];
+      jobs[i] = {src, la_direct ? c->pin_arena + seg[i] : c->m_tent_batch + 2 * seg[n_pairs] + seg[i], c->m_count + (dedup ? kept_slot(i) : count_slot(i)), c->la_count + LA_MAX_JOBS + i};
+      grid_n = std::max(grid_n, nr[2 * i]);
+    }
+    if ((rc = la_filter_dev(c, jobs.data(), n_pairs, grid_n, lk))) return rc;
+  }
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
+  std::vector<char> la_pending(n_pairs, c->la_on ? 1 : 0);     // lists the local affine filter has yet to see, on the host
+  std::vector<char> host_deduped(n_pairs, 0);
   std::vector<size_t> off(n_pairs, (size_t)-1);
-  size_t used = direct ? seg[n_pairs] : 0;       // (lists that were not filtered on the device go behind the segments)
+  size_t used = direct || la_direct ? seg[n_pairs] : 0;       // (lists that were not filtered on the device go behind the segments)
   bool copies = false;
   for (int i = 0; i < n_pairs; i++) {
     int n = read_slot(c->m_count, count_slot(i));
@@ -263,12 +288,22 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     if (n > c->max_cand || n > nr[2 * i]) { set_error("tentative list overflow"); return MODS_E_CAPACITY; }
     // filtered on the device: the kept correspondences come over, the verify stage sees n_unique == list length and does not filter again
     const bool filtered = dedup && read_slot(c->m_count, status_slot(i)) == 0;
+    bool in_arena = filtered && direct;
     const char *list = c->m_tent_batch + seg[i];
-    if (filtered) { n = read_slot(c->m_count, kept_slot(i)); res[i]->n_unique = n; list = c->m_tent_batch + seg[n_pairs] + seg[i]; }
+    if (filtered) { n = read_slot(c->m_count, kept_slot(i)); res[i]->n_unique = n; list = c->m_tent_batch + seg[n_pairs] + seg[i]; host_deduped[i] = 1; }
+    if (la_dev && (filtered || !dedup)) {
+      const int m = read_slot(c->la_count, LA_MAX_JOBS + i);
+      if (m < 0 || m > n) { set_error("local_affine: the device returned %d of %d", m, n); return MODS_E_CAPACITY; }
+      c->la_n_in = n; c->la_n_kept = m;
+      n = m; list = c->m_tent_batch + 2 * seg[n_pairs] + seg[i];
+      if (par->dup_before_ransac) res[i]->n_unique = n;
+      la_pending[i] = 0;
+      in_arena = la_direct;
+    }
     lists[i]->resize(n);
     if (n > 0) {
       const size_t bytes = tent_bytes((size_t)n);
-      if (filtered && direct) off[i] = seg[i];          // already in the arena
+      if (in_arena) off[i] = seg[i];                    // already in the arena
       else if (used + bytes <= c->pin_arena.capacity()) {
         MODS_HIP_CHECK(hipMemcpyAsync(c->pin_arena + used, list, bytes, hipMemcpyDeviceToHost, c->stream));
         off[i] = used; used += (bytes + 15) & ~(size_t)15;
@@ -286,6 +321,11 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     res[i]->ms_match = (tm1 - tm0) / n_pairs;
     if (off[i] != (size_t)-1) lists[i]->unpack_from(c->pin_arena + off[i], lists[i]->size());
   }
+  for (int i = 0; i < n_pairs; i++)       // lists that were final only on the host (DuplicateFiltering ran or runs there): the host-list entry point
+    if (la_pending[i]) {
+      if ((rc = local_affine_prefilter(c, par, lists[i], host_deduped[i] != 0))) return rc;
+      if (par->dup_before_ransac) res[i]->n_unique = (int)lists[i]->size();
+    }
   return MODS_OK;
 }
 

@@ -238,6 +238,21 @@ int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCo
   return MODS_OK;
 }
 
+// the local affine consistency filter of every list of the pipeline (mods_ctx_local_affine on the workers' contexts)
+int mods_pipeline_local_affine(mods_pipeline *p, const mods_local_affine_params *par) {
+  LaConst k;
+  if (par) { const int rc = la_check(par, &k); if (rc) return rc; }
+  if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: local_affine after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) { const int rc = mods_ctx_local_affine(c, par); if (rc) return rc; }
+  if (par) {      // the filter's scratch for the lists of a full batch now: a first hipMalloc inside the running pipeline would synchronise the device
+    MODS_HIP_CHECK(hipSetDevice(p->device));
+    for (auto *c : p->ctxs) { const int rc = la_reserve(c, std::min(p->pairs_per_batch, (int)LA_MAX_JOBS), c->max_cand); if (rc) return rc; }
+  }
+  return MODS_OK;
+}
+
 int mods_pipeline_create_ex(int device, int w, int h, const mods_pair_params *par, int gpu_workers, int verify_workers,
                             int pairs_per_batch, mods_pipeline **out) {
   return mods_pipeline_create_clahe(device, w, h, par, gpu_workers, verify_workers, pairs_per_batch, nullptr, out);
