@@ -910,6 +910,12 @@ int mods_match_overlap_reps(mods_ctx *ctx, const mods_imgrep *q, const mods_imgr
                             const mods_overlap_params *par, mods_overlap_match *out, int max_out, int *n_out,
                             mods_overlap_counts *counts);             /* HBM-resident banks */
 int mods_ctx_overlap_splits(mods_ctx *ctx, int splits);
+/* Launch geometry of the sweep of a search of two region lists: out = {query blocks, train splits, 256-train tiles per split}.
+ * search 0: mods_match_guided; 1: mods_match_overlap and mods_match_overlap_area, for which forced_splits is what
+ * mods_ctx_overlap_splits was given (the guided search has no such knob and ignores it).  Host arithmetic only (no device, no
+ * launch); the lists may be empty.  A null out, another search or a negative number: MODS_E_ARG.  The result of a search does not
+ * depend on it, its speed does; tests pin the choice with it. */
+int mods_list_search_grid(int search, int n_q, int n_t, int forced_splits, int out[3]);
 
 /* ---- area-overlap matching of two region lists (the repeatability measure of Mikolajczyk et al., IJCV 2005) --------------
  * The same question as mods_match_overlap, scored with the customary measure: eps = 1 - |A n B| / |A u B| of the two ellipses, the

@@ -126,6 +126,32 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _tentatives(room, call):
+    """room for tentatives, their correspondences and their frames; call(tent, u6, laf, n) runs the search that fills them and
+    returns its code; returns (tent, u6, laf) cut to the count"""
+    room = max(room, 1)
+    out = np.zeros(room, TENT_DTYPE)
+    u6 = np.zeros((room, 6), np.float64)
+    laf = np.zeros((room, 14), np.float64)
+    n = C.c_int()
+    _check(call(_vp(out), _vp(u6), _vp(laf), C.byref(n)))
+    return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+
+
+def _overlap(fn, dtype, lists, params, cap):
+    """one of the four overlap searches: fn(*lists, params, out, cap, n, counts) with room for cap rows of dtype; returns (matches
+    cut to the count, OverlapCounts)"""
+    out = np.zeros(max(cap, 1), dtype)
+    n = C.c_int()
+    counts = OverlapCounts()
+    _check(fn(*lists, C.byref(params), _vp(out), cap, C.byref(n), C.byref(counts)))
+    return out[:n.value].copy(), counts
+
+
 def u8_strips_layout(w, h):
     """(width limit, strips per image, bytes per strip, bytes per image) of the 8-bit strip copy of a w x h image (csrc/u8_strips.hpp;
     no device needed)"""
@@ -663,65 +689,36 @@ class Context:
     def match_fginn(self, q, t, ratio=0.8, contrad=10.0, nn=50):
         q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
         cap = max(len(q), 1)
-        out = np.zeros(cap, TENT_DTYPE)
-        u6 = np.zeros((cap, 6), np.float64)
-        laf = np.zeros((cap, 14), np.float64)
-        n = C.c_int()
-        _check(lib().mods_match_fginn(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
-                                      C.c_double(ratio), C.c_double(contrad), nn, out.ctypes.data_as(C.c_void_p),
-                                      u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        self.last_laf = laf[:n.value].copy()
-        return out[:n.value].copy(), u6[:n.value].copy()
+        tent, u6, self.last_laf = _tentatives(cap, lambda out, u6, laf, n: lib().mods_match_fginn(
+            self.h, _vp(q), len(q), _vp(t), len(t), C.c_double(ratio), C.c_double(contrad), nn, out, u6, laf, cap, n))
+        return tent, u6
 
     def match_distance(self, q, t, threshold):
         """MatchFLANNDistance (matching.cpp:572-633): nearest train by Hamming distance, kept within the threshold."""
         q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
         cap = max(len(q), 1)
-        out = np.zeros(cap, TENT_DTYPE)
-        u6 = np.zeros((cap, 6), np.float64)
-        laf = np.zeros((cap, 14), np.float64)
-        n = C.c_int()
-        _check(lib().mods_match_distance(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
-                                         C.c_double(threshold), out.ctypes.data_as(C.c_void_p),
-                                         u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        return out[:n.value].copy(), u6[:n.value].copy()
+        return _tentatives(cap, lambda out, u6, laf, n: lib().mods_match_distance(
+            self.h, _vp(q), len(q), _vp(t), len(t), C.c_double(threshold), out, u6, laf, cap, n))[:2]
 
     def match_guided(self, q, t, params):
         """mods_match_guided: the model-guided search of two host region lists (GuidedParams); returns (tent, u6, laf)."""
         q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
         cap = max(len(q), 1)
-        out = np.zeros(cap, TENT_DTYPE)
-        u6 = np.zeros((cap, 6), np.float64)
-        laf = np.zeros((cap, 14), np.float64)
-        n = C.c_int()
-        _check(lib().mods_match_guided(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
-                                       C.byref(params), out.ctypes.data_as(C.c_void_p), u6.ctypes.data_as(C.c_void_p),
-                                       laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-        return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+        return _tentatives(cap, lambda out, u6, laf, n: lib().mods_match_guided(
+            self.h, _vp(q), len(q), _vp(t), len(t), C.byref(params), out, u6, laf, cap, n))
 
     def match_overlap(self, q, t, params):
         """mods_match_overlap: ground-truth overlap matching of two host region lists (OverlapParams); returns (matches as
         OVERLAP_DTYPE rows in query order, OverlapCounts)."""
         q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
-        cap = max(len(q), 1)
-        out = np.zeros(cap, OVERLAP_DTYPE)
-        n = C.c_int()
-        counts = OverlapCounts()
-        _check(lib().mods_match_overlap(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
-                                        C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(counts)))
-        return out[:n.value].copy(), counts
+        return _overlap(lib().mods_match_overlap, OVERLAP_DTYPE, (self.h, _vp(q), len(q), _vp(t), len(t)), params, max(len(q), 1))
 
     def match_overlap_area(self, q, t, params):
         """mods_match_overlap_area: area-overlap matching (1 - intersection over union on the lattice) of two host region lists
         (OverlapAreaParams); returns (matches as OVERLAP_AREA_DTYPE rows in query order, OverlapCounts)."""
         q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
-        cap = max(len(q), 1)
-        out = np.zeros(cap, OVERLAP_AREA_DTYPE)
-        n = C.c_int()
-        counts = OverlapCounts()
-        _check(lib().mods_match_overlap_area(self.h, q.ctypes.data_as(C.c_void_p), len(q), t.ctypes.data_as(C.c_void_p), len(t),
-                                             C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(counts)))
-        return out[:n.value].copy(), counts
+        return _overlap(lib().mods_match_overlap_area, OVERLAP_AREA_DTYPE, (self.h, _vp(q), len(q), _vp(t), len(t)), params,
+                        max(len(q), 1))
 
     def overlap_splits(self, splits):
         """mods_ctx_overlap_splits: train splits of the overlap sweeps (0 = automatic); the result does not depend on it."""
@@ -861,6 +858,14 @@ def match_grid(n_q, n_t):
     """mods_match_grid: (query blocks, train splits, tiles per split) of the first pass of an n_q x n_t FGINN search; needs no device."""
     out = (C.c_int * 3)()
     _check(lib().mods_match_grid(int(n_q), int(n_t), out))
+    return out[0], out[1], out[2]
+
+
+def list_search_grid(search, n_q, n_t, forced_splits=0):
+    """mods_list_search_grid: (query blocks, train splits, tiles per split) of the sweep of an n_q x n_t search of two region lists
+    (search 0: guided, 1: overlap and area-overlap, with forced_splits as Context.overlap_splits sets them); needs no device."""
+    out = (C.c_int * 3)()
+    _check(lib().mods_list_search_grid(int(search), int(n_q), int(n_t), int(forced_splits), out))
     return out[0], out[1], out[2]
 
 
@@ -1162,14 +1167,8 @@ def match_reps(ctx, q, t, q_begin=0, q_end=None, ratio=0.8, contrad=10.0, nn=50)
     """MatchImgReps for the query slice [q_begin, q_end) of ImgRep q against all of ImgRep t."""
     q_end = len(q) if q_end is None else q_end
     cap = max(q_end - q_begin, 1)
-    out = np.zeros(cap, TENT_DTYPE)
-    u6 = np.zeros((cap, 6), np.float64)
-    laf = np.zeros((cap, 14), np.float64)
-    n = C.c_int()
-    _check(lib().mods_match_reps(ctx.h, q.h, q_begin, q_end, t.h, C.c_double(ratio), C.c_double(contrad), nn,
-                                 out.ctypes.data_as(C.c_void_p), u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p),
-                                 cap, C.byref(n)))
-    return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+    return _tentatives(cap, lambda out, u6, laf, n: lib().mods_match_reps(
+        ctx.h, q.h, q_begin, q_end, t.h, C.c_double(ratio), C.c_double(contrad), nn, out, u6, laf, cap, n))
 
 
 class GuidedParams(C.Structure):
@@ -1191,13 +1190,8 @@ def match_guided_reps(ctx, rep_q, rep_t, params, cap=None):
     """mods_match_guided_reps: the guided search of ImgRep rep_q against ImgRep rep_t (HBM resident); returns (tent, u6, laf).
     cap: room for that many tentatives (default: one per query, which always suffices)."""
     cap = max(len(rep_q), 1) if cap is None else cap
-    out = np.zeros(max(cap, 1), TENT_DTYPE)
-    u6 = np.zeros((max(cap, 1), 6), np.float64)
-    laf = np.zeros((max(cap, 1), 14), np.float64)
-    n = C.c_int()
-    _check(lib().mods_match_guided_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p),
-                                        u6.ctypes.data_as(C.c_void_p), laf.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
-    return out[:n.value].copy(), u6[:n.value].copy(), laf[:n.value].copy()
+    return _tentatives(cap, lambda out, u6, laf, n: lib().mods_match_guided_reps(
+        ctx.h, rep_q.h, rep_t.h, C.byref(params), out, u6, laf, cap, n))
 
 
 OVERLAP_DTYPE = np.dtype([("q", "i4"), ("t", "i4"), ("E", "f8"), ("dist", "f8"), ("diff", "f8")])
@@ -1227,12 +1221,7 @@ def match_overlap_reps(ctx, rep_q, rep_t, params, cap=None):
     """mods_match_overlap_reps: overlap matching of ImgRep rep_q against ImgRep rep_t (HBM resident); returns (matches, counts).
     cap: room for that many matches (default: one per query, which always suffices)."""
     cap = max(len(rep_q), 1) if cap is None else cap
-    out = np.zeros(max(cap, 1), OVERLAP_DTYPE)
-    n = C.c_int()
-    counts = OverlapCounts()
-    _check(lib().mods_match_overlap_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
-                                         C.byref(counts)))
-    return out[:n.value].copy(), counts
+    return _overlap(lib().mods_match_overlap_reps, OVERLAP_DTYPE, (ctx.h, rep_q.h, rep_t.h), params, cap)
 
 
 OVERLAP_AREA_DTYPE = np.dtype([("q", "i4"), ("t", "i4"), ("E", "f8"), ("n_q_px", "i4"), ("n_t_px", "i4"), ("n_both", "i4"), ("pad", "i4")])
@@ -1257,12 +1246,7 @@ def match_overlap_area_reps(ctx, rep_q, rep_t, params, cap=None):
     """mods_match_overlap_area_reps: area-overlap matching of ImgRep rep_q against ImgRep rep_t (HBM resident); returns (matches,
     counts).  cap: room for that many matches (default: one per query, which always suffices)."""
     cap = max(len(rep_q), 1) if cap is None else cap
-    out = np.zeros(max(cap, 1), OVERLAP_AREA_DTYPE)
-    n = C.c_int()
-    counts = OverlapCounts()
-    _check(lib().mods_match_overlap_area_reps(ctx.h, rep_q.h, rep_t.h, C.byref(params), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
-                                              C.byref(counts)))
-    return out[:n.value].copy(), counts
+    return _overlap(lib().mods_match_overlap_area_reps, OVERLAP_AREA_DTYPE, (ctx.h, rep_q.h, rep_t.h), params, cap)
 
 
 def _verified_lafs(fn, handle):

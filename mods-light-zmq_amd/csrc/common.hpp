@@ -298,6 +298,8 @@ struct mods_ctx {
   mods::TentList h_list;             // host copy for the sequential stages
   int h_verified = 0;                // rows at the head of h_list that the last pair / ladder / verify call verified (mods_ctx_verified_lafs)
   std::vector<unsigned char> h_mask;
+  // the searches of two region lists (list_search.hpp): the staging of host lists, which they share
+  mods::Buf<mods_region> ls_regs;
   // guided matching (guided.hip), its own buffers: gate records and dense descriptor rows of both lists (queries first), the
   // per-query (nearest, inconsistent second) and per-train keys, accept flags + block counts, the packed result and its length
   mods::Buf<double4> g_rec;
@@ -305,7 +307,6 @@ struct mods_ctx {
   mods::Buf<unsigned long long> g_key;
   mods::Buf<int> g_int;
   mods::Buf<char> g_tent;
-  mods::Buf<mods_region> g_regs;     // staging of host lists
   mods::PinnedBuf<int> g_count;
   // overlap matching (overlap.hip), its own buffers: 48-byte fp64 records of both lists (queries first, 6 doubles each), the error
   // keys (per train, per query, per split and query), the integer twins (common counts, per-train owner, per-query train, block
@@ -314,20 +315,18 @@ struct mods_ctx {
   mods::Buf<unsigned long long> o_key;
   mods::Buf<int> o_int;
   mods::Buf<mods_overlap_match> o_out;
-  mods::Buf<mods_region> o_regs;     // staging of host lists
   mods::PinnedBuf<int> o_count;
   int o_splits = 0;
   // area-overlap matching (overlap_area.hip), its own buffers: the 48-byte records of both lists (queries first), the error keys
-  // (per train, per query, per listed pair), the integers (common counts, per-train owner, per-query pair, the sweep's block
-  // counts, per split and query the pair count and the list offset; oa_pair: the list's (q, t), its three pixel counts and the
-  // compaction's block counts), the matches, the staging of host lists and (items, common queries, common trains, listed pairs
-  // as two halves of 64 bits); oa_host: the accepted pairs of mode 2
+  // (per train, per query, per listed pair), the integers (common counts, per-train owner, per-query pair and train, the sweep's
+  // block counts, per split and query the pair count and the list offset; oa_pair: the list's (q, t), its three pixel counts and
+  // the compaction's block counts), the matches and (items, common queries, common trains, listed pairs as two halves of 64
+  // bits); oa_host: the accepted pairs of mode 2
   mods::Buf<double> oa_rec;
   mods::Buf<unsigned long long> oa_key;
   mods::Buf<int> oa_int;
   mods::Buf<int> oa_pair;            // what is sized by the pair list (its length is known between the two gate sweeps)
   mods::Buf<mods_overlap_area_match> oa_out;
-  mods::Buf<mods_region> oa_regs;
   mods::PinnedBuf<int> oa_count;
   std::vector<mods_overlap_area_match> oa_host;
   // mutual check of the FGINN searches (mutual.hip; mods_ctx_match_mutual), reserved on the first search with a mode set: 16 counters

@@ -7,13 +7,12 @@
 // geometry with one rounding per operation, integer descriptor distances, every reduction a minimum over a total order - so the
 // result does not depend on the launch geometry, the train splits or the arrival order of the atomics.
 //
-// Shape: pack (208-byte regions -> 32-byte fp64 gate records + dense 128-byte descriptor rows), two sweeps of the n_q x n_t gate
-// (nearest gated train, then nearest gated train inconsistent with it), accept (+ one-to-one by atomicMin per train), ordered
-// compaction and emit in the packed layout of common.hpp.  A thread owns a query (its record in registers), the block walks the
-// trains through LDS tiles that all lanes read at the same address (a broadcast), four trains per branch, and the few pairs that
-// pass the gate get their descriptor distance from the whole wave: 32 lanes per 128-byte row, two rows at a time.  VALU only, no
-// matrix cores.
-#include "common.hpp"
+// The shape is that of list_search.hpp: the pack gives 32-byte fp64 gate records + dense 128-byte descriptor rows (an 8 KB tile
+// of records), there are two sweeps of the n_q x n_t gate (nearest gated train, then nearest gated train inconsistent with it),
+// accept settles one-to-one by one atomicMin per train, and the emit is in the packed layout of common.hpp.  The sweep takes four
+// trains per branch, and the few pairs that pass the gate get their descriptor distance from the whole wave: 32 lanes per
+// 128-byte row, two rows at a time.  VALU only, no matrix cores.
+#include "list_search.hpp"
 #include <cmath>
 
 namespace mods {
@@ -28,10 +27,6 @@ struct GuidedConst {
   int tiles_per_split;    // train tiles a block of the sweep walks (blockIdx.y = split)
 };
 
-constexpr int G_THREADS = 256;   // queries per block of the sweep, threads of every kernel here
-constexpr int G_TILE = 256;      // trains per LDS tile (8 KB of records)
-constexpr unsigned long long G_NONE = ~0ull;
-
 __device__ __forceinline__ void guided_project(const double *M, double x, double y, double *px, double *py) {
   const double X = (M[0] * x + M[1] * y) + M[2];
   const double Y = (M[3] * x + M[4] * y) + M[5];
@@ -42,9 +37,9 @@ __device__ __forceinline__ void guided_project(const double *M, double x, double
 // One list: thread (8 i + c) copies 16-byte chunk c of region i's descriptor, chunk 0's thread also writes the gate record.
 //   H, query: px py x1 y1      H, train: x2 y2 bx by
 //   F, query: a b c0 gq        F, train: x2 y2 gt 0
-__global__ __launch_bounds__(G_THREADS) void guided_pack_kernel(GuidedConst k, const mods_region *__restrict__ reg, int n, int is_train,
+__global__ __launch_bounds__(LS_THREADS) void guided_pack_kernel(GuidedConst k, const mods_region *__restrict__ reg, int n, int is_train,
                                                                 double4 *__restrict__ rec, uint4 *__restrict__ desc) {
-  const size_t gid = (size_t)blockIdx.x * G_THREADS + threadIdx.x;
+  const size_t gid = (size_t)blockIdx.x * LS_THREADS + threadIdx.x;
   const size_t i = gid >> 3;
   const int ch = (int)(gid & 7);
   if (i >= (size_t)n) return;
@@ -90,12 +85,12 @@ template <int MODE> __device__ __forceinline__ bool gate_rest(const double4 r, c
 // The gate sweep.  SECOND = false: out[q] = min (d, t) over the gated trains.  SECOND = true: the same minimum over the gated trains
 // other than t1 = the train of best[q] whose centre lies farther than contradDist from t1's.  grid = (ceil(n_q / 256), splits).
 template <int MODE, bool SECOND>
-__global__ __launch_bounds__(G_THREADS) void guided_sweep_kernel(GuidedConst k, const double4 *__restrict__ qrec, const double4 *__restrict__ trec,
+__global__ __launch_bounds__(LS_THREADS) void guided_sweep_kernel(GuidedConst k, const double4 *__restrict__ qrec, const double4 *__restrict__ trec,
                                                                  const unsigned int *__restrict__ qdesc, const unsigned int *__restrict__ tdesc,
                                                                  const unsigned long long *__restrict__ best, unsigned long long *__restrict__ out) {
-  __shared__ double4 s_t[G_TILE];
+  __shared__ double4 s_t[LS_TILE];
   const int tid = threadIdx.x, lane = tid & 63, sub = lane & 31;
-  const int q = blockIdx.x * G_THREADS + tid;
+  const int q = blockIdx.x * LS_THREADS + tid;
   const int qw = q - lane;                               // the wave's first query
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const double4 none = make_double4(nan, nan, nan, nan);
@@ -105,14 +100,14 @@ __global__ __launch_bounds__(G_THREADS) void guided_sweep_kernel(GuidedConst k, 
   if (q < k.n_q) {
     if (SECOND) {
       const unsigned long long k1 = best[q];
-      if (k1 != G_NONE) { r = qrec[q]; t1 = (int)(unsigned int)k1; const double4 c = trec[t1]; t1x = c.x; t1y = c.y; }
+      if (k1 != LS_NONE) { r = qrec[q]; t1 = (int)(unsigned int)k1; const double4 c = trec[t1]; t1x = c.x; t1y = c.y; }
     } else r = qrec[q];
   }
-  const int t_begin = min(k.n_t, (int)blockIdx.y * k.tiles_per_split * G_TILE);
-  const int t_end = min(k.n_t, t_begin + k.tiles_per_split * G_TILE);
-  unsigned long long mine = G_NONE;
-  for (int t0 = t_begin; t0 < t_end; t0 += G_TILE) {
-    const int cnt = min(G_TILE, t_end - t0);             // the tail of the last tile holds records that pass nothing
+  const TrainRange range = train_range(k.n_t, k.tiles_per_split);
+  const int t_begin = range.begin, t_end = range.end;
+  unsigned long long mine = LS_NONE;
+  for (int t0 = t_begin; t0 < t_end; t0 += LS_TILE) {
+    const int cnt = min(LS_TILE, t_end - t0);             // the tail of the last tile holds records that pass nothing
     __syncthreads();
     double4 rec = none;
     if (tid < cnt) rec = trec[t0 + tid];
@@ -159,79 +154,58 @@ __global__ __launch_bounds__(G_THREADS) void guided_sweep_kernel(GuidedConst k, 
       }
     }
   }
-  if (mine != G_NONE) atomicMin(&out[q], mine);
+  if (mine != LS_NONE) atomicMin(&out[q], mine);
 }
 
 // acc[q] = the query passes the distance cap and the ratio test; with one_to_one its (d1, q) competes for its train
-__global__ __launch_bounds__(G_THREADS) void guided_accept_kernel(GuidedConst k, const unsigned long long *__restrict__ best,
+__global__ __launch_bounds__(LS_THREADS) void guided_accept_kernel(GuidedConst k, const unsigned long long *__restrict__ best,
                                                                   const unsigned long long *__restrict__ second, int *__restrict__ acc,
                                                                   unsigned long long *__restrict__ train_best) {
-  const int q = blockIdx.x * G_THREADS + threadIdx.x;
+  const int q = blockIdx.x * LS_THREADS + threadIdx.x;
   if (q >= k.n_q) return;
   const unsigned long long k1 = best[q], k2 = second[q];
-  bool ok = k1 != G_NONE;
+  bool ok = k1 != LS_NONE;
   if (ok) {
     const int d1 = (int)(k1 >> 32);
     ok = k.max_dist == 0 || d1 <= k.max_dist;
-    if (k2 != G_NONE) ok = ok && ((double)d1 < k.rho2 * (double)(int)(k2 >> 32));
+    if (k2 != LS_NONE) ok = ok && ((double)d1 < k.rho2 * (double)(int)(k2 >> 32));
     if (ok && k.one_to_one) atomicMin(&train_best[(unsigned int)k1], (k1 & 0xffffffff00000000ull) | (unsigned int)q);
   }
   acc[q] = ok ? 1 : 0;
 }
 
-__device__ __forceinline__ bool guided_final(const GuidedConst &k, int q, const unsigned long long *best, const int *acc,
-                                             const unsigned long long *train_best) {
-  if (q >= k.n_q || !acc[q]) return false;
-  return !k.one_to_one || (unsigned int)train_best[(unsigned int)best[q]] == (unsigned int)q;
-}
+// whether query q is emitted: it was accepted and, with one_to_one, owns its train
+struct guided_final {
+  int n_q, one_to_one;
+  const unsigned long long *best, *train_best;
+  const int *acc;
+  __device__ bool operator()(int q) const {
+    if (q >= n_q || !acc[q]) return false;
+    return !one_to_one || (unsigned int)train_best[(unsigned int)best[q]] == (unsigned int)q;
+  }
+};
 
-__global__ __launch_bounds__(G_THREADS) void guided_count_kernel(GuidedConst k, const unsigned long long *__restrict__ best,
-                                                                 const int *__restrict__ acc, const unsigned long long *__restrict__ train_best,
-                                                                 int *__restrict__ block_counts) {
-  const bool emit = guided_final(k, blockIdx.x * G_THREADS + threadIdx.x, best, acc, train_best);
-  const int c = __syncthreads_count(emit ? 1 : 0);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = c;
-}
-
-// Ordered compaction: a block's offset is the sum of the counts of the blocks before it, a query's slot the accepted queries before
-// it in its block.  Output in the packed layout of common.hpp (tentatives | correspondences | frames) for the total count.
-__global__ __launch_bounds__(G_THREADS) void guided_emit_kernel(GuidedConst k, const unsigned long long *__restrict__ best,
-                                                                const unsigned long long *__restrict__ second, const int *__restrict__ acc,
-                                                                const unsigned long long *__restrict__ train_best,
-                                                                const int *__restrict__ block_counts, const mods_region *__restrict__ qreg,
-                                                                const mods_region *__restrict__ treg, char *__restrict__ out,
-                                                                int *__restrict__ out_count) {
-  __shared__ int s_wave[G_THREADS / 64], s_wtot[G_THREADS / 64];
-  __shared__ int s_base, s_total;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int n_blocks = gridDim.x;
-  int part = 0, tot = 0;
-  for (int b = tid; b < n_blocks; b += G_THREADS) { const int c = block_counts[b]; tot += c; if (b < (int)blockIdx.x) part += c; }
-  for (int off = 32; off > 0; off >>= 1) { part += __shfl_xor(part, off); tot += __shfl_xor(tot, off); }
-  if (lane == 0) { s_wave[wv] = part; s_wtot[wv] = tot; }
-  __syncthreads();
-  if (tid == 0) { int t = 0, u = 0; for (int w = 0; w < G_THREADS / 64; w++) { t += s_wave[w]; u += s_wtot[w]; } s_base = t; s_total = u; }
-  __syncthreads();
-  const int base = s_base;
-  const size_t n_out = (size_t)s_total;                  // at most n_q, which the output buffer holds
+// The emit kernel of the ordered compaction.  Output in the packed layout of common.hpp (tentatives | correspondences | frames),
+// whose parts lie where the total count puts them: every block sums all the block counts before it writes
+__global__ __launch_bounds__(LS_THREADS) void guided_emit_kernel(guided_final final, const unsigned long long *__restrict__ second,
+                                                                 const int *__restrict__ block_counts, const mods_region *__restrict__ qreg,
+                                                                 const mods_region *__restrict__ treg, char *__restrict__ out,
+                                                                 int *__restrict__ out_count) {
+  __shared__ int s_wave[LS_WAVES];
+  const size_t n_out = (size_t)block_sum_before(block_counts, (int)gridDim.x, s_wave);   // at most n_q, which the output buffer holds
   mods_tentative *tent = (mods_tentative *)out;
   double *u6 = (double *)(out + tent_u6_off(n_out)), *laf = (double *)(out + tent_laf_off(n_out));
-  __syncthreads();
-  const int q = blockIdx.x * G_THREADS + tid;
-  const bool emit = guided_final(k, q, best, acc, train_best);
-  const unsigned long long mm = __ballot(emit);
-  if (lane == 0) s_wave[wv] = __popcll(mm);
-  __syncthreads();
-  int off = base;
-  for (int w = 0; w < wv; w++) off += s_wave[w];
+  const int q = blockIdx.x * LS_THREADS + threadIdx.x;
+  const bool emit = final(q);
+  int upto;
+  const int slot = compact_slot(emit, block_counts, s_wave, &upto);
   if (emit) {
-    const int slot = off + __popcll(mm & ((1ull << lane) - 1ull));
-    const unsigned long long k1 = best[q], k2 = second[q];
-    const int d1 = (int)(k1 >> 32), d2 = k2 != G_NONE ? (int)(k2 >> 32) : 0;
+    const unsigned long long k1 = final.best[q], k2 = second[q];
+    const int d1 = (int)(k1 >> 32), d2 = k2 != LS_NONE ? (int)(k2 >> 32) : 0;
     mods_tentative tc;
-    tc.q = q; tc.t = (int)(unsigned int)k1; tc.t_bad = k2 != G_NONE ? (int)(unsigned int)k2 : -1; tc.t_2nd = -1;
+    tc.q = q; tc.t = (int)(unsigned int)k1; tc.t_bad = k2 != LS_NONE ? (int)(unsigned int)k2 : -1; tc.t_2nd = -1;
     tc.d1 = (float)d1; tc.d2 = (float)d2; tc.d2nd = 0.f; tc.pad = 0.f;
-    tc.ratio = k2 != G_NONE ? sqrt((double)d1 / (double)d2) : 0.;
+    tc.ratio = k2 != LS_NONE ? sqrt((double)d1 / (double)d2) : 0.;
     tent[slot] = tc;
     const mods_region &r1 = qreg[tc.q], &r2 = treg[tc.t];
     double *u = u6 + (size_t)slot * 6;
@@ -240,15 +214,11 @@ __global__ __launch_bounds__(G_THREADS) void guided_emit_kernel(GuidedConst k, c
     f[0] = r1.x; f[1] = r1.y; f[2] = r1.a11; f[3] = r1.a12; f[4] = r1.a21; f[5] = r1.a22; f[6] = r1.s;
     f[7] = r2.x; f[8] = r2.y; f[9] = r2.a11; f[10] = r2.a12; f[11] = r2.a21; f[12] = r2.a22; f[13] = r2.s;
   }
-  if ((int)blockIdx.x == n_blocks - 1 && tid == 0) {     // total = offset of the last block + its own count
-    int t = base;
-    for (int w = 0; w < G_THREADS / 64; w++) t += s_wave[w];
-    *out_count = t;
-  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *out_count = upto;
 }
 
-// Every refusal of a guided call that needs no device; fills the kernels' constants
-static int guided_check(const mods_guided_params *par, GuidedConst *k) {
+// Every refusal of a guided call that needs no device, the parameters before the output; fills the kernels' constants
+static int guided_check(const mods_guided_params *par, const mods_tentative *out, int max_out, GuidedConst *k) {
   if (!par) { set_error("match_guided: null argument"); return MODS_E_ARG; }
   if (par->model_type != 0 && par->model_type != 1) { set_error("match_guided: model_type %d (0 or 1)", par->model_type); return MODS_E_ARG; }
   for (int i = 0; i < 9; i++)
@@ -270,13 +240,14 @@ static int guided_check(const mods_guided_params *par, GuidedConst *k) {
   k->c2 = par->contradDist * par->contradDist;
   k->max_dist = par->max_dist; k->one_to_one = par->one_to_one ? 1 : 0;
   k->tiles_per_split = 1;
+  if (max_out < 0 || (max_out > 0 && !out)) { set_error("match_guided: null argument"); return MODS_E_ARG; }
   return MODS_OK;
 }
 
 template <int MODE, bool SECOND>
 static void launch_sweep(mods_ctx *c, dim3 grid, const GuidedConst &k, const double4 *rec, const unsigned int *desc,
                          const unsigned long long *best, unsigned long long *out) {
-  hipLaunchKernelGGL((guided_sweep_kernel<MODE, SECOND>), grid, dim3(G_THREADS), 0, c->stream, k, rec, rec + k.n_q, desc,
+  hipLaunchKernelGGL((guided_sweep_kernel<MODE, SECOND>), grid, dim3(LS_THREADS), 0, c->stream, k, rec, rec + k.n_q, desc,
                      desc + (size_t)k.n_q * 32, best, out);
 }
 
@@ -290,7 +261,10 @@ static int guided_run(mods_ctx *c, const mods_region *q_dev, const mods_region *
     return MODS_OK;
   }
   const size_t nq = (size_t)k.n_q, nt = (size_t)k.n_t, n = nq + nt;
-  const int qblocks = (k.n_q + G_THREADS - 1) / G_THREADS;
+  const SweepGrid gr = sweep_grid(k.n_q, k.n_t, GUIDED_TARGET_BLOCKS, 0);
+  const int qblocks = gr.qblocks;
+  k.tiles_per_split = gr.tiles_per_split;
+  const dim3 grid(qblocks, gr.splits);
   MODS_HIP_CHECK(mods::reserve_scratch(c, c->g_rec, n, n + n / 4));
   MODS_HIP_CHECK(mods::reserve_scratch(c, c->g_desc, n * 128, (n + n / 4) * 128));
   MODS_HIP_CHECK(mods::reserve_scratch(c, c->g_key, 2 * nq + nt, 2 * nq + nt + n / 4));
@@ -300,24 +274,20 @@ static int guided_run(mods_ctx *c, const mods_region *q_dev, const mods_region *
   uint4 *desc = (uint4 *)c->g_desc.get();
   unsigned long long *best = c->g_key, *second = best + nq, *train_best = second + nq;
   int *acc = c->g_int, *block_counts = acc + nq;
-  // splits of the train range: enough blocks for a few waves on every SIMD of the 256 CUs even when the query list is short
-  const int n_tiles = (k.n_t + G_TILE - 1) / G_TILE;
-  const int splits = std::max(1, std::min(n_tiles, (2048 + qblocks - 1) / qblocks));
-  k.tiles_per_split = (n_tiles + splits - 1) / splits;
-  const dim3 grid(qblocks, (n_tiles + k.tiles_per_split - 1) / k.tiles_per_split);
   StageScope scope(c, MODS_STAGE_GUIDED, (double)n * sizeof(mods_region));
   MODS_HIP_CHECK(hipMemsetAsync(best, 0xff, sizeof(unsigned long long) * (2 * nq + nt), c->stream));
-  hipLaunchKernelGGL(guided_pack_kernel, dim3((unsigned)((nq * 8 + G_THREADS - 1) / G_THREADS)), dim3(G_THREADS), 0, c->stream, k, q_dev,
+  hipLaunchKernelGGL(guided_pack_kernel, dim3((unsigned)((nq * 8 + LS_THREADS - 1) / LS_THREADS)), dim3(LS_THREADS), 0, c->stream, k, q_dev,
                      k.n_q, 0, rec, desc);
-  hipLaunchKernelGGL(guided_pack_kernel, dim3((unsigned)((nt * 8 + G_THREADS - 1) / G_THREADS)), dim3(G_THREADS), 0, c->stream, k, t_dev,
+  hipLaunchKernelGGL(guided_pack_kernel, dim3((unsigned)((nt * 8 + LS_THREADS - 1) / LS_THREADS)), dim3(LS_THREADS), 0, c->stream, k, t_dev,
                      k.n_t, 1, rec + nq, desc + nq * 8);
   const unsigned int *d32 = (const unsigned int *)desc;
   if (k.mode == 0) { launch_sweep<0, false>(c, grid, k, rec, d32, best, best); launch_sweep<0, true>(c, grid, k, rec, d32, best, second); }
   else { launch_sweep<1, false>(c, grid, k, rec, d32, best, best); launch_sweep<1, true>(c, grid, k, rec, d32, best, second); }
-  hipLaunchKernelGGL(guided_accept_kernel, dim3(qblocks), dim3(G_THREADS), 0, c->stream, k, best, second, acc, train_best);
-  hipLaunchKernelGGL(guided_count_kernel, dim3(qblocks), dim3(G_THREADS), 0, c->stream, k, best, acc, train_best, block_counts);
-  hipLaunchKernelGGL(guided_emit_kernel, dim3(qblocks), dim3(G_THREADS), 0, c->stream, k, best, second, acc, train_best, block_counts,
-                     q_dev, t_dev, c->g_tent.get(), c->g_count.get());
+  hipLaunchKernelGGL(guided_accept_kernel, dim3(qblocks), dim3(LS_THREADS), 0, c->stream, k, best, second, acc, train_best);
+  const guided_final final{k.n_q, k.one_to_one, best, train_best, acc};
+  hipLaunchKernelGGL(compact_count_kernel<guided_final>, dim3(qblocks), dim3(LS_THREADS), 0, c->stream, final, block_counts);
+  hipLaunchKernelGGL(guided_emit_kernel, dim3(qblocks), dim3(LS_THREADS), 0, c->stream, final, second, block_counts, q_dev, t_dev,
+                     c->g_tent.get(), c->g_count.get());
   MODS_HIP_CHECK(hipGetLastError());
   return MODS_OK;
 }
@@ -345,20 +315,17 @@ extern "C" {
 
 int mods_match_guided(mods_ctx *c, const mods_region *q, int n_q, const mods_region *t, int n_t, const mods_guided_params *par,
                       mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out) {
-  if (!n_out || (n_q > 0 && !q) || (n_t > 0 && !t)) { set_error("match_guided: null argument"); return MODS_E_ARG; }
-  if (n_q < 0 || n_t < 0) { set_error("match_guided: negative count (%d queries, %d trains)", n_q, n_t); return MODS_E_ARG; }
-  GuidedConst k;
-  int rc = guided_check(par, &k);
+  if (!n_out) { set_error("match_guided: null argument"); return MODS_E_ARG; }
+  int rc = check_host_lists("match_guided", q, n_q, t, n_t);
   if (rc) return rc;
+  GuidedConst k;
+  if ((rc = guided_check(par, out, max_out, &k))) return rc;
   k.n_q = n_q; k.n_t = n_t;
-  if (max_out < 0 || (max_out > 0 && !out)) { set_error("match_guided: null argument"); return MODS_E_ARG; }
   if (!c) { set_error("match_guided: null context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  const size_t n = (size_t)n_q + (size_t)n_t;
-  MODS_HIP_CHECK(mods::reserve_scratch(c, c->g_regs, n, n + n / 4));
-  if (n_q) MODS_HIP_CHECK(hipMemcpyAsync(c->g_regs, q, sizeof(mods_region) * (size_t)n_q, hipMemcpyHostToDevice, c->stream));
-  if (n_t) MODS_HIP_CHECK(hipMemcpyAsync(c->g_regs + n_q, t, sizeof(mods_region) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
-  if ((rc = guided_run(c, c->g_regs, c->g_regs + n_q, k))) return rc;
+  const mods_region *q_dev, *t_dev;
+  if ((rc = stage_lists(c, q, n_q, t, n_t, &q_dev, &t_dev))) return rc;
+  if ((rc = guided_run(c, q_dev, t_dev, k))) return rc;
   return guided_fetch(c, out, u6_out, laf_out, max_out, n_out);
 }
 
@@ -366,9 +333,8 @@ int mods_match_guided_reps(mods_ctx *c, const mods_imgrep *q, const mods_imgrep 
                            double *u6_out, double *laf_out, int max_out, int *n_out) {
   if (!n_out || !q || !t) { set_error("match_guided: null argument"); return MODS_E_ARG; }
   GuidedConst k;
-  int rc = guided_check(par, &k);
+  int rc = guided_check(par, out, max_out, &k);
   if (rc) return rc;
-  if (max_out < 0 || (max_out > 0 && !out)) { set_error("match_guided: null argument"); return MODS_E_ARG; }
   if (!c) { set_error("match_guided: null context"); return MODS_E_ARG; }
   k.n_q = mods_imgrep_count(q); k.n_t = mods_imgrep_count(t);   // (the banks are read only behind every refusal)
   MODS_HIP_CHECK(hipSetDevice(c->device));

@@ -5,57 +5,31 @@
 // rounding per operation in front of three integer counts, so the result does not depend on the launch geometry, the train splits
 // or the arrival order of the atomics.
 //
-// Shape: pack (as overlap.hip, but a train keeps its frame, not the inverse: the pair's scale comes from the query), a gate sweep
-// of the n_q x n_t pairs run twice - it counts the pairs to evaluate per (split, query), the host reads their total and sizes the
-// list, it runs again and writes each pair to the place the counts give it, so the list is in (split, query, train) order
-// whatever the blocks' order - then one wave per listed pair walks the lattice (lanes take consecutive points of the box row by
-// row, three integers per lane, a wave reduction), and accept takes per query the minimum over its runs of the list in split
-// order: no atomic on the way, two atomicMin per train for the one-to-one rule as in overlap.hip.  Ordered compaction and emit
-// over the queries (modes 0, 1) or over the listed pairs (mode 2, whose sort and greedy pass run on the host).  A thread of the
-// sweep owns a query (its normalised frame in registers), the block walks the trains through LDS tiles that all lanes read at
-// the same address.  VALU only, no matrix cores.
+// The shape is that of list_search.hpp, with the pack, the one-to-one rule and the parameter checks of overlap_common.hpp; a train
+// keeps its frame, not the inverse: the pair's scale comes from the query.  The gate sweep of the n_q x n_t pairs runs twice - it
+// counts the pairs to evaluate per (split, query), the host reads their total and sizes the list, it runs again and writes each
+// pair to the place the counts give it, so the list is in (split, query, train) order whatever the blocks' order - then one wave
+// per listed pair walks the lattice (lanes take consecutive points of the box row by row, three integers per lane, a wave
+// reduction), and accept takes per query the minimum over its runs of the list in split order: no atomic on the way.  The
+// compaction runs over the queries (modes 0, 1) or over the listed pairs (mode 2, whose sort and greedy pass run on the host).
+// VALU only, no matrix cores.
 #include "overlap_common.hpp"
-#include <algorithm>
-#include <cmath>
 
 namespace mods {
 
 struct AreaConst {
   int n_q, n_t;
-  double H[9], Hinv[9];   // row-major; Hinv = adjugate / determinant
+  OvGeom geo;
   double max_error;
   double g;               // 0.9 * (1.0 - max_error)
   int one_to_one;         // 0, 1, 2
-  int area;               // the common-area test runs (all four sizes > 0)
-  double w1, h1, w2, h2;
   int tiles_per_split;    // train tiles a block of the sweep walks (blockIdx.y = split)
 };
 
 // query: px py C11 C12 C21 C22     train: x2 y2 M11 M12 M21 M22
 using AreaRec = OvRec;
 
-constexpr int A_THREADS = 256;   // queries per block of the sweep, threads of every kernel here
-constexpr int A_TILE = 256;      // trains per LDS tile (12 KB of records)
-constexpr int A_WAVES = A_THREADS / 64;
-constexpr unsigned long long A_NONE = ~0ull;
 constexpr long long A_MAX_PAIRS = 1ll << 26;   // listed pairs a search may hold (28 bytes each, 60 with the output of mode 2)
-
-// One list, a thread per region.  cnt[is_train] += the regions of the list that take part (all of them without the area test)
-__global__ __launch_bounds__(A_THREADS) void area_pack_kernel(AreaConst k, const mods_region *__restrict__ reg, int n, int is_train,
-                                                              AreaRec *__restrict__ rec, int *__restrict__ cnt) {
-  const int i = blockIdx.x * A_THREADS + threadIdx.x;
-  bool part = false;
-  if (i < n) {
-    AreaRec r = overlap_frame(reg[i]);                   // a train keeps its frame: the pair's scale comes from the query
-    if (!is_train) {
-      r = overlap_query_rec(k.H, r);
-      part = !k.area || overlap_in_image(r.a, r.b, k.w2, k.h2);
-    } else part = !k.area || overlap_maps_into(k.Hinv, r.a, r.b, k.w1, k.h1);
-    rec[i] = part ? r : overlap_nan_rec();
-  }
-  const int c = __syncthreads_count(part ? 1 : 0);
-  if (threadIdx.x == 0 && c) atomicAdd(&cnt[is_train], c);
-}
 
 // The query's half of a pair's set-up: the scale that gives its ellipse the area of a circle of radius 30, its frame and half
 // box at that scale
@@ -95,67 +69,36 @@ __device__ __forceinline__ bool area_gate(double g, const AreaQuery &q, const Ar
   return true;
 }
 
-// exclusive prefix of v over the block's threads and, in *total, the block's sum (s_wave: A_WAVES ints of LDS)
-__device__ __forceinline__ int area_block_scan(int v, int *s_wave, int *total) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int incl = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(incl, off);
-    if (lane >= off) incl += o;
-  }
-  __syncthreads();
-  if (lane == 63) s_wave[wv] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int w = 0; w < A_WAVES; w++) { const int c = s_wave[w]; if (w < wv) before += c; all += c; }
-  *total = all;
-  return before + incl - v;
-}
-
-// the sum of counts[0 .. n) by the whole block (s_wave as above)
-__device__ __forceinline__ int area_block_sum_before(const int *__restrict__ counts, int n, int *s_wave) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int part = 0;
-  for (int b = tid; b < n; b += A_THREADS) part += counts[b];
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  __syncthreads();
-  if (lane == 0) s_wave[wv] = part;
-  __syncthreads();
-  int t = 0;
-  for (int w = 0; w < A_WAVES; w++) t += s_wave[w];
-  return t;
-}
-
 // The gate sweep.  grid = (ceil(n_q / 256), splits); a block's place in the list's order is blockIdx.y * gridDim.x + blockIdx.x.
 // EMIT == false: cnt_sq[split][q] = the pairs of the query in the split that are evaluated, block_cnt[block] = their sum.
 // EMIT == true (behind the other): off_sq[split][q] = where the query's run of the split starts in the list - the counts of the
 // blocks before this one plus those of the block's threads before this one -, pair_q / pair_t = the run, trains ascending
 template <bool EMIT>
-__global__ __launch_bounds__(A_THREADS) void area_sweep_kernel(AreaConst k, const AreaRec *__restrict__ qrec, const AreaRec *__restrict__ trec,
+__global__ __launch_bounds__(LS_THREADS) void area_sweep_kernel(AreaConst k, const AreaRec *__restrict__ qrec, const AreaRec *__restrict__ trec,
                                                                int *__restrict__ cnt_sq, int *__restrict__ block_cnt, int *__restrict__ off_sq,
                                                                int *__restrict__ pair_q, int *__restrict__ pair_t, int n_pairs) {
-  __shared__ AreaRec s_t[A_TILE];
-  __shared__ int s_wave[A_WAVES];
+  __shared__ AreaRec s_t[LS_TILE];
+  __shared__ int s_wave[LS_WAVES];
   const int tid = threadIdx.x;
-  const int q = blockIdx.x * A_THREADS + tid;
+  const int q = blockIdx.x * LS_THREADS + tid;
   const size_t at = (size_t)blockIdx.y * (size_t)k.n_q + (size_t)q;
   AreaRec r = overlap_nan_rec();                            // lanes past the list
   if (q < k.n_q) r = qrec[q];
   const AreaQuery aq = area_query(r);
   int pos = 0, end = 0;
   if (EMIT) {
-    const int base = area_block_sum_before(block_cnt, (int)(blockIdx.y * gridDim.x + blockIdx.x), s_wave);
+    const int base = block_sum_before(block_cnt, (int)(blockIdx.y * gridDim.x + blockIdx.x), s_wave);
     const int mine = q < k.n_q ? cnt_sq[at] : 0;
     int total;
-    pos = base + area_block_scan(mine, s_wave, &total);
+    pos = base + block_scan(mine, s_wave, &total);
     end = min(pos + mine, n_pairs);                      // (the counts say it already: no store leaves the list)
     if (q < k.n_q) off_sq[at] = pos;
   }
-  const int t_begin = min(k.n_t, (int)blockIdx.y * k.tiles_per_split * A_TILE);
-  const int t_end = min(k.n_t, t_begin + k.tiles_per_split * A_TILE);
+  const TrainRange range = train_range(k.n_t, k.tiles_per_split);
+  const int t_begin = range.begin, t_end = range.end;
   int c = 0;
-  for (int t0 = t_begin; t0 < t_end; t0 += A_TILE) {
-    const int n = min(A_TILE, t_end - t0);
+  for (int t0 = t_begin; t0 < t_end; t0 += LS_TILE) {
+    const int n = min(LS_TILE, t_end - t0);
     __syncthreads();
     if (tid < n) s_t[tid] = trec[t0 + tid];
     __syncthreads();
@@ -171,35 +114,35 @@ __global__ __launch_bounds__(A_THREADS) void area_sweep_kernel(AreaConst k, cons
   if (!EMIT) {
     if (q < k.n_q) cnt_sq[at] = c;
     int total;
-    area_block_scan(c, s_wave, &total);
+    block_scan(c, s_wave, &total);
     if (tid == 0) block_cnt[blockIdx.y * gridDim.x + blockIdx.x] = total;
   }
 }
 
 // the list's length, as two halves of 64 bits, next to the common counts (pinned)
-__global__ __launch_bounds__(A_THREADS) void area_total_kernel(const int *__restrict__ block_cnt, int n_blocks, int *__restrict__ counts_out) {
-  __shared__ unsigned long long s_wave[A_WAVES];
+__global__ __launch_bounds__(LS_THREADS) void area_total_kernel(const int *__restrict__ block_cnt, int n_blocks, int *__restrict__ counts_out) {
+  __shared__ unsigned long long s_wave[LS_WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   unsigned long long part = 0;
-  for (int b = tid; b < n_blocks; b += A_THREADS) part += (unsigned long long)block_cnt[b];
+  for (int b = tid; b < n_blocks; b += LS_THREADS) part += (unsigned long long)block_cnt[b];
   for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
   if (lane == 0) s_wave[wv] = part;
   __syncthreads();
   if (tid == 0) {
     unsigned long long t = 0;
-    for (int w = 0; w < A_WAVES; w++) t += s_wave[w];
+    for (int w = 0; w < LS_WAVES; w++) t += s_wave[w];
     counts_out[3] = (int)(unsigned)(t & 0xffffffffull); counts_out[4] = (int)(unsigned)(t >> 32);
   }
 }
 
 // One wave per listed pair.  The lanes take consecutive points of the box, row by row (a row is 1 .. 513 points); every point is
 // decided by the contract's expression.  pair_key = the bits of E when E < max_error (E >= 0: an error's order is the order of
-// its bits), A_NONE otherwise; pair_px = n_q_px, n_t_px, n_both
-__global__ __launch_bounds__(A_THREADS) void area_lattice_kernel(AreaConst k, const AreaRec *__restrict__ qrec, const AreaRec *__restrict__ trec,
+// its bits), LS_NONE otherwise; pair_px = n_q_px, n_t_px, n_both
+__global__ __launch_bounds__(LS_THREADS) void area_lattice_kernel(AreaConst k, const AreaRec *__restrict__ qrec, const AreaRec *__restrict__ trec,
                                                                  const int *__restrict__ pair_q, const int *__restrict__ pair_t, int n_pairs,
                                                                  unsigned long long *__restrict__ pair_key, int *__restrict__ pair_px) {
   const int lane = threadIdx.x & 63;
-  const int p = blockIdx.x * A_WAVES + (threadIdx.x >> 6);
+  const int p = blockIdx.x * LS_WAVES + (threadIdx.x >> 6);
   if (p >= n_pairs) return;                              // the whole wave
   const AreaQuery aq = area_query(qrec[pair_q[p]]);
   AreaPair g;
@@ -226,7 +169,7 @@ __global__ __launch_bounds__(A_THREADS) void area_lattice_kernel(AreaConst k, co
   }
   for (int off = 32; off > 0; off >>= 1) { cq += __shfl_xor(cq, off); ct += __shfl_xor(ct, off); cb += __shfl_xor(cb, off); }
   if (lane == 0) {
-    unsigned long long key = A_NONE;
+    unsigned long long key = LS_NONE;
     const int uni = cq + ct - cb;
     if (uni != 0) {
       const double E = 1.0 - (double)cb / (double)uni;
@@ -237,15 +180,16 @@ __global__ __launch_bounds__(A_THREADS) void area_lattice_kernel(AreaConst k, co
   }
 }
 
-// best_e / best_p[q] = the smallest (E, t) of the query's accepted pairs and its place in the list: the runs in split order, a run
-// in train order, strict comparisons - a tie stays with the lower train.  With one_to_one == 1 the error competes for the train
-__global__ __launch_bounds__(A_THREADS) void area_accept_kernel(AreaConst k, int splits, const int *__restrict__ cnt_sq, const int *__restrict__ off_sq,
-                                                                const unsigned long long *__restrict__ pair_key, const int *__restrict__ pair_t,
-                                                                int n_pairs, unsigned long long *__restrict__ best_e, int *__restrict__ best_p,
-                                                                unsigned long long *__restrict__ train_e) {
-  const int q = blockIdx.x * A_THREADS + threadIdx.x;
+// best_e / best_p / best_t[q] = the smallest (E, t) of the query's accepted pairs, its place in the list and its train (-1: none):
+// the runs in split order, a run in train order, strict comparisons - a tie stays with the lower train.  With one_to_one == 1 the
+// error competes for the train
+__global__ __launch_bounds__(LS_THREADS) void area_accept_kernel(AreaConst k, int splits, const int *__restrict__ cnt_sq, const int *__restrict__ off_sq,
+                                                                 const unsigned long long *__restrict__ pair_key, const int *__restrict__ pair_t,
+                                                                 int n_pairs, unsigned long long *__restrict__ best_e, int *__restrict__ best_p,
+                                                                 int *__restrict__ best_t, unsigned long long *__restrict__ train_e) {
+  const int q = blockIdx.x * LS_THREADS + threadIdx.x;
   if (q >= k.n_q) return;
-  unsigned long long e = A_NONE;
+  unsigned long long e = LS_NONE;
   int bp = -1;
   for (int s = 0; s < splits; s++) {
     const size_t at = (size_t)s * (size_t)k.n_q + (size_t)q;
@@ -255,96 +199,61 @@ __global__ __launch_bounds__(A_THREADS) void area_accept_kernel(AreaConst k, int
       if (key < e) { e = key; bp = p; }
     }
   }
-  best_e[q] = e; best_p[q] = bp;
-  if (bp >= 0 && k.one_to_one == 1) atomicMin(&train_e[pair_t[bp]], e);
+  const int t = bp >= 0 ? pair_t[bp] : -1;
+  best_e[q] = e; best_p[q] = bp; best_t[q] = t;
+  if (t >= 0 && k.one_to_one == 1) atomicMin(&train_e[t], e);
 }
 
-// ... and of the queries with that error on the train, the lowest index owns it
-__global__ __launch_bounds__(A_THREADS) void area_owner_kernel(AreaConst k, const unsigned long long *__restrict__ best_e, const int *__restrict__ best_p,
-                                                               const int *__restrict__ pair_t, const unsigned long long *__restrict__ train_e,
-                                                               int *__restrict__ train_q) {
-  const int q = blockIdx.x * A_THREADS + threadIdx.x;
-  if (q >= k.n_q) return;
-  const int p = best_p[q];
-  if (p < 0) return;
-  const int t = pair_t[p];
-  if (train_e[t] == best_e[q]) atomicMin(&train_q[t], q);
-}
+// What the compaction runs over: the queries (modes 0 and 1: a query's chosen pair) or the listed pairs (mode 2: the accepted ones)
+struct area_final {
+  int n_items, one_to_one;
+  const int *best_p, *best_t, *train_q;
+  const unsigned long long *pair_key;
+  // the list place of item i when it is emitted, -1 otherwise
+  __device__ int place(int i) const {
+    if (i >= n_items) return -1;
+    if (one_to_one == 2) return pair_key[i] != LS_NONE ? i : -1;
+    const int p = best_p[i];
+    if (p < 0) return -1;
+    return (one_to_one == 0 || train_q[best_t[i]] == i) ? p : -1;
+  }
+  __device__ bool operator()(int i) const { return place(i) >= 0; }
+};
 
-// What the compaction runs over: the queries (modes 0 and 1: a query's chosen pair) or the listed pairs (mode 2: the accepted ones).
-// The list place of item i when it is emitted, -1 otherwise
-__device__ __forceinline__ int area_final(const AreaConst &k, int i, int n_items, const int *best_p, const int *pair_t, const int *train_q,
-                                          const unsigned long long *pair_key) {
-  if (i >= n_items) return -1;
-  if (k.one_to_one == 2) return pair_key[i] != A_NONE ? i : -1;
-  const int p = best_p[i];
-  if (p < 0) return -1;
-  return (k.one_to_one == 0 || train_q[pair_t[p]] == i) ? p : -1;
-}
-
-__global__ __launch_bounds__(A_THREADS) void area_count_kernel(AreaConst k, int n_items, const int *__restrict__ best_p, const int *__restrict__ pair_t,
-                                                               const int *__restrict__ train_q, const unsigned long long *__restrict__ pair_key,
-                                                               int *__restrict__ block_counts) {
-  const bool emit = area_final(k, blockIdx.x * A_THREADS + threadIdx.x, n_items, best_p, pair_t, train_q, pair_key) >= 0;
-  const int c = __syncthreads_count(emit ? 1 : 0);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = c;
-}
-
-// Ordered compaction: a block's offset is the sum of the counts of the blocks before it, an item's slot the emitted items before it
-// in its block.  counts_out (pinned): emitted items, queries and trains in the common area
-__global__ __launch_bounds__(A_THREADS) void area_emit_kernel(AreaConst k, int n_items, const int *__restrict__ best_p, const int *__restrict__ pair_q,
-                                                              const int *__restrict__ pair_t, const int *__restrict__ train_q,
-                                                              const unsigned long long *__restrict__ pair_key, const int *__restrict__ pair_px,
-                                                              const int *__restrict__ block_counts, const int *__restrict__ cnt,
-                                                              mods_overlap_area_match *__restrict__ out, int *__restrict__ counts_out) {
-  __shared__ int s_wave[A_WAVES];
-  const int base = area_block_sum_before(block_counts, (int)blockIdx.x, s_wave);
-  const int p = area_final(k, blockIdx.x * A_THREADS + threadIdx.x, n_items, best_p, pair_t, train_q, pair_key);
-  int total;
-  const int slot = base + area_block_scan(p >= 0 ? 1 : 0, s_wave, &total);
+// The emit kernel of the ordered compaction.  counts_out (pinned): emitted items, queries and trains in the common area
+__global__ __launch_bounds__(LS_THREADS) void area_emit_kernel(area_final final, const int *__restrict__ pair_q, const int *__restrict__ pair_t,
+                                                               const int *__restrict__ pair_px, const int *__restrict__ block_counts,
+                                                               const int *__restrict__ cnt, mods_overlap_area_match *__restrict__ out,
+                                                               int *__restrict__ counts_out) {
+  __shared__ int s_wave[LS_WAVES];
+  const int p = final.place(blockIdx.x * LS_THREADS + threadIdx.x);
+  int upto;
+  const int slot = compact_slot(p >= 0, block_counts, s_wave, &upto);
   if (p >= 0) {
     mods_overlap_area_match m;
     m.q = pair_q[p]; m.t = pair_t[p];
-    m.E = __longlong_as_double((long long)pair_key[p]);
+    m.E = __longlong_as_double((long long)final.pair_key[p]);
     m.n_q_px = pair_px[3 * (size_t)p]; m.n_t_px = pair_px[3 * (size_t)p + 1]; m.n_both = pair_px[3 * (size_t)p + 2]; m.pad = 0;
     out[slot] = m;                                       // slot < the emitted items <= n_items, the room of `out`
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { counts_out[0] = base + total; counts_out[1] = cnt[0]; counts_out[2] = cnt[1]; }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) { counts_out[0] = upto; counts_out[1] = cnt[0]; counts_out[2] = cnt[1]; }
 }
 
-// nothing to evaluate (an empty list on either side, or no pair through the gates): no match, the common counts stand
-__global__ void area_empty_kernel(const int *__restrict__ cnt, int *__restrict__ counts_out) {
-  counts_out[0] = 0; counts_out[1] = cnt[0]; counts_out[2] = cnt[1];
-}
-
-// Every refusal of an area-overlap call that needs no device; fills the kernels' constants
-static int area_check(const mods_overlap_area_params *par, AreaConst *k) {
-  if (!par) { set_error("match_overlap_area: null argument"); return MODS_E_ARG; }
-  for (int i = 0; i < 9; i++)
-    if (!std::isfinite(par->H[i])) { set_error("match_overlap_area: H entry %d is not finite", i); return MODS_E_ARG; }
-  if (!(par->max_error > 0 && par->max_error <= 1)) { set_error("match_overlap_area: max_error %g (in (0, 1])", par->max_error); return MODS_E_ARG; }
-  if (par->one_to_one < 0 || par->one_to_one > 2) { set_error("match_overlap_area: one_to_one %d (0, 1 or 2)", par->one_to_one); return MODS_E_ARG; }
-  if (par->w1 < 0 || par->h1 < 0 || par->w2 < 0 || par->h2 < 0) {
-    set_error("match_overlap_area: negative image size (%d x %d, %d x %d)", par->w1, par->h1, par->w2, par->h2);
-    return MODS_E_ARG;
-  }
-  double d;
-  if (!invert3_adjugate(par->H, k->Hinv, &d)) { set_error("match_overlap_area: singular homography (determinant %g)", d); return MODS_E_ARG; }
-  for (int i = 0; i < 9; i++) k->H[i] = par->H[i];
+// Every refusal of an area-overlap call that needs no device, the parameters before the output; fills the kernels' constants
+static int area_check(const mods_overlap_area_params *par, const mods_overlap_area_match *out, int max_out, const int *n_out,
+                      const mods_overlap_counts *counts, AreaConst *k) {
+  const int rc = overlap_check_geom("match_overlap_area", par, [par] {
+    if (!(par->max_error > 0 && par->max_error <= 1)) { set_error("match_overlap_area: max_error %g (in (0, 1])", par->max_error); return MODS_E_ARG; }
+    if (par->one_to_one < 0 || par->one_to_one > 2) { set_error("match_overlap_area: one_to_one %d (0, 1 or 2)", par->one_to_one); return MODS_E_ARG; }
+    return MODS_OK;
+  }, &k->geo);
+  if (rc) return rc;
   k->n_q = k->n_t = 0;
   k->max_error = par->max_error;
   k->g = 0.9 * (1.0 - par->max_error);
   k->one_to_one = par->one_to_one;
-  k->area = par->w1 > 0 && par->h1 > 0 && par->w2 > 0 && par->h2 > 0;
-  k->w1 = (double)par->w1; k->h1 = (double)par->h1; k->w2 = (double)par->w2; k->h2 = (double)par->h2;
   k->tiles_per_split = 1;
-  return MODS_OK;
-}
-
-// the refusals that concern the output, behind those of the parameters
-static int area_check_out(const mods_overlap_area_match *out, int max_out, const int *n_out, const mods_overlap_counts *counts) {
-  if (!n_out || !counts || max_out < 0 || (max_out > 0 && !out)) { set_error("match_overlap_area: null argument"); return MODS_E_ARG; }
-  return MODS_OK;
+  return overlap_check_out("match_overlap_area", out, max_out, n_out, counts);
 }
 
 // The search of device lists; leaves the emitted items in c->oa_out and (items, common queries, common trains) in c->oa_count
@@ -353,32 +262,25 @@ static int area_check_out(const mods_overlap_area_match *out, int max_out, const
 static int area_run(mods_ctx *c, const mods_region *q_dev, const mods_region *t_dev, AreaConst k) {
   if (!c->oa_count.get()) { MODS_HIP_CHECK(c->oa_count.reserve(8)); }
   const size_t nq = (size_t)k.n_q, nt = (size_t)k.n_t, n = nq + nt;
-  const int qblocks = (k.n_q + A_THREADS - 1) / A_THREADS;
-  // splits of the train range, as overlap.hip chooses them: some 16 blocks per CU so that the last round is a small part of the sweep
-  const int n_tiles = (k.n_t + A_TILE - 1) / A_TILE;
-  int splits = std::max(1, std::min(n_tiles, (4096 + qblocks - 1) / std::max(qblocks, 1)));
-  if (c->o_splits > 0) splits = std::max(1, std::min(n_tiles, c->o_splits));
-  k.tiles_per_split = std::max(1, (n_tiles + splits - 1) / splits);
-  splits = std::max(1, (n_tiles + k.tiles_per_split - 1) / k.tiles_per_split);
+  const SweepGrid gr = sweep_grid(k.n_q, k.n_t, OVERLAP_TARGET_BLOCKS, c->o_splits);
+  const int qblocks = gr.qblocks, splits = gr.splits;
+  k.tiles_per_split = gr.tiles_per_split;
   const size_t np = nq * (size_t)splits, sblocks = (size_t)qblocks * (size_t)splits;
   MODS_HIP_CHECK(mods::reserve_scratch(c, c->oa_rec, 6 * (n + 1), 6 * (n + n / 4 + 1)));
-  MODS_HIP_CHECK(mods::reserve_scratch(c, c->oa_int, 2 + nt + nq + sblocks + 2 * np + 1, 2 + n + n / 4 + sblocks + 2 * np + 64));
+  MODS_HIP_CHECK(mods::reserve_scratch(c, c->oa_int, 2 + nt + 2 * nq + sblocks + 2 * np + 1, 2 + n + nq + n / 4 + sblocks + 2 * np + 64));
   AreaRec *rec = (AreaRec *)c->oa_rec.get();
-  int *cnt = c->oa_int, *train_q = cnt + 2, *best_p = train_q + nt, *sweep_cnt = best_p + nq, *cnt_sq = sweep_cnt + sblocks, *off_sq = cnt_sq + np;
+  int *cnt = c->oa_int, *train_q = cnt + 2, *best_p = train_q + nt, *best_t = best_p + nq, *sweep_cnt = best_t + nq;
+  int *cnt_sq = sweep_cnt + sblocks, *off_sq = cnt_sq + np;
   int *counts_out = c->oa_count.get();
   long long n_pairs = 0;
   {
     StageScope scope(c, MODS_STAGE_OVERLAP_AREA, (double)n * sizeof(mods_region));
     MODS_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int) * 2, c->stream));
-    if (k.n_q)
-      hipLaunchKernelGGL(area_pack_kernel, dim3(qblocks), dim3(A_THREADS), 0, c->stream, k, q_dev, k.n_q, 0, rec, cnt);
-    if (k.n_t)
-      hipLaunchKernelGGL(area_pack_kernel, dim3((k.n_t + A_THREADS - 1) / A_THREADS), dim3(A_THREADS), 0, c->stream, k, t_dev, k.n_t, 1,
-                         rec + nq, cnt);
+    overlap_pack<false>(c, k.geo, q_dev, k.n_q, t_dev, k.n_t, rec, cnt);
     if (k.n_q && k.n_t) {
-      hipLaunchKernelGGL((area_sweep_kernel<false>), dim3(qblocks, splits), dim3(A_THREADS), 0, c->stream, k, rec, rec + nq, cnt_sq, sweep_cnt,
+      hipLaunchKernelGGL((area_sweep_kernel<false>), dim3(qblocks, splits), dim3(LS_THREADS), 0, c->stream, k, rec, rec + nq, cnt_sq, sweep_cnt,
                          off_sq, (int *)nullptr, (int *)nullptr, 0);
-      hipLaunchKernelGGL(area_total_kernel, dim3(1), dim3(A_THREADS), 0, c->stream, sweep_cnt, (int)sblocks, counts_out);
+      hipLaunchKernelGGL(area_total_kernel, dim3(1), dim3(LS_THREADS), 0, c->stream, sweep_cnt, (int)sblocks, counts_out);
       MODS_HIP_CHECK(hipGetLastError());
     }
   }
@@ -392,13 +294,13 @@ static int area_run(mods_ctx *c, const mods_region *q_dev, const mods_region *t_
   }
   StageScope scope(c, MODS_STAGE_OVERLAP_AREA, 0.);
   if (n_pairs == 0) {
-    hipLaunchKernelGGL(area_empty_kernel, dim3(1), dim3(1), 0, c->stream, cnt, counts_out);
+    hipLaunchKernelGGL(overlap_empty_kernel, dim3(1), dim3(1), 0, c->stream, cnt, counts_out);
     MODS_HIP_CHECK(hipGetLastError());
     return MODS_OK;
   }
   const int npairs = (int)n_pairs;
   const int n_items = k.one_to_one == 2 ? npairs : k.n_q;
-  const int iblocks = (n_items + A_THREADS - 1) / A_THREADS;
+  const int iblocks = (n_items + LS_THREADS - 1) / LS_THREADS;
   const size_t npz = (size_t)npairs;
   MODS_HIP_CHECK(mods::reserve_scratch(c, c->oa_pair, 5 * npz + (size_t)iblocks + 1, 5 * (npz + npz / 4) + (size_t)iblocks + 64));
   MODS_HIP_CHECK(mods::reserve_scratch(c, c->oa_key, nt + nq + npz + 1, n + n / 4 + npz + npz / 4 + 1));
@@ -406,23 +308,21 @@ static int area_run(mods_ctx *c, const mods_region *q_dev, const mods_region *t_
   int *pair_q = c->oa_pair, *pair_t = pair_q + npz, *pair_px = pair_t + npz, *block_counts = pair_px + 3 * npz;
   unsigned long long *train_e = c->oa_key, *best_e = train_e + nt, *pair_key = best_e + nq;
   MODS_HIP_CHECK(hipMemsetAsync(pair_q, 0, sizeof(int) * 2 * npz, c->stream));   // every place is written below; a valid pair all the same
-  hipLaunchKernelGGL((area_sweep_kernel<true>), dim3(qblocks, splits), dim3(A_THREADS), 0, c->stream, k, rec, rec + nq, cnt_sq, sweep_cnt, off_sq,
+  hipLaunchKernelGGL((area_sweep_kernel<true>), dim3(qblocks, splits), dim3(LS_THREADS), 0, c->stream, k, rec, rec + nq, cnt_sq, sweep_cnt, off_sq,
                      pair_q, pair_t, npairs);
-  hipLaunchKernelGGL(area_lattice_kernel, dim3((npairs + A_WAVES - 1) / A_WAVES), dim3(A_THREADS), 0, c->stream, k, rec, rec + nq, pair_q, pair_t,
+  hipLaunchKernelGGL(area_lattice_kernel, dim3((npairs + LS_WAVES - 1) / LS_WAVES), dim3(LS_THREADS), 0, c->stream, k, rec, rec + nq, pair_q, pair_t,
                      npairs, pair_key, pair_px);
   if (k.one_to_one != 2) {
-    if (k.one_to_one == 1) {
-      MODS_HIP_CHECK(hipMemsetAsync(train_e, 0xff, sizeof(unsigned long long) * nt, c->stream));
-      MODS_HIP_CHECK(hipMemsetAsync(train_q, 0x7f, sizeof(int) * nt, c->stream));
-    }
-    hipLaunchKernelGGL(area_accept_kernel, dim3(qblocks), dim3(A_THREADS), 0, c->stream, k, splits, cnt_sq, off_sq, pair_key, pair_t, npairs, best_e,
-                       best_p, train_e);
+    if (k.one_to_one == 1) MODS_HIP_CHECK(overlap_owner_reset(c, train_e, train_q, nt));
+    hipLaunchKernelGGL(area_accept_kernel, dim3(qblocks), dim3(LS_THREADS), 0, c->stream, k, splits, cnt_sq, off_sq, pair_key, pair_t, npairs, best_e,
+                       best_p, best_t, train_e);
     if (k.one_to_one == 1)
-      hipLaunchKernelGGL(area_owner_kernel, dim3(qblocks), dim3(A_THREADS), 0, c->stream, k, best_e, best_p, pair_t, train_e, train_q);
+      hipLaunchKernelGGL(overlap_owner_kernel, dim3(qblocks), dim3(LS_THREADS), 0, c->stream, k.n_q, best_e, best_t, train_e, train_q);
   }
-  hipLaunchKernelGGL(area_count_kernel, dim3(iblocks), dim3(A_THREADS), 0, c->stream, k, n_items, best_p, pair_t, train_q, pair_key, block_counts);
-  hipLaunchKernelGGL(area_emit_kernel, dim3(iblocks), dim3(A_THREADS), 0, c->stream, k, n_items, best_p, pair_q, pair_t, train_q, pair_key, pair_px,
-                     block_counts, cnt, c->oa_out.get(), counts_out);
+  const area_final final{n_items, k.one_to_one, best_p, best_t, train_q, pair_key};
+  hipLaunchKernelGGL(compact_count_kernel<area_final>, dim3(iblocks), dim3(LS_THREADS), 0, c->stream, final, block_counts);
+  hipLaunchKernelGGL(area_emit_kernel, dim3(iblocks), dim3(LS_THREADS), 0, c->stream, final, pair_q, pair_t, pair_px, block_counts, cnt,
+                     c->oa_out.get(), counts_out);
   MODS_HIP_CHECK(hipGetLastError());
   return MODS_OK;
 }
@@ -447,8 +347,6 @@ static void area_greedy(std::vector<mods_overlap_area_match> &v, int n_q, int n_
 static int area_fetch(mods_ctx *c, const AreaConst &k, mods_overlap_area_match *out, int max_out, int *n_out, mods_overlap_counts *counts) {
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   int n = read_slot(c->oa_count, 0);
-  counts->n_q_common = read_slot(c->oa_count, 1);
-  counts->n_t_common = read_slot(c->oa_count, 2);
   const bool greedy = k.one_to_one == 2;
   if (greedy) {
     c->oa_host.resize((size_t)std::max(n, 0));
@@ -459,9 +357,7 @@ static int area_fetch(mods_ctx *c, const AreaConst &k, mods_overlap_area_match *
       n = (int)c->oa_host.size();
     }
   }
-  counts->n_matches = n;
-  const int lo = std::min(counts->n_q_common, counts->n_t_common);
-  counts->repeatability = lo > 0 ? (double)n / (double)lo : 0.;
+  overlap_fill_counts(c->oa_count, n, counts);
   *n_out = n;
   if (n > max_out) { set_error("match_overlap_area: output overflow: %d > %d", n, max_out); return MODS_E_CAPACITY; }
   if (n <= 0) return MODS_OK;
@@ -479,20 +375,16 @@ extern "C" {
 
 int mods_match_overlap_area(mods_ctx *c, const mods_region *q, int n_q, const mods_region *t, int n_t, const mods_overlap_area_params *par,
                             mods_overlap_area_match *out, int max_out, int *n_out, mods_overlap_counts *counts) {
-  if ((n_q > 0 && !q) || (n_t > 0 && !t)) { set_error("match_overlap_area: null argument"); return MODS_E_ARG; }
-  if (n_q < 0 || n_t < 0) { set_error("match_overlap_area: negative count (%d queries, %d trains)", n_q, n_t); return MODS_E_ARG; }
-  AreaConst k;
-  int rc = area_check(par, &k);
+  int rc = check_host_lists("match_overlap_area", q, n_q, t, n_t);
   if (rc) return rc;
-  if ((rc = area_check_out(out, max_out, n_out, counts))) return rc;
+  AreaConst k;
+  if ((rc = area_check(par, out, max_out, n_out, counts, &k))) return rc;
   k.n_q = n_q; k.n_t = n_t;
   if (!c) { set_error("match_overlap_area: null context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
-  const size_t n = (size_t)n_q + (size_t)n_t;
-  MODS_HIP_CHECK(mods::reserve_scratch(c, c->oa_regs, n + 1, n + n / 4 + 1));
-  if (n_q) MODS_HIP_CHECK(hipMemcpyAsync(c->oa_regs, q, sizeof(mods_region) * (size_t)n_q, hipMemcpyHostToDevice, c->stream));
-  if (n_t) MODS_HIP_CHECK(hipMemcpyAsync(c->oa_regs + n_q, t, sizeof(mods_region) * (size_t)n_t, hipMemcpyHostToDevice, c->stream));
-  if ((rc = area_run(c, c->oa_regs, c->oa_regs + n_q, k))) return rc;
+  const mods_region *q_dev, *t_dev;
+  if ((rc = stage_lists(c, q, n_q, t, n_t, &q_dev, &t_dev))) return rc;
+  if ((rc = area_run(c, q_dev, t_dev, k))) return rc;
   return area_fetch(c, k, out, max_out, n_out, counts);
 }
 
@@ -500,9 +392,8 @@ int mods_match_overlap_area_reps(mods_ctx *c, const mods_imgrep *q, const mods_i
                                  mods_overlap_area_match *out, int max_out, int *n_out, mods_overlap_counts *counts) {
   if (!q || !t) { set_error("match_overlap_area: null argument"); return MODS_E_ARG; }
   AreaConst k;
-  int rc = area_check(par, &k);
+  int rc = area_check(par, out, max_out, n_out, counts, &k);
   if (rc) return rc;
-  if ((rc = area_check_out(out, max_out, n_out, counts))) return rc;
   if (!c) { set_error("match_overlap_area: null context"); return MODS_E_ARG; }
   k.n_q = mods_imgrep_count(q); k.n_t = mods_imgrep_count(t);   // (the banks are read only behind every refusal)
   MODS_HIP_CHECK(hipSetDevice(c->device));

@@ -76,6 +76,43 @@ def test_overlap_splits_refusals(pkg):
     assert pkg.lib().mods_ctx_overlap_splits(None, 0) == -2 and pkg.lib().mods_ctx_overlap_splits(BUF, -1) == -2
 
 
+def _grid_formula(search, n_q, n_t, forced):
+    """the split plan as the three searches wrote it out before they shared it: ceil(n_q / 256) query blocks, as many splits of the
+    256-train tiles as bring the grid to 2048 (guided) or 4096 (overlap, area-overlap) blocks unless the overlap knob forces a count,
+    and the split count that the tiles per split leave.  (The guided search returned before this arithmetic when a list was empty;
+    there the guards of the other two stand in.)"""
+    qblocks, n_tiles = (n_q + 255) // 256, (n_t + 255) // 256
+    splits = max(1, min(n_tiles, ((2048 if search == 0 else 4096) + qblocks - 1) // max(qblocks, 1)))
+    if search == 1 and forced > 0:
+        splits = max(1, min(n_tiles, forced))
+    tiles_per_split = max(1, (n_tiles + splits - 1) // splits)
+    return qblocks, max(1, (n_tiles + tiles_per_split - 1) // tiles_per_split), tiles_per_split
+
+
+def test_list_search_grid(pkg):
+    """mods_list_search_grid: the sweeps' split plan.  No result depends on it, the speed of the sweeps does
+    (profiles/overlap_area_timing.txt: 7.0 ms with 1 split, 4.3 ms with 16), so the choice is pinned here"""
+    GUIDED, OVERLAP = 0, 1
+    for search, n_q, n_t, forced, want in [(OVERLAP, 5000, 4099, 0, (20, 17, 1)), (OVERLAP, 5000, 4099, 3, (20, 3, 6)),
+                                           (OVERLAP, 60156, 47177, 0, (235, 17, 11)), (GUIDED, 60156, 47177, 0, (235, 9, 21)),
+                                           (OVERLAP, 0, 5, 0, (0, 1, 1))]:
+        assert pkg.list_search_grid(search, n_q, n_t, forced) == want == _grid_formula(search, n_q, n_t, forced)
+    for search in (GUIDED, OVERLAP):
+        for n_q in (0, 1, 256, 257, 5000, 60156):
+            for n_t in (0, 1, 256, 257, 4099, 47177):
+                for forced in (0, 1, 3, 1000):
+                    got = pkg.list_search_grid(search, n_q, n_t, forced)
+                    assert got == _grid_formula(search, n_q, n_t, forced), (search, n_q, n_t, forced)
+                    # every train lies in a split and no split is empty
+                    assert got[1] >= 1 and got[2] >= 1 and (got[1] - 1) * got[2] * 256 < max(n_t, 1) <= got[1] * got[2] * 256
+    assert pkg.list_search_grid(GUIDED, 300, 257, 7) == pkg.list_search_grid(GUIDED, 300, 257)      # the guided search has no knob
+    lib = pkg.lib()
+    out = (C.c_int * 3)()
+    for args in ((2, 5, 5, 0), (-1, 5, 5, 0), (1, -1, 5, 0), (1, 5, -1, 0), (1, 5, 5, -1)):
+        assert lib.mods_list_search_grid(*args, out) == -2 and lib.mods_last_error().startswith(b"list_search_grid: ")
+    assert lib.mods_list_search_grid(1, 5, 5, 0, None) == -2
+
+
 def test_overlap_layouts_and_defaults(pkg):
     assert C.sizeof(pkg.OverlapParams) == 72 + 8 + 6 * 4           # 9 doubles, a double, 6 ints
     assert C.sizeof(pkg.OverlapCounts) == 16 + 8                   # 3 ints + pad, a double

@@ -117,6 +117,61 @@ def test_tile_tails(pkg, gpu_ctx, n_q, n_t, mode):
             assert len(check(pkg, gpu_ctx, q1, t1, H_PROJ.reshape(9), radius=0.5)[0]) == 1
 
 
+def _same_bits(got, want, what):
+    """two answers of one search, part by part: every field of every row to the bit, and the counts of the overlap searches"""
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        if not isinstance(g, np.ndarray):
+            assert (g.n_q_common, g.n_t_common, g.n_matches) == (w.n_q_common, w.n_t_common, w.n_matches), what
+            assert np.float64(g.repeatability).view(np.uint64) == np.float64(w.repeatability).view(np.uint64), (what, "repeatability bits")
+            continue
+        assert g.shape == w.shape, (what, g.shape, w.shape)
+        for f in g.dtype.names or (slice(None),):
+            assert g[f].dtype == w[f].dtype and g[f].tobytes() == w[f].tobytes(), (what, f)
+
+
+def test_searches_interleaved_on_one_context(pkg):
+    """the three searches of two host lists alternate on one context, with list lengths that grow and shrink: they stage their lists
+    in one buffer (csrc/list_search.hpp), which is so reallocated and reused between different searches.  Every answer equals the
+    answer of the same call alone on a fresh context and the numpy reference"""
+    import overlap_area_ref as oar
+    import overlap_ref as orf
+
+    def guided(n_q, n_t):
+        q, t = scene(np.random.default_rng(100 + n_q + n_t), n_q, n_t, H_PROJ)        # (the scenes of test_tile_tails)
+        p, a = params(pkg, H_PROJ.reshape(9), radius=6.0, one_to_one=1)
+        return (lambda ctx: ctx.match_guided(q, t, p)), ref_of(q, t, H_PROJ.reshape(9), a), 0 if n_q < 300 else 10
+
+    def overlap(n_q, n_t):
+        q, t = orf.scene(np.random.default_rng(100 + n_q + n_t), n_q, n_t)
+        p = pkg.OverlapParams.default(H_PROJ, one_to_one=1, w1=400, h1=300, w2=400, h2=300)
+        want = orf.overlap_ref(q, t, orf.params(H_PROJ, one_to_one=1, w1=400, h1=300, w2=400, h2=300))
+        return (lambda ctx: ctx.match_overlap(q, t, p)), want, 0
+
+    def area(seed, n_q, n_t, mode):
+        q, t = orf.scene(np.random.default_rng(seed), n_q, n_t)
+        p = pkg.OverlapAreaParams.default(H_PROJ, one_to_one=mode)
+        return (lambda ctx: ctx.match_overlap_area(q, t, p)), oar.overlap_area_ref(q, t, oar.params(H_PROJ, 0.4, mode)), 10
+
+    first = [guided(300, 257), overlap(63, 65), area(7, 257, 131, 1)]
+    calls = first + [guided(5000, 4099), overlap(1, 1), area(11, 300, 301, 2)] + first
+    alone = []
+    for call, want, least in calls[:6]:
+        ctx = pkg.Context(0, 640, 480, 1)
+        try:
+            alone.append(call(ctx))
+        finally:
+            ctx.close()
+        assert len(alone[-1][0]) >= least                            # (an empty answer cannot pass)
+        _same_bits(alone[-1], want, "call %d alone against the reference" % len(alone))
+    ctx = pkg.Context(0, 640, 480, 1)
+    try:
+        for i, (call, want, _) in enumerate(calls):
+            _same_bits(call(ctx), alone[i % 6], "call %d of the sequence" % i)
+    finally:
+        ctx.close()
+
+
 def test_h_exact_boundaries(pkg, gpu_ctx):
     """translation by (3, 4) or (-5, 12) on a quarter-pixel lattice: every product and sum of the gate is exact, so many pairs sit
     exactly at distance r (3-4-5 and 5-12-13 offsets) - the <= of the forward and of the backward test decides them"""
