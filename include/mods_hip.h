@@ -430,7 +430,8 @@ typedef struct mods_ransac_params {
   int errorType;            /* 0 */
   int doSymmCheck;          /* 1 */
   int useF;                 /* 0: homography (ver_type "Homog"), 1: epipolar geometry (DEGENSAC, ver_type "Epipolar"),
-                             * 2: epipolar geometry verified by ORSA (RANSAC_mode_t ORSA; mods_orsa_f) */
+                             * 2: epipolar geometry verified by ORSA (RANSAC_mode_t ORSA; mods_orsa_f),
+                             * 3: homography verified by ORSA-H (mods_orsa_h); mods_model_kind() tells H from F */
   /* ver_type 1 of the command line (GR_TRUTH, mods.cpp:290-320): verification against a known homography.
    * groundTruth 0: off; 1: HMatrixFiltering of the tentatives only; 2: doBothRANSACgroundTruth - LORANSACFiltering first, then
    * HMatrixFiltering of its inliers (the verified list), next to HMatrixFiltering of all tentatives for the log. */
@@ -491,6 +492,57 @@ int mods_test_orsa_score(const float *p1, const float *p2, int n, int w, int h, 
 /* the device's (float)log10((double)x) against glibc's for the float bit patterns [begin, begin + count): the number of
  * mismatches (< 0: MODS_E_*), the first max_list of them in list */
 long long mods_test_orsa_log10_sweep(unsigned begin, unsigned count, unsigned *list, int max_list);
+
+/* ORSA-H, useF = 3: a-contrario homography verification after Moisan, Moulon, Monasse, "Automatic Homographic Registration of a
+ * Pair of Images, with A Contrario Elimination of Outliers", IPOL 2012.  The reference tree has no such verifier: the contract is
+ * this project's own, stated here, restated in numpy in tests/orsa_h_ref.py and pinned to the bit between the device and the host
+ * path (parity with the IPOL code unpinned).  Arguments as mods_orsa_f; the model maps image 1 (u6[0..1]) to image 2 (u6[3..4]).
+ * n < 8: no model, MODS_OK.
+ *  - Normalisation as orsa(): norm = 1 / (float)sqrt(nx ny), points centred by half the size, scaled, stored as float.
+ *  - Sampling: 4 raw rand() values of glibc's generator per iteration (seeded as mods_orsa_f: mods_ransac_pin_seed /
+ *    MODS_RANSAC_SEED), mapped to 4 distinct indices the way random_p7 maps 7, over the current (nid, id).
+ *  - Minimal solve: the 8 x 8 system of the 4 correspondences with h33 = 1, rows (x, y, 1, 0, 0, 0, -ux, -uy | u) and
+ *    (0, 0, 0, x, y, 1, -vx, -vy | v), fp64 Gaussian elimination with partial pivoting (the first largest magnitude wins), fixed
+ *    operation order, no contraction, rounded to 9 floats.  A zero (or NaN) pivot or a non-finite entry: the model is invalid.
+ *  - Error of correspondence i: the squared distance in image 2 between H p1 (after the projective division) and p2, in double
+ *    from the float operands, rounded to float; its bits are the sort key.  A NaN error makes the model invalid, +inf is an
+ *    ordinary key.  An invalid model scores nfa = 10000, imin = 0.
+ *  - NFA over the sorted errors e_i, 0-based 4 <= i < n, in float: la = logalpha0 + (float)log10((double)max(e_i, FLT_MIN)),
+ *    nfa = loge0 + la (float)(i - 3) + logcn[i + 1] + logc4[i + 1], logalpha0 = (float)log10(pi) (the normalised image has area 1;
+ *    the log of a squared point error enters with multiplier 1), loge0 = (float)log10((double)(n - 4)), logcn[m] = logcombi(m, n),
+ *    logc4[m] = logcombi(4, m).  The lowest i among equal values wins.
+ *  - Control loop: orsa()'s, t = 10000, maxniter = t - t / 10; one model per iteration; a record below 0 - or the last iteration,
+ *    where a record exists - starts the optimisation phase, which samples from the record's subset for t / 10 more iterations.  The
+ *    subset is the first imin + 1 indices of the errors sorted stably by (error, index).
+ *  - Final refit: one least-squares model (u2h) from the record's subset, rounded to 9 floats, scored like any other; it replaces
+ *    the record only where its NFA is lower.
+ * When log_nfa < -2: H_out row-major, image 1 to image 2, in pixels (T^-1 h T in double); *thr_px = sqrt(e_imin) / norm, the
+ * data-driven inlier threshold in pixels; index_out / *n_index = the subset in sorted order; mask = 1 on the subset, then - laf
+ * given and HLAFCoef > 0 - H_LAF_check with bound HLAFCoef * thr_px, cleared below 8.  Otherwise H_out is all -1 and the mask
+ * empty.  log_nfa: 10000 when nothing was scored.  stats3 = {iterations, models scored, rewinds}. */
+int mods_orsa_h(const double *u6, const double *laf, int n, int w, int h, const mods_ransac_params *par, unsigned char *mask,
+                double *H_out, int *n_inliers, float *log_nfa, double *thr_px, int *index_out, int *n_index, int *stats3);
+/* the same with the scoring back end chosen, as mods_orsa_f_ex: on_device 0 = the host path (no device needed), which runs the
+ * same solver and error function.  Results do not depend on batch, wg_keys or MODS_RANSAC_THREADS.  mods_orsa_last_profile
+ * reports these calls too (ms5[0]: the mapping of the samples; the solves run inside the scoring kernel). */
+int mods_orsa_h_ex(const double *u6, const double *laf, int n, int w, int h, const mods_ransac_params *par, unsigned char *mask,
+                   double *H_out, int *n_inliers, float *log_nfa, double *thr_px, int *index_out, int *n_index, int *stats3,
+                   int on_device, int batch, int wg_keys);
+/* the refit of the calling thread's last mods_orsa_h[_ex] call: the loop's best NFA, the refit model's (10000: none scored or
+ * invalid), and whether it replaced the record */
+int mods_orsa_h_last_refit(float *nfa_loop, float *nfa_refit, int *taken);
+/* log_nfa and thr_px (0 when not significant) of the calling thread's last mods_orsa_h[_ex] call, for callers that reach it
+ * through the pair, pipeline or ladder entry points (the command line's verbose report) */
+int mods_orsa_h_last_threshold(double *thr_px, float *log_nfa);
+/* self-test hooks: the tables logcn, logc4 of n (n + 1 entries each); the solve and scoring of m samples (samples4: m x 4 distinct
+ * indices below n) over the normalised points p1 / p2 (n x 2 floats, image 1 / 2; n >= 5), through the device kernel (on_device 1)
+ * or the host path: out4 per model = {nfa bits, first argmin, logalpha bits, invalid flag}, H_out9 = the m solved models */
+int mods_test_orsa_h_tables(int n, float *logcn, float *logc4);
+int mods_test_orsa_h_score(const float *p1, const float *p2, int n, int w, int h, const int *samples4, int m, int on_device,
+                           int wg_keys, int *out4, float *H_out9);
+/* the model a value of mods_ransac_params.useF verifies: 0 = homography (useF 0, 3), 1 = fundamental matrix (useF 1, 2),
+ * MODS_E_ARG for any other value */
+int mods_model_kind(int useF);
 /* The verification half of one step of the reference's loop (mods.cpp:278-368), in place on (tent, u6, laf):
  *   par->dup_before_ransac = 1 ([DuplicateFiltering] doBeforeRANSAC): DuplicateFiltering (mods.cpp:283), then LORANSACFiltering;
  *   par->dup_before_ransac = 0: LORANSACFiltering on every tentative, then DuplicateFiltering on the verified list
@@ -503,8 +555,8 @@ int mods_verify_tentatives(int device, const struct mods_pair_params *par, mods_
 /* the same with the three ground-truth counts of mods_ladder_result (gt3, may be NULL; zeros outside ground-truth mode) */
 int mods_verify_tentatives_ex(int device, const struct mods_pair_params *par, mods_tentative *tent, double *u6, double *laf, int n,
                               int *n_unique, int *n_verified, double *H_out, int *stats3, int *gt3, double *ms_dup, double *ms_ransac);
-/* the same with the image size (w, h) that useF = 2 (ORSA, mods_orsa_f) needs; the two calls above have none and return MODS_E_ARG
- * for useF = 2.  mods_match_pair_dev and the pipeline pass their frame size. */
+/* the same with the image size (w, h) that useF = 2 and 3 (ORSA: mods_orsa_f, mods_orsa_h) need; the two calls above have none and
+ * return MODS_E_ARG for them.  mods_match_pair_dev and the pipeline pass their frame size. */
 int mods_verify_tentatives_wh(int device, const struct mods_pair_params *par, mods_tentative *tent, double *u6, double *laf, int n,
                               int w, int h, int *n_unique, int *n_verified, double *H_out, int *stats3, int *gt3, double *ms_dup,
                               double *ms_ransac);

@@ -973,6 +973,61 @@ def orsa_f(u6, laf, w, h, params=None, seed_time=12345, on_device=True, batch=0,
                 stats=list(stats))
 
 
+def orsa_h(u6, laf, w, h, params=None, seed_time=12345, on_device=True, batch=0, wg_keys=0):
+    """ORSA-H (useF = 3): a-contrario homography verification, samples solved and scored on the GPU (on_device=False: the host
+    path, no device needed).  Returns dict(mask, H row-major img1 -> img2 in pixels, n, log_nfa, thr_px, index, stats, refit)
+    with refit = (the loop's nfa, the refit model's nfa, taken)."""
+    params = params or RansacParams.default(useF=3)
+    if seed_time is not None:
+        ransac_pin_seed(seed_time)
+    u = np.ascontiguousarray(u6, np.float64)
+    if u.ndim != 2 or u.shape[1] != 6:
+        raise ValueError("u6 must be n x 6 (x1 y1 1 x2 y2 1)")
+    n = len(u)
+    lf = np.ascontiguousarray(laf, np.float64) if laf is not None else None
+    if lf is not None and lf.shape != (n, 14):
+        raise ValueError("laf must be n x 14")
+    mask = np.zeros(max(n, 1), np.uint8)
+    H = np.zeros(9, np.float64)
+    index = np.zeros(max(n, 1), np.int32)
+    ninl, nidx, nfa, thr = C.c_int(), C.c_int(), C.c_float(), C.c_double()
+    stats = (C.c_int * 3)()
+    _check(lib().mods_orsa_h_ex(u.ctypes.data_as(C.c_void_p), lf.ctypes.data_as(C.c_void_p) if lf is not None else None, n,
+                                int(w), int(h), C.byref(params), mask.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p),
+                                C.byref(ninl), C.byref(nfa), C.byref(thr), index.ctypes.data_as(C.c_void_p), C.byref(nidx), stats,
+                                1 if on_device else 0, int(batch), int(wg_keys)))
+    a, b, taken = C.c_float(), C.c_float(), C.c_int()
+    _check(lib().mods_orsa_h_last_refit(C.byref(a), C.byref(b), C.byref(taken)))
+    return dict(mask=mask[:n].astype(bool), H=H, n=ninl.value, log_nfa=np.float32(nfa.value), thr_px=thr.value,
+                index=index[:nidx.value].copy(), stats=list(stats), refit=(np.float32(a.value), np.float32(b.value), taken.value))
+
+
+def orsa_h_test_tables(n):
+    a, b = np.zeros(n + 1, np.float32), np.zeros(n + 1, np.float32)
+    _check(lib().mods_test_orsa_h_tables(int(n), _fp(a), _fp(b)))
+    return a, b
+
+
+def orsa_h_test_score(p1, p2, w, h, samples4, on_device=True, wg_keys=0):
+    """per-sample (nfa bits, first argmin, logalpha bits, invalid flag) and the solved models (m x 9 float32) of samples4
+    (m x 4 indices) over normalised points p1 / p2 (n x 2 float32 each, flattened)"""
+    p1 = np.ascontiguousarray(p1, np.float32).reshape(-1); p2 = np.ascontiguousarray(p2, np.float32).reshape(-1)
+    s = np.ascontiguousarray(samples4, np.int32).reshape(-1, 4)
+    out = np.zeros((len(s), 4), np.int32)
+    Hs = np.zeros((len(s), 9), np.float32)
+    _check(lib().mods_test_orsa_h_score(_fp(p1), _fp(p2), len(p1) // 2, int(w), int(h), s.ctypes.data_as(C.c_void_p), len(s),
+                                        1 if on_device else 0, int(wg_keys), out.ctypes.data_as(C.c_void_p), _fp(Hs)))
+    return out, Hs
+
+
+def model_kind(useF):
+    """0: useF verifies a homography (0, 3); 1: a fundamental matrix (1, 2)"""
+    kind = lib().mods_model_kind(int(useF))
+    if kind < 0:
+        _check(kind)
+    return kind
+
+
 def orsa_last_profile():
     """ms of the calling thread's last orsa_f call: solve, score, kernel, replay, total; and the scoring launches."""
     ms = (C.c_double * 5)()
@@ -1025,7 +1080,7 @@ def orsa_log10_sweep(begin, count, max_list=1024):
 def verify_tentatives(tent, u6, laf, params, device=0, seed_time=None, wh=None):
     """mods_verify_tentatives: duplicate filtering + LORANSACFiltering in the order [DuplicateFiltering] doBeforeRANSAC asks for
     (mods.cpp:278-368).  Returns (verified tentatives, their u6, their laf, n_unique, H, stats).  wh = (w, h): the image size,
-    required by useF = 2 (ORSA; mods_verify_tentatives_wh)."""
+    required by useF = 2 and 3 (ORSA F and H; mods_verify_tentatives_wh)."""
     if seed_time is not None:
         ransac_pin_seed(seed_time)
     tent = np.ascontiguousarray(tent).copy()

@@ -6,7 +6,7 @@
 //   argv layout        getCLIparam, io_mods.cpp:558-603 (Tmin = 9, io_mods.h:13):
 //       mods img1 img2 out1 out2 k1 k2 matchings log [logOnly] [ver_type] [H/F file] [config.ini] [iters.ini]
 //            [read_pre_extracted] [match_one_to_many]
-//       ver_type 0 = LO-RANSAC homography, 1 = ground-truth homography (the H file is read), 2 = LO-RANSAC epipolar (3 = ORSA: not built)
+//       ver_type 0 = LO-RANSAC homography, 1 = ground-truth homography (the H file is read), 2 = LO-RANSAC epipolar ([RANSAC] aContrario = 1: ORSA-H under 0, ORSA F under 2; 3 is rejected)
 //   configuration      the [HessianAffine], [DominantOrientation], [SIFTDescriptor], [Matching], [DuplicateFiltering],
 //                      [RANSAC], [TextOutput], [Computing] keys of io_mods.cpp:160-207, 423-455, 605-740 and the
 //                      [Iterations] / [HessianAffine<i>] sections of the iterations file (:457-492)
@@ -208,7 +208,11 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   r.doSymmCheck = (int)ini.GetInteger("RANSAC", "doSymmCheck", 0);
   const std::string et = ini.GetStringVector("RANSAC", "ErrorType")[0];
   r.errorType = et == "Sampson" ? 0 : et == "SymmMax" ? 1 : 2;
-  r.useF = ver_type == 2 ? 1 : 0;
+  // [RANSAC] aContrario = 1 (this project's key): the threshold-free a-contrario verifier of the chosen model, ORSA-H (useF = 3)
+  // under ver_type 0 and ORSA F (useF = 2) under ver_type 2; err_threshold then only bounds the LAF check of ORSA F
+  const long a_contrario = ini.GetInteger("RANSAC", "aContrario", 0);
+  if (a_contrario != 0 && a_contrario != 1) { std::cerr << "[RANSAC] aContrario must be 0 or 1" << std::endl; return 1; }
+  r.useF = ver_type == 2 ? (a_contrario ? 2 : 1) : (a_contrario ? 3 : 0);
   // GR_TRUTH (mods.cpp:85-87, 290-320, 381-383; io_mods.cpp:340-341): with doBothRANSACgroundTruth the verified list is the
   // LORANSAC inliers that the ground truth confirms, RANSACforStopping stops the step loop on the RANSAC inlier count
   r.groundTruth = ver_type == 1 ? (ini.GetInteger("Matching", "doBothRANSACgroundTruth", 1) ? 2 : 1) : 0;
@@ -702,7 +706,7 @@ int main(int argc, char **argv) {
     ver_type = atoi(argv[Tmin + 1]);
     if (ver_type != 0 && ver_type != 1 && ver_type != 2) {
       std::cerr << ver_type << " is wrong correspondence verification type." << std::endl
-                << "Try 0 for LO-RANSAC(homography), 1 for ground truth matrix or 2 for LO-RANSAC(epipolar) (3, ORSA, is not part of this build)" << std::endl;
+                << "Try 0 for LO-RANSAC(homography), 1 for ground truth matrix or 2 for LO-RANSAC(epipolar) (3 is not taken: [RANSAC] aContrario = 1 selects ORSA under 0 or 2)" << std::endl;
       return 1;
     }
     if (ver_type == 1 && argc < Tmin + 3) {   // io_mods.cpp:594-599
@@ -717,6 +721,7 @@ int main(int argc, char **argv) {
   Config cfg;
   memset(&cfg.pair, 0, sizeof(cfg.pair));
   if (read_config(config_fn, iters_fn, ver_type, &cfg)) return 1;
+  const bool model_is_f = mods_model_kind(cfg.pair.ransac.useF) == 1;   // the verified model: F (useF 1, 2) or H (0, 3)
   if (ver_type == 1) {   // mods.cpp:89-104: the file holds the matrix row by row
     std::ifstream gf(argv[Tmin + 2]);
     double *g = cfg.pair.ransac.gtH;
@@ -878,7 +883,7 @@ int main(int argc, char **argv) {
     else if (cfg.guided && have_model && !all_m1) {
       mods_guided_params gp;
       memset(&gp, 0, sizeof(gp));
-      gp.model_type = cfg.pair.ransac.useF ? 1 : 0;
+      gp.model_type = model_is_f ? 1 : 0;
       for (int i = 0; i < 9; i++) gp.model[i] = res.H[i];
       gp.radius = cfg.guided_radius; gp.ratio = cfg.guided_ratio; gp.contradDist = cfg.pair.contradDist;
       gp.max_dist = cfg.guided_max_dist; gp.one_to_one = cfg.guided_one_to_one;
@@ -922,7 +927,14 @@ int main(int argc, char **argv) {
         std::cerr << "Now RANSAC" << std::endl << res.gt_ransac_inliers << " RANSAC matches are identified" << std::endl
                   << res.gt_true_of_ransac << " RANSAC true matches are identified" << std::endl;
     } else {
-      std::cerr << (cfg.pair.ransac.useF ? "LO-RANSAC(epipolar)" : "LO-RANSAC(homography)") << " verification is used..." << std::endl;
+      static const char *const verifier[4] = {"LO-RANSAC(homography)", "LO-RANSAC(epipolar)", "ORSA(epipolar)", "ORSA(homography)"};
+      std::cerr << verifier[cfg.pair.ransac.useF] << " verification is used..." << std::endl;
+      if (cfg.pair.ransac.useF == 3 && !multi) {
+        double thr_px = 0;
+        float log_nfa = 0;
+        if (!mods_orsa_h_last_threshold(&thr_px, &log_nfa))
+          std::cerr << "ORSA(homography): log10(nfa) = " << log_nfa << ", inlier threshold = " << thr_px << " px" << std::endl;
+      }
       std::cerr << res.n_inliers << " RANSAC correspondences got" << std::endl;
     }
     if (n_guided >= 0) std::cerr << "Guided matching (radius " << cfg.guided_radius << ", ratio " << cfg.guided_ratio << "): " << n_guided
@@ -945,7 +957,7 @@ int main(int argc, char **argv) {
            << final_step << " " << std::endl;
       } else {
         lf << std::setprecision(3) << final_time << " " << res.n_inliers << " " << res.n_unique << " " << ratio * 100 << " ";
-        if (cfg.pair.ransac.useF) lf << res.n_described[0] << " " << res.n_described[1] << " ";
+        if (model_is_f) lf << res.n_described[0] << " " << res.n_described[1] << " ";
         else lf << res.n_unoriented[0] << " " << res.n_unoriented[1] << " ";
         lf << final_step << " " << std::endl;
       }
@@ -980,8 +992,8 @@ int main(int argc, char **argv) {
       mods_draw_matches_params dp;
       memset(&dp, 0, sizeof(dp));
       dp.draw_only_centers = cfg.draw_only_centers;
-      dp.reproject_to_one_image = !cfg.pair.ransac.useF && cfg.draw_reprojected;
-      dp.draw_epipolar_lines = cfg.pair.ransac.useF && cfg.draw_epipolar;
+      dp.reproject_to_one_image = !model_is_f && cfg.draw_reprojected;
+      dp.draw_epipolar_lines = model_is_f && cfg.draw_epipolar;
       for (int i = 0; i < 9; i++) dp.M[i] = res.H[i];
       {   // without a usable model (no verified match: H is all -1, singular) the centres are drawn side by side
         const double *H = res.H;

@@ -5,6 +5,7 @@
 #include "detmath.hpp"
 #include "ransac_host.hpp"
 #include "f_laf.hpp"
+#include "h_laf.hpp"
 #include "../../include/mods_degensac.h"
 #include <cstdarg>
 #include <memory>
@@ -986,6 +987,72 @@ static bool invert3(const double *S, double *t) {
   return true;
 }
 
+}  // extern "C"
+
+namespace mods {
+// H_LAF_check (matching.cpp:250-308), shared by mods_loransac_h and mods_orsa_h: correspondence i of cur survives when the
+// symmetric transfer errors (HDsSymMax) of its centre and of the two frame points k_sigma along the local affine frame's axes sum
+// to at most bound^2.  H21: the model from image 2 to image 1, row-major (its inverse is taken here, as the error function takes
+// it); laf: n x 14 frames; bound <= 0 or laf == NULL: nothing is checked.  ops = the host SIMD table, evaluated lanes-wide over
+// structure-of-arrays copies (every lane does the scalar code's operations in its order: the same bits); nullptr: the scalar
+// statement.
+void h_laf_check(const double *laf, const double *H21, double bound, const rs::SimdOps *ops, std::vector<int> &cur) {
+  if (!(bound > 0) || !laf) return;
+  const double ks = 3.0;   // matching.cpp:171
+  const double Hd[9] = {H21[0], H21[3], H21[6], H21[1], H21[4], H21[7], H21[2], H21[5], H21[8]};   // degensac's layout
+  if (ops) {
+    const int m = (int)cur.size();
+    if (m == 0) return;
+    const int m_pad = (m + rs::SIMD_PAD - 1) / rs::SIMD_PAD * rs::SIMD_PAD;
+    std::vector<double> buf((size_t)7 * m_pad);
+    double *c0 = buf.data(), *c1 = c0 + m_pad, *c2 = c1 + m_pad, *c3 = c2 + m_pad, *e0 = c3 + m_pad, *e1 = e0 + m_pad, *e2 = e1 + m_pad;
+    const double *soa[5] = {c0, c1, c2, c3, c3};
+    rs::SymH sh;
+    rs::sym_prepare(Hd, &sh);
+    // the centre pair is the correspondence itself (u[0..1], u[3..4] = f[0..1], f[7..8]); then the two frame points
+    for (int k = 0; k < m_pad; k++) { const double *f = laf + (size_t)cur[k < m ? k : m - 1] * 14; c0[k] = f[0]; c1[k] = f[1]; c2[k] = f[7]; c3[k] = f[8]; }
+    ops->hsym_all(soa, m_pad, sh.H1, sh.Hinv, 1, e0);
+    for (int k = 0; k < m_pad; k++) {
+      const double *f = laf + (size_t)cur[k < m ? k : m - 1] * 14;
+      c0[k] = f[0] + ks * f[3] * f[6]; c1[k] = f[1] + ks * f[5] * f[6]; c2[k] = f[7] + ks * f[10] * f[13]; c3[k] = f[8] + ks * f[12] * f[13];
+    }
+    ops->hsym_all(soa, m_pad, sh.H1, sh.Hinv, 1, e1);
+    for (int k = 0; k < m_pad; k++) {
+      const double *f = laf + (size_t)cur[k < m ? k : m - 1] * 14;
+      c0[k] = f[0] + ks * f[2] * f[6]; c1[k] = f[1] + ks * f[4] * f[6]; c2[k] = f[7] + ks * f[9] * f[13]; c3[k] = f[8] + ks * f[11] * f[13];
+    }
+    ops->hsym_all(soa, m_pad, sh.H1, sh.Hinv, 1, e2);
+    int kept = 0;
+    for (int k = 0; k < m; k++) {
+      const double sumErr = std::sqrt(e0[k] + e1[k] + e2[k]);
+      if (!(sumErr > bound)) cur[kept++] = cur[k];
+    }
+    cur.resize(kept);
+    return;
+  }
+  std::vector<int> good;
+  for (int i : cur) {
+    const double *f = laf + (size_t)i * 14;
+    double u[18], err[3];
+    u[0] = f[0]; u[1] = f[1]; u[2] = 1.0;
+    u[3] = f[7]; u[4] = f[8]; u[5] = 1.0;
+    u[6] = u[0] + ks * f[3] * f[6]; u[7] = u[1] + ks * f[5] * f[6]; u[8] = 1.0;
+    u[9] = u[3] + ks * f[10] * f[13]; u[10] = u[4] + ks * f[12] * f[13]; u[11] = 1.0;
+    u[12] = u[0] + ks * f[2] * f[6]; u[13] = u[1] + ks * f[4] * f[6]; u[14] = 1.0;
+    u[15] = u[3] + ks * f[9] * f[13]; u[16] = u[4] + ks * f[11] * f[13]; u[17] = 1.0;
+    HDsSymMax(nullptr, u, Hd, err, 3);
+    const double sumErr = std::sqrt(err[0] + err[1] + err[2]);
+    if (!(sumErr > bound)) good.push_back(i);
+  }
+  cur.swap(good);
+}
+
+// cv::invert of a 3 x 3 matrix as the homography branch takes it, for the other verifiers
+bool invert3x3(const double *S, double *t) { return invert3(S, t); }
+}  // namespace mods
+
+extern "C" {
+
 // What LORANSACFiltering does with the model of the homography branch (matching.cpp:745-805): H -> row-major img1->img2 by inv(H^T),
 // NaiveHCheck (10 px, :1014-1043) over the RANSAC inliers, H_LAF_check (:250-308: HDsSymMax on the three frame points).  mask[i] = 1
 // for the correspondences that survive; returns their number.  ops = the host SIMD table (ransac_simd.hpp): both checks are the
@@ -1006,15 +1073,14 @@ static int h_post_checks(const double *u6, const double *laf, int n, const unsig
   for (int i = 0; i < n; i++) if (inl2[i]) cur.push_back(i);
   const double affineFerror = 3.0 * par->HLAFCoef * par->err_threshold;
   const double err_sq = 10.0 * 10.0;
-  const double ks = 3.0;   // matching.cpp:171
   double Hi[9];
   invert3(Hinv, Hi);
   if (ops) {
     const int m = (int)cur.size();
     if (m == 0) return 0;
     const int m_pad = (m + mods::rs::SIMD_PAD - 1) / mods::rs::SIMD_PAD * mods::rs::SIMD_PAD;
-    std::vector<double> buf((size_t)7 * m_pad);
-    double *c0 = buf.data(), *c1 = c0 + m_pad, *c2 = c1 + m_pad, *c3 = c2 + m_pad, *e0 = c3 + m_pad, *e1 = e0 + m_pad, *e2 = e1 + m_pad;
+    std::vector<double> buf((size_t)6 * m_pad);
+    double *c0 = buf.data(), *c1 = c0 + m_pad, *c2 = c1 + m_pad, *c3 = c2 + m_pad, *e0 = c3 + m_pad, *e1 = e0 + m_pad;
     const double *soa[5] = {c0, c1, c2, c3, c3};
     for (int k = 0; k < m_pad; k++) {
       const double *p = u6 + (size_t)cur[k < m ? k : m - 1] * 6;
@@ -1024,29 +1090,7 @@ static int h_post_checks(const double *u6, const double *laf, int n, const unsig
     int ok = 0;
     for (int k = 0; k < m; k++) if ((e0[k] <= err_sq) && (e1[k] <= err_sq)) ok++;
     if (ok < MIN_POINTS) return 0;
-    if (affineFerror > 0 && laf) {
-      mods::rs::SymH sh;
-      mods::rs::sym_prepare(Hloran, &sh);
-      // the centre pair is the correspondence itself (u[0..1], u[3..4] = f[0..1], f[7..8]); then the two frame points
-      for (int k = 0; k < m_pad; k++) { const double *f = laf + (size_t)cur[k < m ? k : m - 1] * 14; c0[k] = f[0]; c1[k] = f[1]; c2[k] = f[7]; c3[k] = f[8]; }
-      ops->hsym_all(soa, m_pad, sh.H1, sh.Hinv, 1, e0);
-      for (int k = 0; k < m_pad; k++) {
-        const double *f = laf + (size_t)cur[k < m ? k : m - 1] * 14;
-        c0[k] = f[0] + ks * f[3] * f[6]; c1[k] = f[1] + ks * f[5] * f[6]; c2[k] = f[7] + ks * f[10] * f[13]; c3[k] = f[8] + ks * f[12] * f[13];
-      }
-      ops->hsym_all(soa, m_pad, sh.H1, sh.Hinv, 1, e1);
-      for (int k = 0; k < m_pad; k++) {
-        const double *f = laf + (size_t)cur[k < m ? k : m - 1] * 14;
-        c0[k] = f[0] + ks * f[2] * f[6]; c1[k] = f[1] + ks * f[4] * f[6]; c2[k] = f[7] + ks * f[9] * f[13]; c3[k] = f[8] + ks * f[11] * f[13];
-      }
-      ops->hsym_all(soa, m_pad, sh.H1, sh.Hinv, 1, e2);
-      int kept = 0;
-      for (int k = 0; k < m; k++) {
-        const double sumErr = std::sqrt(e0[k] + e1[k] + e2[k]);
-        if (!(sumErr > affineFerror)) cur[kept++] = cur[k];
-      }
-      cur.resize(kept);
-    }
+    mods::h_laf_check(laf, Ht, affineFerror, ops, cur);
   } else {
     // NaiveHCheck over the RANSAC inliers
     {
@@ -1064,24 +1108,7 @@ static int h_post_checks(const double *u6, const double *laf, int n, const unsig
       }
       if (ok < MIN_POINTS) cur.clear();
     }
-    // H_LAF_check with HDsSymMax on the three frame points
-    if (affineFerror > 0 && laf) {
-      std::vector<int> good;
-      for (int i : cur) {
-        const double *f = laf + (size_t)i * 14;
-        double u[18], err[3];
-        u[0] = f[0]; u[1] = f[1]; u[2] = 1.0;
-        u[3] = f[7]; u[4] = f[8]; u[5] = 1.0;
-        u[6] = u[0] + ks * f[3] * f[6]; u[7] = u[1] + ks * f[5] * f[6]; u[8] = 1.0;
-        u[9] = u[3] + ks * f[10] * f[13]; u[10] = u[4] + ks * f[12] * f[13]; u[11] = 1.0;
-        u[12] = u[0] + ks * f[2] * f[6]; u[13] = u[1] + ks * f[4] * f[6]; u[14] = 1.0;
-        u[15] = u[3] + ks * f[9] * f[13]; u[16] = u[4] + ks * f[11] * f[13]; u[17] = 1.0;
-        HDsSymMax(nullptr, u, Hloran, err, 3);
-        const double sumErr = std::sqrt(err[0] + err[1] + err[2]);
-        if (!(sumErr > affineFerror)) good.push_back(i);
-      }
-      cur.swap(good);
-    }
+    mods::h_laf_check(laf, Ht, affineFerror, nullptr, cur);
   }
   if ((int)cur.size() < MIN_POINTS) cur.clear();
   for (int i : cur) mask[i] = 1;

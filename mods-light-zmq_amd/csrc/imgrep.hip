@@ -239,8 +239,8 @@ static void gather_tentatives(mods_ctx *c, const std::vector<TentList> lists[2])
     for (const TentList &l : lists[desc]) c->h_list.append(l);
 }
 
-// DuplicateFiltering + LORANSACFiltering (ORSAFiltering for useF = 2) of the gathered list (mods.cpp:278-383); w, h: the size
-// ORSA normalises by, ((w1 + w2) / 2, (h1 + h2) / 2) in the step loop (mods.cpp:347-350), 0 where the caller has none
+// DuplicateFiltering + LORANSACFiltering (ORSAFiltering for useF = 2, ORSA-H for 3) of the gathered list (mods.cpp:278-383); w, h:
+// the size ORSA normalises by, ((w1 + w2) / 2, (h1 + h2) / 2) in the step loop (mods.cpp:347-350), 0 where the caller has none
 static int verify_gathered(mods_ctx *c, const mods_pair_params *par, mods_ladder_result *res, int w, int h) {
   res->n_tentatives = (int)c->h_list.size();
   mods_pair_params p2;
@@ -284,7 +284,7 @@ static int match_verify_banks(mods_ctx *c, mods_imgrep *rep1, mods_imgrep *rep2,
   if (fginn_ratio_half > 0 && (rc = match_into(c, rep1h, rep2h, fginn_ratio_half, par, &lists[1][0]))) return rc;
   gather_tentatives(c, lists);
   res->ms_match += now_ms() - t1;
-  return verify_gathered(c, par, res, 0, 0);   // banks only: no image size (useF = 2 is refused)
+  return verify_gathered(c, par, res, 0, 0);   // banks only: no image size (useF = 2 / 3 are refused)
 }
 
 // One synthesised view of one image for one detector of a step, and where its regions were left

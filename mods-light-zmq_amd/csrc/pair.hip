@@ -466,8 +466,8 @@ int mods_verify_tentatives_wh(int device, const mods_pair_params *par, mods_tent
                               double *ms_ransac) {
   if (gt3) gt3[0] = gt3[1] = gt3[2] = 0;
   if (!par || !n_unique || !n_verified || (n > 0 && (!tent || !u6 || !laf))) { set_error("verify_tentatives: null argument"); return MODS_E_ARG; }
-  if (par->ransac.useF == 2 && !par->ransac.groundTruth && (w <= 0 || h <= 0)) {
-    set_error("verify_tentatives: useF = 2 (ORSA) needs the image size: call mods_verify_tentatives_wh");
+  if ((par->ransac.useF == 2 || par->ransac.useF == 3) && !par->ransac.groundTruth && (w <= 0 || h <= 0)) {
+    set_error("verify_tentatives: useF = %d (ORSA) needs the image size: call mods_verify_tentatives_wh", par->ransac.useF);
     return MODS_E_ARG;
   }
   int rc;
@@ -508,7 +508,9 @@ int mods_verify_tentatives_wh(int device, const mods_pair_params *par, mods_tent
   } else {
     if (par->ransac.useF == 2)
       rc = mods_orsa_f(u6, laf, nu, w, h, &par->ransac, mask.data(), H, &ninl, nullptr, nullptr, nullptr, stats);
-    else if (par->ransac.useF) rc = mods_loransac_f(u6, laf, nu, &par->ransac, mask.data(), H, &ninl, stats);
+    else if (par->ransac.useF == 3)
+      rc = mods_orsa_h(u6, laf, nu, w, h, &par->ransac, mask.data(), H, &ninl, nullptr, nullptr, nullptr, nullptr, stats);
+    else if (mods_model_kind(par->ransac.useF) != 0) rc = mods_loransac_f(u6, laf, nu, &par->ransac, mask.data(), H, &ninl, stats);
     else rc = mods_loransac_h(u6, laf, nu, &par->ransac, mask.data(), H, &ninl, stats);
     if (rc) return rc;
   }
