@@ -319,6 +319,38 @@ int mods_patches_fetch(mods_ctx *ctx, int img, int ps, float *out, int max_regio
  * iterations run since mods_baumberg_stats_enable(ctx, 1); one iteration = smmWindowSize^2 bilinear taps (affine.cpp:26-158). */
 int mods_baumberg_stats_enable(mods_ctx *ctx, int on);
 int mods_baumberg_stats(mods_ctx *ctx, int img, unsigned long long *keypoints, unsigned long long *iterations);
+/* ---- detection masks ----------------------------------------------------------------------------
+ * Restricts the regions of an image to a per-image mask, as cv::Feature2D::detect(image, mask) does (the reference began
+ * mods-with-mask.cpp, which loads <image>_mask.png, and never wired it in).  A mask is an 8-bit image of the ORIGINAL image's size
+ * (w x h, row stride `stride` >= w bytes): 0 = no regions here, anything else = allowed.
+ * The rule: a point (x, y) in original-image coordinates - the doubles a mods_affkey / mods_region carries - is on the mask iff
+ * 0 <= ix < w, 0 <= iy < h and mask[iy * stride + ix] != 0 with ix = (int)floor(x + 0.5), iy = (int)floor(y + 0.5) (pixel centres
+ * sit at integer coordinates).  Only the centre counts; the measurement region may overlap masked pixels.
+ * mods_detection_mask_test states the rule on the host (1 on the mask, 0 off it or on bad arguments; no device needed).
+ *  - HessianAffine, DoG, HarrisAffine, plain images and synthesised views (there the centre is the reprojected one, in the original
+ *    frame): an extremum with an off-mask centre is removed after the octave-map rule and before affine adaptation.  It still
+ *    claims its octave-map cell (which of two rival extrema survives is what it was without a mask), never reaches Baumberg, a shape
+ *    network, orientation or description, and takes no part in the export selection: RelativeTh's maximum, FixedRegNumber,
+ *    RelativeRegNumber and NotLessThanRegions see on-mask points only.  In FixedTh mode the key and region lists are therefore the
+ *    unmasked call's with the off-mask entries deleted, order kept, every field equal to the bit except the list positions in
+ *    id / parent.
+ *  - MSER: the keys with an off-mask centre are deleted from the key list MSER exports, before orientation; MSER's own count
+ *    modes (prepareKeysForExport) have been applied by then, so they count off-mask regions too.
+ *  - Regions that come from the caller are not filtered: mods_orient_describe*, the command line's pre-extracted mode,
+ *    mods_imgrep_append_*.
+ *  - No mask set: the calls are what they were, launch for launch (the gate kernel is not launched).
+ * `image` is the index in the call's image list: the batch entry of mods_detect_*_dev / mods_detect_describe_dev*, 0 / 1 for the
+ * first / second image of the view2, pair and ladder entry points (whichever context of the ladder runs a view).
+ * mods_ctx_detection_mask copies a host mask into a buffer of the context; _dev borrows the caller's device buffer, which must stay
+ * valid while it is set (its bytes are read when a call runs: new contents need no new call here).  A null pointer clears that
+ * image's mask, _masks_clear all of them.  A mask whose w x h differs from the image of a call makes that call MODS_E_ARG.
+ * _counts: entries of image `image` that reached the gate in the context's last call and entries it kept (-1, -1 when the image
+ * had no mask in that call); after a ladder call: the sums over the views of the call, whichever context ran them. */
+int mods_ctx_detection_mask(mods_ctx *ctx, int image, const unsigned char *mask_host, int w, int h, int stride);
+int mods_ctx_detection_mask_dev(mods_ctx *ctx, int image, const unsigned char *mask_dev, int w, int h, int stride);
+int mods_ctx_detection_masks_clear(mods_ctx *ctx);
+int mods_ctx_detection_mask_counts(mods_ctx *ctx, int image, int *n_accepted, int *n_kept);
+int mods_detection_mask_test(const unsigned char *mask, int w, int h, int stride, double x, double y);
 int mods_unoriented_count(mods_ctx *ctx, int img);   /* |"None" region list| of slot img after the last describe call */
 int mods_regions_fetch(mods_ctx *ctx, int img, mods_region *out, int max_out, int *n_out);
 
@@ -849,6 +881,10 @@ int mods_pipeline_submit(mods_pipeline *p, const float *img_dev, long tag);
  * mods_host_alloc); the memory must stay valid until the pair's result has been fetched */
 int mods_pipeline_submit_host(mods_pipeline *p, const float *img_host, long tag);
 int mods_pipeline_submit_host_u8(mods_pipeline *p, const unsigned char *img_host, long tag);
+/* the 8-bit pair with its detection masks (see mods_ctx_detection_mask): mask_host = two stacked masks of the images' geometry
+ * ([2][h][w] bytes, valid as long as the images), or null for an unmasked pair - a batch may mix both.  The masks are staged and
+ * uploaded with the images; the pair's result is what mods_match_pair_dev gives on a context with the same two masks set. */
+int mods_pipeline_submit_host_u8_masked(mods_pipeline *p, const unsigned char *img_host, const unsigned char *mask_host, long tag);
 int mods_pipeline_next(mods_pipeline *p, mods_pair_result *res, long *tag);
 /* the same, and the verified matches of the pair (rows x1 y1 x2 y2, the order of mods_match_pair_dev's matches_out): the first
  * min(res->n_inliers, max_matches) rows are written */

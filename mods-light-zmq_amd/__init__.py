@@ -152,6 +152,23 @@ def _overlap(fn, dtype, lists, params, cap):
     return out[:n.value].copy(), counts
 
 
+def _mask_rows(mask):
+    """a detection mask as the library takes it: (array that owns the bytes, row stride in bytes); a 2-D uint8 array whose rows are
+    contiguous keeps its row stride, anything else is copied dense"""
+    m = np.asarray(mask)
+    if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
+        raise ValueError("a detection mask is a non-empty 2-D uint8 array")
+    if m.strides[1] != 1 or m.strides[0] < m.shape[1]:
+        m = np.ascontiguousarray(m)
+    return m, m.strides[0]
+
+
+def detection_mask_test(mask, x, y):
+    """the on-mask rule (mods_detection_mask_test) for one point: True when (x, y) is on the mask; no device needed"""
+    m, stride = _mask_rows(mask)
+    return bool(lib().mods_detection_mask_test(_vp(m), m.shape[1], m.shape[0], stride, C.c_double(x), C.c_double(y)))
+
+
 def u8_strips_layout(w, h):
     """(width limit, strips per image, bytes per strip, bytes per image) of the 8-bit strip copy of a w x h image (csrc/u8_strips.hpp;
     no device needed)"""
@@ -367,6 +384,29 @@ class Context:
         kp, it = C.c_ulonglong(), C.c_ulonglong()
         _check(lib().mods_baumberg_stats(self.h, img, C.byref(kp), C.byref(it)))
         return kp.value, it.value
+
+    # ---- detection masks (include/mods_hip.h, "detection masks")
+    def set_detection_mask(self, image, mask):
+        """mask: a 2-D uint8 array of the image's size (0 = no regions here), copied into the context; rows may be strided (a
+        column slice of a wider array); None clears the mask of that image of a call"""
+        if mask is None:
+            _check(lib().mods_ctx_detection_mask(self.h, int(image), None, 0, 0, 0))
+            return
+        m, stride = _mask_rows(mask)
+        _check(lib().mods_ctx_detection_mask(self.h, int(image), _vp(m), m.shape[1], m.shape[0], stride))
+
+    def set_detection_mask_dev(self, image, dev_ptr, w, h, stride=None):
+        """the same for a mask in device memory, which the context borrows: it must stay valid while set (0 / None clears)"""
+        _check(lib().mods_ctx_detection_mask_dev(self.h, int(image), C.c_void_p(dev_ptr or 0), w, h, stride or w))
+
+    def clear_detection_masks(self):
+        _check(lib().mods_ctx_detection_masks_clear(self.h))
+
+    def detection_mask_counts(self, image):
+        """(entries of that image that reached the gate in the last call, entries it kept); (-1, -1) when the image had no mask"""
+        a, k = C.c_int(), C.c_int()
+        _check(lib().mods_ctx_detection_mask_counts(self.h, int(image), C.byref(a), C.byref(k)))
+        return a.value, k.value
 
     def graphs(self, on=True):
         """replay the launches of detect + describe as a hipGraph from the second call with the same arguments on"""
@@ -1674,8 +1714,15 @@ class Pipeline:
     def submit(self, dev_ptr, tag=0):
         _check(lib().mods_pipeline_submit(self.h, C.c_void_p(dev_ptr), C.c_long(tag)))
 
-    def submit_host(self, host_ptr, tag=0, u8=False):
-        """The pair in host memory ([2][h][w] fp32, or 8-bit grey with u8=True): uploaded on the worker's stream."""
+    def submit_host(self, host_ptr, tag=0, u8=False, mask=None):
+        """The pair in host memory ([2][h][w] fp32, or 8-bit grey with u8=True): uploaded on the worker's stream.
+        mask (8-bit pairs only): the address of the pair's two stacked detection masks ([2][h][w] bytes in host memory, valid as
+        long as the images), see Context.set_detection_mask."""
+        if mask is not None:
+            if not u8:
+                raise ValueError("detection masks go with 8-bit pairs (u8=True)")
+            _check(lib().mods_pipeline_submit_host_u8_masked(self.h, C.c_void_p(host_ptr), C.c_void_p(mask), C.c_long(tag)))
+            return
         fn = lib().mods_pipeline_submit_host_u8 if u8 else lib().mods_pipeline_submit_host
         _check(fn(self.h, C.c_void_p(host_ptr), C.c_long(tag)))
 

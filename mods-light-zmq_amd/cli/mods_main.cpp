@@ -58,6 +58,11 @@ struct Config {
   int max_steps = 4, min_matches = 15;
   int load_color = 1;
   int do_clahe = 0;                // [Matching] doCLAHE (io_mods.cpp:526): CLAHE on both 8-bit grey images before detection
+  // [DetectionMask] (no counterpart in the reference's command line; its author began mods-with-mask.cpp): mask1 / mask2 = an 8-bit
+  // image of image 1 / 2's size, 0 = no regions there; useMaskFiles = 1: <image path without extension>_mask.png for an image
+  // without a key of its own, where that file exists (mods_ctx_detection_mask)
+  std::string mask_fn[2];
+  int use_mask_files = 0;
   int mutual_check = 0;            // [Matching] mutualCheck (no counterpart in the reference): mods_ctx_match_mutual
   // [SIFTDescriptor] domainSizePooling (the gate; no counterpart in the reference) with the reference's numScales / startCoef /
   // endCoef (io_mods.cpp:431-433, parsed there and never used): mods_ctx_domain_pooling
@@ -251,6 +256,9 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->draw_epipolar = (int)ini.GetInteger("ImageOutput", "drawEpipolarLines", 0);
   cfg->draw_regions = ini.GetBoolean("ImageOutput", "drawDetectedRegions", false) ? 1 : 0;
   cfg->do_clahe = (int)ini.GetInteger("Matching", "doCLAHE", 0);
+  cfg->mask_fn[0] = ini.GetString("DetectionMask", "mask1", "");
+  cfg->mask_fn[1] = ini.GetString("DetectionMask", "mask2", "");
+  cfg->use_mask_files = (int)ini.GetInteger("DetectionMask", "useMaskFiles", 0);
   cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
   if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
   // [LocalAffineFiltering]: the filter of the list that goes to the verification, its parameters under the names of mods_local_affine_params
@@ -736,6 +744,35 @@ int main(int argc, char **argv) {
   if (!load_grey(img2_fn, cfg.load_color, &img2)) { std::cerr << "Cannot read image " << img2_fn << std::endl; return 1; }
   if (cfg.verbose) std::cerr << "Image1: " << img1.w << "x" << img1.h << ", Image2: " << img2.w << "x" << img2.h << std::endl;
 
+  // [DetectionMask]: read as grey with the image reader, checked against the image before anything else runs
+  std::vector<unsigned char> det_mask[2];
+  bool masks_ignored = false;
+  {
+    const std::string *img_fn[2] = {&img1_fn, &img2_fn};
+    const GreyImage *im[2] = {&img1, &img2};
+    for (int i = 0; i < 2; i++) {
+      std::string fn = cfg.mask_fn[i];
+      while (!fn.empty() && isspace((unsigned char)fn.back())) fn.pop_back();
+      if (fn.empty() && cfg.use_mask_files) {
+        const size_t dot = img_fn[i]->find_last_of('.'), slash = img_fn[i]->find_last_of('/');
+        const std::string stem = (dot != std::string::npos && (slash == std::string::npos || dot > slash)) ? img_fn[i]->substr(0, dot) : *img_fn[i];
+        if (std::ifstream(stem + "_mask.png").good()) fn = stem + "_mask.png";
+      }
+      if (fn.empty()) continue;
+      if (pre_extracted || getenv("MODS_DEVICES")) { masks_ignored = true; continue; }
+      GreyImage m;
+      if (!load_grey(fn, 0, &m)) { std::cerr << "Cannot read detection mask " << fn << " ([DetectionMask] mask" << i + 1 << ")" << std::endl; return 1; }
+      if (m.w != im[i]->w || m.h != im[i]->h) {
+        std::cerr << "Detection mask " << fn << " is " << m.w << "x" << m.h << ", image " << i + 1 << " is " << im[i]->w << "x" << im[i]->h << std::endl;
+        return 1;
+      }
+      det_mask[i].resize(m.px.size());
+      for (size_t q = 0; q < m.px.size(); q++) det_mask[i][q] = m.px[q] != 0.0f ? 255 : 0;
+      if (cfg.verbose) std::cerr << "Detection mask of image " << i + 1 << ": " << fn << std::endl;
+    }
+    if (masks_ignored) std::cerr << "Note: [DetectionMask] is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
+  }
+
   if (mods_device_count() <= 0) { std::cerr << "mods: no MI355X / HIP device available (" << mods_last_error() << "); this build has no CPU path" << std::endl; return 1; }
   const int device = getenv("MODS_DEVICE") ? atoi(getenv("MODS_DEVICE")) : 0;
   const double diag = std::ceil(std::max(std::hypot((double)img1.w, (double)img1.h), std::hypot((double)img2.w, (double)img2.h))) + 2;
@@ -750,6 +787,9 @@ int main(int argc, char **argv) {
   // One run of one pair: further contexts for the views of a step (MODS_LADDER_WORKERS) take longer to set up than they save
   setenv("MODS_LADDER_WORKERS", "1", 0);
   if (mods_ctx_create(device, (int)diag, (int)diag, 2, &ctx)) return fail("context");
+  for (int i = 0; i < 2; i++)
+    if (!det_mask[i].empty() && mods_ctx_detection_mask(ctx, i, det_mask[i].data(), i ? img2.w : img1.w, i ? img2.h : img1.h, i ? img2.w : img1.w))
+      return fail("[DetectionMask]");
   if (cfg.mutual_check && mods_ctx_match_mutual(ctx, cfg.mutual_check)) return fail("mutualCheck");
   if (cfg.local_affine && mods_ctx_local_affine(ctx, &cfg.la_par)) return fail("[LocalAffineFiltering]");
   if (cfg.dsp && cfg.use_zmq) { std::cerr << "[SIFTDescriptor] domainSizePooling = 1 pools SIFT histograms: it cannot be combined with the [zmqDescriptor] descriptor" << std::endl; return 1; }
@@ -915,6 +955,21 @@ int main(int argc, char **argv) {
   if (cfg.verbose) {
     std::cerr << res.n_views << " views synthesised, " << res.n_tentatives << " tentatives found." << std::endl;
     std::cerr << res.n_unique << " unique tentatives left" << std::endl;
+    for (int i = 0; i < 2; i++)
+      if (!det_mask[i].empty()) {
+        int acc = 0, kept = 0;
+        if (mods_ctx_detection_mask_counts(ctx, i, &acc, &kept)) return fail("[DetectionMask]");
+        std::cerr << "Detection mask of image " << i + 1 << ": " << acc << " points accepted, " << kept << " kept" << std::endl;
+      }
+    if (!det_mask[0].empty() || !det_mask[1].empty()) {      // the rule itself over what is about to be written
+      int on = 0;
+      for (int i = 0; i < n_written; i++) {
+        const double *m = &matches[4 * (size_t)i];
+        on += (det_mask[0].empty() || mods_detection_mask_test(det_mask[0].data(), img1.w, img1.h, img1.w, m[0], m[1])) &&
+              (det_mask[1].empty() || mods_detection_mask_test(det_mask[1].data(), img2.w, img2.h, img2.w, m[2], m[3]));
+      }
+      std::cerr << on << " of " << n_written << " matches have both centres on the detection masks" << std::endl;
+    }
     if (cfg.local_affine && !multi) {
       int la_in = 0, la_kept = 0;
       if (mods_local_affine_counts(ctx, &la_in, &la_kept)) return fail("[LocalAffineFiltering]");

@@ -687,6 +687,71 @@ int mods_baumberg_stats(mods_ctx *c, int img, unsigned long long *keypoints, uns
   return MODS_OK;
 }
 
+// ---- detection masks (detection_mask.hpp; the gate: detect.hip) ---------------------------------------------------------------
+// Every change goes through dev_state_changed: a recorded detect + describe call holds the launches of the mask set it was recorded
+// with (with or without the gate) and is not replayed across a change.  The mask's BYTES are read when the gate runs, so new
+// contents behind an unchanged pointer need nothing.
+static int detection_mask_set(mods_ctx *c, int image, const unsigned char *dev, int w, int h, int stride) {
+  if ((int)c->det_masks.size() < c->batch) c->det_masks.resize((size_t)c->batch, mods::DetMaskDev{nullptr, 0, 0, 0, 0});
+  if (dev) {     // the gate's table and counters, here and not in the first masked call: that call then changes no pool
+    MODS_HIP_CHECK(hipSetDevice(c->device));
+    MODS_HIP_CHECK(mods::reserve_pool(c, c->gate_tab_dev, (size_t)c->batch, (size_t)c->batch));
+    MODS_HIP_CHECK(mods::reserve_pool(c, c->gate_counts_dev, 2 * (size_t)c->batch, 2 * (size_t)c->batch));
+  }
+  c->det_masks[image] = dev ? mods::DetMaskDev{dev, w, h, stride, 0} : mods::DetMaskDev{nullptr, 0, 0, 0, 0};
+  mods::dev_state_changed(c);
+  return MODS_OK;
+}
+static int detection_mask_args(mods_ctx *c, int image, const void *mask, int w, int h, int stride, const char *who) {
+  if (!c) { set_error("%s: null context", who); return MODS_E_ARG; }
+  if (image < 0 || image >= c->batch) { set_error("%s: image %d, context batch %d", who, image, c->batch); return MODS_E_ARG; }
+  if (mask && (w <= 0 || h <= 0 || stride < w)) { set_error("%s: a mask of %d x %d with row stride %d", who, w, h, stride); return MODS_E_ARG; }
+  return MODS_OK;
+}
+int mods_ctx_detection_mask_dev(mods_ctx *c, int image, const unsigned char *mask_dev, int w, int h, int stride) {
+  const int rc = detection_mask_args(c, image, mask_dev, w, h, stride, "detection_mask_dev");
+  if (rc) return rc;
+  return detection_mask_set(c, image, mask_dev, w, h, stride);
+}
+int mods_ctx_detection_mask(mods_ctx *c, int image, const unsigned char *mask_host, int w, int h, int stride) {
+  const int rc = detection_mask_args(c, image, mask_host, w, h, stride, "detection_mask");
+  if (rc) return rc;
+  if (!mask_host) return detection_mask_set(c, image, nullptr, 0, 0, 0);
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  if ((int)c->det_mask_own.size() < c->batch) c->det_mask_own.resize((size_t)c->batch);
+  mods::Buf<unsigned char> &own = c->det_mask_own[image];
+  const size_t bytes = (size_t)w * h;
+  MODS_HIP_CHECK(mods::reserve_pool(c, own, bytes, bytes));
+  // the context's copy is dense; ordered on the stream behind whatever still reads the previous contents
+  MODS_HIP_CHECK(hipMemcpy2DAsync(own, (size_t)w, mask_host, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
+  MODS_HIP_CHECK(mods::stream_wait(c->stream));
+  return detection_mask_set(c, image, own, w, h, w);
+}
+int mods_ctx_detection_masks_clear(mods_ctx *c) {
+  if (!c) { set_error("detection_masks_clear: null context"); return MODS_E_ARG; }
+  for (auto &m : c->det_masks) m = mods::DetMaskDev{nullptr, 0, 0, 0, 0};
+  mods::dev_state_changed(c);
+  return MODS_OK;
+}
+int mods_ctx_detection_mask_counts(mods_ctx *c, int image, int *n_accepted, int *n_kept) {
+  if (!c || image < 0 || image >= c->batch) { set_error("detection_mask_counts: bad argument"); return MODS_E_ARG; }
+  int v[2] = {-1, -1};
+  if (c->gate_ladder_last) {
+    if (image < 2 && image < (int)c->det_masks.size() && c->det_masks[image].mask) { v[0] = (int)c->gate_ladder[2 * image]; v[1] = (int)c->gate_ladder[2 * image + 1]; }
+  } else if (image < (int)c->gate_had_mask.size() && c->gate_had_mask[image] && c->gate_counts_dev) {
+    MODS_HIP_CHECK(hipSetDevice(c->device));
+    MODS_HIP_CHECK(mods::stream_wait(c->stream));
+    MODS_HIP_CHECK(mods::copy_wait(c->stream, v, c->gate_counts_dev + 2 * (size_t)image, sizeof(v), hipMemcpyDeviceToHost));
+  }
+  if (n_accepted) *n_accepted = v[0];
+  if (n_kept) *n_kept = v[1];
+  return MODS_OK;
+}
+int mods_detection_mask_test(const unsigned char *mask, int w, int h, int stride, double x, double y) {
+  if (!mask || w <= 0 || h <= 0 || stride < w) return 0;
+  return mods::detection_mask_on(mask, w, h, stride, x, y) ? 1 : 0;
+}
+
 int mods_unoriented_count(mods_ctx *c, int img) {
   if (!c || img < 0 || img >= (int)c->last_inside_counts.size()) return 0;
   return c->last_inside_counts[img];

@@ -12,6 +12,7 @@
 #include "../../include/mods_hip.h"
 #include "buffer.hpp"
 #include "pixel_sources.hpp"
+#include "detection_mask.hpp"
 
 namespace mods {
 
@@ -343,6 +344,26 @@ struct mods_ctx {
   mods::Buf<char> la_buf, la_io;
   mods::PinnedBuf<int> la_count;
   int la_n_in = 0, la_n_kept = 0;
+  // detection masks (mods_ctx_detection_mask*; detection_mask.hpp, detect.hip): det_masks = what the caller set per image of a call
+  // (det_mask_own: the context's copies of host masks), gate_tab_host / gate_tab_dev = the table the gate kernel reads, per image
+  // slot, as the last call bound it (a view worker of the ladder binds its owner's masks: gate_owner, gate_image), gate_counts_dev =
+  // [batch][2] entries that reached the gate and entries kept, gate_had_mask = which slots of the last call were gated
+  std::vector<mods::DetMaskDev> det_masks;
+  std::vector<mods::Buf<unsigned char>> det_mask_own;
+  mods::Buf<unsigned char> det_mask_stage;   // [batch][h][w]: the masks of a batch of host pairs (pair pipeline), uploaded with their images
+  bool det_mask_staged = false;              // det_masks hold what the last batch of pairs staged, not what the caller set
+  std::vector<mods::DetMaskDev> gate_tab_host;
+  mods::Buf<mods::DetMaskDev> gate_tab_dev;
+  mods::Buf<int> gate_counts_dev;
+  std::vector<char> gate_had_mask;
+  bool gate_active = false;          // the call in flight has a mask on at least one of its images
+  mods::DetGateFrame gate_frame;     // ... and this is the frame they live in
+  const mods_ctx *gate_owner = nullptr;
+  int gate_image[2] = {0, 1};
+  // a ladder call's counts: summed over its views by whichever context ran them, per image of the call {reached the gate, kept};
+  // gate_ladder_last: the context's last call was a ladder (mods_ctx_detection_mask_counts then reports these)
+  std::atomic<long long> gate_ladder[4] = {{0}, {0}, {0}, {0}};
+  bool gate_ladder_last = false;
   mods::MserState *mser = nullptr;   // MserState (mser.hip): buffers of the MSER detector, allocated on first use
   // the step loop spreads the views of a step over a few more contexts of the same GPU (imgrep.hip: run_view_jobs)
   std::vector<mods_ctx *> helpers;
@@ -420,9 +441,13 @@ int clahe_launch(mods_ctx *ctx, const unsigned char *src, int n_img, int w, int 
 int detect_run(mods_ctx *ctx);       // NMS -> localise -> dedup -> Baumberg -> sort, for the configured batch
 size_t nms_octave_mask_words(int w, int h, int border, int n_scales);   // ballot words of one image's NMS over one octave
 
+int detection_mask_bind(mods_ctx *ctx, int n_img, int w, int h, const DetGateFrame *frame);   // the call's masks -> the gate's table; sets gate_active
+int launch_detection_mask_keys(mods_ctx *ctx, int n_img);   // the gate over the exported key lists (MSER)
+
 // mser.hip
+// frame: the original image and the way to it when the images are synthesised views (detection masks live there); null: the images themselves
 int detect_any(mods_ctx *ctx, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *par, double tilt,
-               double zoom);         // the detector the parameter set names: scale space (pyramid + detect_run) or MSER
+               double zoom, const DetGateFrame *frame = nullptr);   // the detector the parameter set names: scale space (pyramid + detect_run) or MSER
 void mser_release(mods_ctx *ctx);
 
 // match.hip
@@ -476,6 +501,9 @@ int u8_sources_launch(mods_ctx *c, const unsigned char *src, int n_img, int w, i
 int u8_stage_ensure(mods_ctx *c);          // pair.hip: c->u8_stage_dev and c->u8_strip_dev allocated (a full batch of the context's largest images)
 int describe_run_view(mods_ctx *ctx, const PixelSources &img, int n_img, int w, int h, const mods_describe_params *par, const double *H,
                       int orig_w, int orig_h, mods_region *det_copy_dev);
+// the frame of a view's regions as describe_run_view takes it from H (w x h: the view, orig_w x orig_h: the original): false for the
+// identity view of the same canvas, where nothing is reprojected (frame->Hinv is the identity then)
+bool view_region_frame(const double *H, int w, int h, int orig_w, int orig_h, DetGateFrame *frame);
 int describe_configure(mods_ctx *ctx, const mods_describe_params *par);
 int launch_dominant_angle_test(mods_ctx *ctx, const float *patch_dev, int ps, double th, float *out_dev);
 int launch_sift_patch_test(mods_ctx *ctx, const float *patch_dev, int ps, int root, double max_bin, uint8_t *out_dev);
@@ -496,7 +524,7 @@ int net_run_to_host(mods_ctx *ctx, mods_net *net, const float *patches_dev, int 
 int pair_gpu_stage(mods_ctx *c, const float *img_dev, int w, int h, int stride, const mods_pair_params *par, mods_pair_result *res,
                    TentList *list);
 int pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds, int n_pairs, int w, int h, const mods_pair_params *par,
-                    mods_pair_result *const *res, TentList *const *lists);
+                    mods_pair_result *const *res, TentList *const *lists, const unsigned char *const *masks = nullptr);
 int pair_verify_stage(int device, const mods_pair_params *par, mods_pair_result *res, TentList *list, double *matches_out,
                       int max_matches, int w, int h);
 

@@ -433,8 +433,7 @@ __global__ __launch_bounds__(256) void reproject_regions_kernel(DescConst k, mod
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     mods_region *r = reg + i;
     const double x = r->x, y = r->y, a11 = r->a11, a12 = r->a12, a21 = r->a21, a22 = r->a22;
-    r->x = (k.Hinv[0] * x + k.Hinv[1] * y + k.Hinv[2]);
-    r->y = (k.Hinv[3] * x + k.Hinv[4] * y + k.Hinv[5]);
+    reproject_centre(k.Hinv, x, y, &r->x, &r->y);
     r->a11 = (k.Hinv[0] * a11 + k.Hinv[1] * a21);
     r->a12 = (k.Hinv[0] * a12 + k.Hinv[1] * a22);
     r->a21 = (k.Hinv[3] * a11 + k.Hinv[4] * a21);
@@ -793,6 +792,25 @@ static void invert3_cv(const double *S, double *t) {
   t[6] = (S[3] * S[7] - S[4] * S[6]) * d; t[7] = (S[1] * S[6] - S[0] * S[7]) * d; t[8] = (S[0] * S[4] - S[1] * S[3]) * d;
 }
 
+bool view_region_frame(const double *H, int w, int h, int orig_w, int orig_h, DetGateFrame *fr) {
+  bool view = false;
+  fr->ow = w; fr->oh = h;
+  for (int i = 0; i < 6; i++) fr->Hinv[i] = (i == 0 || i == 4) ? 1.0 : 0.0;
+  if (H) {
+    const bool eye = (std::fabs(H[0] - 1.0) + std::fabs(H[1]) + std::fabs(H[2]) + std::fabs(H[3]) + std::fabs(H[4] - 1.0) + std::fabs(H[5]) +
+                      std::fabs(H[6]) + std::fabs(H[7]) + std::fabs(H[8] - 1.0) < 0.01);
+    // (n_img > 1: the same view of several images of one size - one H for all of them)
+    fr->ow = orig_w; fr->oh = orig_h;
+    if (!eye) {
+      double Hi[9];
+      invert3_cv(H, Hi);
+      view = true;
+      for (int i = 0; i < 6; i++) fr->Hinv[i] = Hi[i];
+    } else if (orig_w != w || orig_h != h) view = true;   // identity map onto a different canvas: the tests still use (ow, oh)
+  }
+  return view;
+}
+
 // The same for a synthesised view: H (original -> view, 9 doubles) and the original image size; the
 // regions come out in the original frame (reproj_kp).  H == nullptr or HIsEye(H) (synth-detection.cpp:
 // 144-149): identity view.  det_copy_dev (optional): receives the described regions in the view frame.
@@ -802,20 +820,10 @@ int describe_run_view(mods_ctx *ctx, const PixelSources &img_all, int n_img, int
   if (rc) return rc;
   if ((rc = describe_configure(ctx, par))) return rc;
   DescConst k;
-  k.view = 0; k.ow = w; k.oh = h;
-  for (int i = 0; i < 6; i++) k.Hinv[i] = (i == 0 || i == 4) ? 1.0 : 0.0;
-  if (H) {
-    const bool eye = (std::fabs(H[0] - 1.0) + std::fabs(H[1]) + std::fabs(H[2]) + std::fabs(H[3]) + std::fabs(H[4] - 1.0) + std::fabs(H[5]) +
-                      std::fabs(H[6]) + std::fabs(H[7]) + std::fabs(H[8] - 1.0) < 0.01);
-    // (n_img > 1: the same view of several images of one size - one H for all of them)
-    k.ow = orig_w; k.oh = orig_h;
-    if (!eye) {
-      double Hi[9];
-      invert3_cv(H, Hi);
-      k.view = 1;
-      for (int i = 0; i < 6; i++) k.Hinv[i] = Hi[i];
-    } else if (orig_w != w || orig_h != h) k.view = 1;   // identity map onto a different canvas: the tests still use (ow, oh)
-  }
+  DetGateFrame fr;
+  k.view = view_region_frame(H, w, h, orig_w, orig_h, &fr) ? 1 : 0;
+  k.ow = fr.ow; k.oh = fr.oh;
+  for (int i = 0; i < 6; i++) k.Hinv[i] = fr.Hinv[i];
   k.w = w; k.h = h; k.max_cand = ctx->max_cand; k.max_reg = ctx->max_cand;
   k.reg_cap = std::min(ctx->max_cand, 1 << 17);
   k.ks = 2 * 3.0 * sqrt(3.0);

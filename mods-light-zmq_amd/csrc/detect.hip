@@ -508,10 +508,132 @@ __global__ __launch_bounds__(256) void omap_reset_kernel(const PyramidDev *__res
   if (n > k.max_cand) n = k.max_cand;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const CandDev &cd = cand[(size_t)b * k.max_cand + i];
-    if (cd.state != 2 && cd.state != 5) continue;
+    if (cd.state != 2 && cd.state != 5 && cd.state != 6) continue;
     const OctaveDev &o = P->oct[cd.octave];
     as_global(o.omap)[(size_t)o.w * o.h * b + (size_t)cd.r * o.w + cd.c] = 0xFFFFFFFFu;
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// The detection-mask gate (mods_ctx_detection_mask*): entries of a per-image list whose centre - in the frame the finished region
+// will carry it in, detection_mask.hpp - is off the image's mask leave the list, in place, order kept.  Launched only for calls
+// with a mask on at least one image; a block whose image has none returns at once.
+// The two lists it serves: the accepted candidates between accept_kernel and Baumberg (an entry = an index into cand; a removed
+// candidate gets state 6: it has claimed its octaveMap cell, which omap_reset_kernel still resets, and is seen by nothing after
+// that), and the exported mods_affkey list of the MSER detector.
+// grid = n_img blocks of 1024: one block walks its image's list in chunks of 1024.  A chunk is read whole before any of it is
+// written (the barrier behind the ballot), and a kept entry moves to a slot at or below its own, so the compaction needs no second
+// list.  Slots come from the wave's ballot and the 16 wave counts in LDS: no atomics, and the same order every run.
+struct GateCandList {
+  CandDev *cand; int *acc_list; int *acc_count;
+  using Item = int;
+  __device__ int *count(int b) const { return acc_count + b; }
+  __device__ Item load(int b, int max_cand, int i) const { return acc_list[(size_t)b * max_cand + i]; }
+  __device__ void centre(int b, int max_cand, const Item &it, double *x, double *y) const {
+    const CandDev &cd = cand[(size_t)b * max_cand + it];
+    *x = cd.x; *y = cd.y;                      // export_kernel's o.x = cd.x, o.y = cd.y
+  }
+  __device__ void reject(int b, int max_cand, const Item &it) const { cand[(size_t)b * max_cand + it].state = 6; }
+  __device__ void store(int b, int max_cand, int slot, const Item &it) const { acc_list[(size_t)b * max_cand + slot] = it; }
+};
+struct GateKeyList {
+  mods_affkey *keys; int *key_count;
+  using Item = mods_affkey;
+  __device__ int *count(int b) const { return key_count + b; }
+  __device__ Item load(int b, int max_cand, int i) const { return keys[(size_t)b * max_cand + i]; }
+  __device__ void centre(int, int, const Item &it, double *x, double *y) const { *x = it.x; *y = it.y; }
+  __device__ void reject(int, int, const Item &) const {}
+  __device__ void store(int b, int max_cand, int slot, const Item &it) const { keys[(size_t)b * max_cand + slot] = it; }
+};
+template <class List>
+__global__ __launch_bounds__(1024) void detection_mask_kernel(DetGateConst g, List L) {
+  __shared__ int s_wave[16];
+  __shared__ int s_base;
+  const int b = blockIdx.x;
+  const DetMaskDev m = g.tab[b];
+  if (!m.mask) return;                           // (block-uniform)
+  int n = *L.count(b);
+  if (n > g.max_cand) n = g.max_cand;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) s_base = 0;
+  __syncthreads();
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + tid;
+    bool keep = false;
+    typename List::Item it{};
+    if (i < n) {
+      it = L.load(b, g.max_cand, i);
+      double x, y, ox, oy;
+      L.centre(b, g.max_cand, it, &x, &y);
+      reproject_centre(g.Hinv, x, y, &ox, &oy);
+      keep = detection_mask_on(m.mask, m.w, m.h, m.stride, ox, oy);
+      if (!keep) L.reject(b, g.max_cand, it);
+    }
+    const unsigned long long kept = __ballot(keep);
+    if (lane == 0) s_wave[wv] = __popcll(kept);
+    __syncthreads();
+    int slot = s_base + __popcll(kept & ((1ull << lane) - 1ull));
+    for (int q = 0; q < wv; q++) slot += s_wave[q];
+    if (keep) L.store(b, g.max_cand, slot, it);
+    __syncthreads();
+    if (tid == 0) { int t = 0; for (int q = 0; q < 16; q++) t += s_wave[q]; s_base += t; }
+    __syncthreads();
+  }
+  if (tid == 0) { g.counts[2 * b] = n; g.counts[2 * b + 1] = s_base; *L.count(b) = s_base; }
+}
+
+// The table the gate reads, for the call that is about to run: slot b holds the mask of the call's image b - the context's own
+// (mods_ctx_detection_mask*), or for a view worker of the ladder its owner's (gate_owner, gate_image).  w x h: the frame the masks
+// live in (frame->ow x oh for views).  Uploaded only when it differs from what the device holds; a change of the context's masks
+// has gone through dev_state_changed, so no upload falls into a recording of the call.
+int detection_mask_bind(mods_ctx *ctx, int n_img, int w, int h, const DetGateFrame *frame) {
+  const mods_ctx *owner = ctx->gate_owner ? ctx->gate_owner : ctx;
+  ctx->gate_active = false;
+  if (!ctx->gate_owner) ctx->gate_ladder_last = false;
+  ctx->gate_had_mask.assign((size_t)ctx->batch, 0);
+  if (owner->det_masks.empty() && ctx->gate_tab_host.empty()) return MODS_OK;      // masks were never set: nothing to look at
+  DetGateFrame fr;
+  if (frame) fr = *frame;
+  else { fr.ow = w; fr.oh = h; for (int i = 0; i < 6; i++) fr.Hinv[i] = (i == 0 || i == 4) ? 1.0 : 0.0; }
+  std::vector<DetMaskDev> want((size_t)ctx->batch, DetMaskDev{nullptr, 0, 0, 0, 0});
+  for (int b = 0; b < n_img && b < ctx->batch; b++) {
+    const int src = ctx->gate_owner ? ctx->gate_image[b < 2 ? b : 1] : b;
+    if (src < 0 || src >= (int)owner->det_masks.size() || !owner->det_masks[src].mask) continue;
+    const DetMaskDev &m = owner->det_masks[src];
+    if (m.w != fr.ow || m.h != fr.oh) {
+      set_error("detection mask of image %d is %d x %d, the image of the call %d x %d", src, m.w, m.h, fr.ow, fr.oh);
+      return MODS_E_ARG;
+    }
+    want[b] = m;
+    ctx->gate_had_mask[b] = 1;
+    ctx->gate_active = true;
+  }
+  if (!ctx->gate_active) return MODS_OK;         // (a stale table is not read: the gate is not launched)
+  ctx->gate_frame = fr;
+  if (!(want == ctx->gate_tab_host)) {
+    MODS_HIP_CHECK(reserve_pool(ctx, ctx->gate_tab_dev, (size_t)ctx->batch, (size_t)ctx->batch));
+    MODS_HIP_CHECK(reserve_pool(ctx, ctx->gate_counts_dev, 2 * (size_t)ctx->batch, 2 * (size_t)ctx->batch));
+    MODS_HIP_CHECK(copy_wait(ctx->stream, ctx->gate_tab_dev, want.data(), sizeof(DetMaskDev) * want.size(), hipMemcpyHostToDevice));
+    ctx->gate_tab_host = want;
+  }
+  // (a list that never reaches the gate - an MSER call without regions - reports 0 / 0)
+  MODS_HIP_CHECK(hipMemsetAsync(ctx->gate_counts_dev, 0, sizeof(int) * 2 * (size_t)ctx->batch, ctx->stream));
+  return MODS_OK;
+}
+
+static DetGateConst gate_const(mods_ctx *ctx) {
+  DetGateConst g;
+  g.tab = ctx->gate_tab_dev; g.counts = ctx->gate_counts_dev; g.max_cand = ctx->max_cand;
+  for (int i = 0; i < 6; i++) g.Hinv[i] = ctx->gate_frame.Hinv[i];
+  return g;
+}
+
+int launch_detection_mask_keys(mods_ctx *ctx, int n_img) {
+  if (!ctx->gate_active) return MODS_OK;
+  hipLaunchKernelGGL(detection_mask_kernel<GateKeyList>, dim3(n_img), dim3(1024), 0, ctx->stream, gate_const(ctx),
+                     GateKeyList{ctx->keys_dev, ctx->cand_count + 2 * ctx->batch});
+  MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1241,6 +1363,9 @@ static int detect_run_stages(mods_ctx *ctx) {
     hipLaunchKernelGGL(localize_kernel, dim3(256, n_img), dim3(256), 0, ctx->stream, ctx->pyr_dev, k, ctx->cand, ctx->cand_count);
     hipLaunchKernelGGL(accept_kernel, dim3(256, n_img), dim3(256), 0, ctx->stream, ctx->pyr_dev, k, ctx->cand, ctx->cand_count,
                        ctx->sort_idx + (size_t)ctx->batch * ctx->max_cand, acc_count);
+    if (ctx->gate_active)      // off-mask candidates leave the accepted list here: after the octaveMap rule, before affine adaptation
+      hipLaunchKernelGGL(detection_mask_kernel<GateCandList>, dim3(n_img), dim3(1024), 0, ctx->stream, gate_const(ctx),
+                         GateCandList{ctx->cand, ctx->sort_idx + (size_t)ctx->batch * ctx->max_cand, acc_count});
     hipLaunchKernelGGL(omap_reset_kernel, dim3(256, n_img), dim3(256), 0, ctx->stream, ctx->pyr_dev, k, ctx->cand, ctx->cand_count);
     MODS_HIP_CHECK(hipGetLastError());
     ctx->omap_dirty = false;

@@ -369,6 +369,12 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
     }
     mods::Buf<mods_region> &A = c->helper_stage[k];
     size_t used = 0;
+    auto gate_tally = [&](mods_ctx *w, int slot, int image) {   // a masked view's gate counts -> the call's sums (the view has been waited for)
+      if (slot >= (int)w->gate_had_mask.size() || !w->gate_had_mask[slot]) return;
+      int v[2] = {0, 0};
+      if (mods::copy_wait(w->stream, v, w->gate_counts_dev + 2 * (size_t)slot, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
+      c->gate_ladder[2 * image] += v[0]; c->gate_ladder[2 * image + 1] += v[1];
+    };
     auto park = [&](int ji, int slot) {                         // regions of context slot `slot` -> this worker's arena
       ViewJob &j = jobs[ji];
       const size_t need = used + (size_t)j.nr * (j.want_half ? 2 : 1);
@@ -397,15 +403,18 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
     for (int u; (u = next.fetch_add(1)) < (int)units.size();) {
       const Unit un = units[u];
       ViewJob &j = jobs[un.a];
+      wk->gate_owner = c;                                       // the caller's detection masks, whichever context runs the view
       if (un.b >= 0 && wk->batch >= 2) {                        // both images of the pair through one chain of launches
         ViewJob &j2 = jobs[un.b];
         int nd[2] = {0, 0}, nr[2] = {0, 0};
+        wk->gate_image[0] = 0; wk->gate_image[1] = 1;
         j.rc = mods_detect_describe_view2_dev(wk, img1_dev, img2_dev, w1, h1, w1, j.vp.tilt, j.vp.phi, j.vp.zoom, j.initSigma, j.doBlur, &dets[j.d],
                                               &j.desc, nullptr, nd, nr);
         j2.rc = j.rc;
         if (!j.rc) {
           j.nd = nd[0]; j.nr = nr[0]; j.unoriented = mods_unoriented_count(wk, 0);
           j2.nd = nd[1]; j2.nr = nr[1]; j2.unoriented = mods_unoriented_count(wk, 1);
+          gate_tally(wk, 0, 0); gate_tally(wk, 1, 1);
           park(un.a, 0);
           if (!j.rc) park(un.b, 1);
         }
@@ -419,13 +428,16 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
         ViewJob &q = jobs[ji];
         const float *img = q.im ? img2_dev : img1_dev;
         const int w = q.im ? w2 : w1, h = q.im ? h2 : h1;
+        wk->gate_image[0] = q.im;                               // (slot 0 of the worker holds image q.im of the call)
         q.rc = mods_detect_describe_view_dev(wk, img, w, h, w, q.vp.tilt, q.vp.phi, q.vp.zoom, q.initSigma, q.doBlur, &dets[q.d], &q.desc, nullptr,
                                              &q.nd, &q.nr);
-        if (!q.rc) { q.unoriented = mods_unoriented_count(wk, 0); park(ji, 0); }
+        if (!q.rc) { q.unoriented = mods_unoriented_count(wk, 0); gate_tally(wk, 0, q.im); park(ji, 0); }
         if (q.rc) q.err = mods_last_error();
         owner[ji] = k;
       }
     }
+    wk->gate_owner = nullptr; wk->gate_image[0] = 0; wk->gate_image[1] = 1;
+    if (!wk->gate_tab_host.empty()) mods::dev_state_changed(wk);   // (its gate table may hold another slot order than a plain call's)
     (void)mods::stream_wait(wk->stream);
   };
   std::vector<std::thread> pool;
@@ -461,6 +473,8 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
   for (int d = 0; d < n_det; d++) if (!reps1[d] || !reps2[d]) { set_error("match_ladder: null region bank"); return MODS_E_ARG; }
   memset(res, 0, sizeof(*res));
   for (int i = 0; i < 9; i++) res->H[i] = -1;
+  for (auto &t : c->gate_ladder) t = 0;         // mods_ctx_detection_mask_counts after this call: the sums over its views
+  c->gate_ladder_last = true;
   int rc, curr_matches = 0;
   struct PerDet {
     std::vector<mods_view_par> hist = std::vector<mods_view_par>(1024);

@@ -459,6 +459,8 @@ int mser_detect(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int 
   hipLaunchKernelGGL(mser_export_kernel, dim3((n_keys + 255) / 256), dim3(256), 0, c->stream, n_keys, ot, ot + n_keys, ot + 2 * (size_t)n_keys,
                      ot + 3 * (size_t)n_keys, ot + 4 * (size_t)n_keys, T.u_slot, T.u_thresh, w, S.ell, c->max_cand, c->keys_dev);
   MODS_HIP_CHECK(hipGetLastError());
+  // detection masks: keys with an off-mask centre leave the exported list here - after the count modes above, before orientation
+  if ((rc = launch_detection_mask_keys(c, n_img))) return rc;
   MODS_HIP_CHECK(hipMemcpyAsync(S.h_counters, S.counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   if (S.h_counters[2]) { set_error("MSER: %llu regions whose runs disagree with the growth's area", S.h_counters[2]); return MODS_E_HIP; }
@@ -467,9 +469,11 @@ int mser_detect(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int 
 
 // DetectAffineRegions for whichever detector the parameter set names (imagerepresentation.cpp:733-783); tilt, zoom: the view's
 // SynthImage fields (1, 1 for the image itself), which scale regionsNumber (scale-space-detector.cpp:20-21, extrema.cpp:201-202)
-int detect_any(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *par, double tilt, double zoom) {
-  if (par->detectorType == MODS_DET_MSER) return mser_detect(c, img_dev, n_img, w, h, stride, par, tilt, zoom);
+int detect_any(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *par, double tilt, double zoom,
+               const DetGateFrame *frame) {
   int rc;
+  if ((rc = detection_mask_bind(c, n_img, w, h, frame))) return rc;
+  if (par->detectorType == MODS_DET_MSER) return mser_detect(c, img_dev, n_img, w, h, stride, par, tilt, zoom);
   if ((rc = pyramid_configure(c, w, h, n_img, par))) return rc;
   if (tilt > 2.0 || zoom < 0.5) c->reg_number_eff = (int)floor(zoom * (double)par->regionsNumber / tilt);
   if ((rc = pyramid_build(c, img_dev, stride))) return rc;

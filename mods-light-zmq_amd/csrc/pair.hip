@@ -164,9 +164,11 @@ int mods::pair_gpu_stage(mods_ctx *c, const float *img_dev, int w, int h, int st
 // 0 fp32 in HBM, 1 fp32 in (pinned) host memory, 2 8-bit grey in (pinned) host memory - host images are uploaded on
 // the context's stream, so the transfer of one worker overlaps the kernels of the others.
 int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds, int n_pairs, int w, int h, const mods_pair_params *par,
-                          mods_pair_result *const *res, TentList *const *lists) {
+                          mods_pair_result *const *res, TentList *const *lists, const unsigned char *const *masks) {
   if (!c || !img || !par || !res || !lists || n_pairs < 1) { set_error("match_pairs: null argument"); return MODS_E_ARG; }
-  if (n_pairs == 1 && (!kinds || kinds[0] == 0) && !c->clahe_on) return pair_gpu_stage(c, (const float *)img[0], w, h, w, par, res[0], lists[0]);
+  bool any_mask = false;
+  for (int i = 0; masks && i < n_pairs; i++) any_mask = any_mask || masks[i] != nullptr;
+  if (n_pairs == 1 && (!kinds || kinds[0] == 0) && !c->clahe_on && !any_mask && !c->det_mask_staged) return pair_gpu_stage(c, (const float *)img[0], w, h, w, par, res[0], lists[0]);
   if (c->batch < 2 * n_pairs) { set_error("match_pairs: context batch %d < %d images", c->batch, 2 * n_pairs); return MODS_E_ARG; }
   if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("match_pairs: image larger than the context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));
@@ -199,6 +201,22 @@ int mods::pairs_gpu_stage(mods_ctx *c, const void *const *img, const int *kinds,
     }
   }
   MODS_HIP_CHECK(hipGetLastError());
+  // detection masks of the batch's pairs ([2][h][w] bytes on the host, null: an unmasked pair): staged next to the images, on the same
+  // stream, and set as the masks of the batch's images 2 i, 2 i + 1.  The set of masked slots is device state a recorded call
+  // depends on: a batch whose set differs from the one before it is not taken for its repeat
+  if (any_mask || c->det_mask_staged) {
+    std::vector<DetMaskDev> want((size_t)c->batch, DetMaskDev{nullptr, 0, 0, 0, 0});
+    if (any_mask) MODS_HIP_CHECK(mods::reserve_pool(c, c->det_mask_stage, (size_t)c->batch * c->max_w * c->max_h, (size_t)c->batch * c->max_w * c->max_h));
+    for (int i = 0; i < n_pairs; i++) {
+      if (!masks || !masks[i]) continue;
+      unsigned char *st = c->det_mask_stage + plane2 * i;
+      MODS_HIP_CHECK(hipMemcpyAsync(st, masks[i], plane2, hipMemcpyHostToDevice, c->stream));
+      want[2 * i] = DetMaskDev{st, w, h, w, 0};
+      want[2 * i + 1] = DetMaskDev{st + plane2 / 2, w, h, w, 0};
+    }
+    if (!(want == c->det_masks)) { c->det_masks = want; mods::dev_state_changed(c); }
+    c->det_mask_staged = any_mask;
+  }
   std::vector<int> nd(n_img), nr(n_img);
   int rc;
   // (queued ahead of the detect stage's scope: no MODS_STAGE_* bracket includes these two launches, rocprofv3 shows their time)

@@ -25,6 +25,7 @@ namespace mods {
 struct Job {
   long tag = 0;
   const void *img = nullptr;
+  const unsigned char *mask = nullptr;   // detection masks of the pair ([2][h][w] bytes on the host) or null
   int kind = 0;                   // 0 fp32 in HBM, 1 fp32 on the host, 2 8-bit grey on the host
   mods_pair_result res;
   TentList list;
@@ -99,12 +100,13 @@ static void gpu_worker(mods_pipeline *p, mods_ctx *ctx) {
     }
     const int n = (int)js.size();
     std::vector<const void *> imgs(n);
+    std::vector<const unsigned char *> masks(n);
     std::vector<int> kinds(n);
     std::vector<mods_pair_result *> res(n);
     std::vector<TentList *> lists(n);
-    for (int i = 0; i < n; i++) { imgs[i] = js[i]->img; kinds[i] = js[i]->kind; res[i] = &js[i]->res; lists[i] = &js[i]->list; }
+    for (int i = 0; i < n; i++) { imgs[i] = js[i]->img; masks[i] = js[i]->mask; kinds[i] = js[i]->kind; res[i] = &js[i]->res; lists[i] = &js[i]->list; }
     const long long c0 = thread_cpu_ns();
-    const int rc = pairs_gpu_stage(ctx, imgs.data(), kinds.data(), n, p->w, p->h, &p->par, res.data(), lists.data());
+    const int rc = pairs_gpu_stage(ctx, imgs.data(), kinds.data(), n, p->w, p->h, &p->par, res.data(), lists.data(), masks.data());
     p->cpu_gpu_ns.fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed);
     const std::string err = rc ? mods_last_error() : "";
     {
@@ -308,10 +310,10 @@ int mods_pipeline_create_clahe(int device, int w, int h, const mods_pair_params 
 
 // Queues one pair ([2][h][w] fp32 in HBM; must stay valid until its result has been fetched).  Blocks
 // only while too many pairs are in flight.
-static int submit_any(mods_pipeline *p, const void *img, int kind, long tag) {
+static int submit_any(mods_pipeline *p, const void *img, int kind, long tag, const unsigned char *mask = nullptr) {
   if (!p || !img) return MODS_E_ARG;
   auto j = std::make_shared<Job>();
-  j->tag = tag; j->img = img; j->kind = kind;
+  j->tag = tag; j->img = img; j->kind = kind; j->mask = mask;
   {
     std::unique_lock<std::mutex> lk(p->mu);
     p->cv_space.wait(lk, [&] { return (int)p->q_order.size() < p->max_in_flight; });
@@ -339,6 +341,11 @@ int mods_pipeline_submit_host(mods_pipeline *p, const float *img_host, long tag)
   return submit_any(p, img_host, 1, tag);
 }
 int mods_pipeline_submit_host_u8(mods_pipeline *p, const unsigned char *img_host, long tag) { return submit_any(p, img_host, 2, tag); }
+// ... with the pair's detection masks (mods_ctx_detection_mask): two stacked masks of the images' geometry, staged and uploaded with
+// the images; null: an unmasked pair.  Must stay valid as long as the images
+int mods_pipeline_submit_host_u8_masked(mods_pipeline *p, const unsigned char *img_host, const unsigned char *mask_host, long tag) {
+  return submit_any(p, img_host, 2, tag, mask_host);
+}
 
 // Result of the oldest submitted pair (blocks until it is verified).  Returns MODS_E_ARG when nothing
 // is in flight.

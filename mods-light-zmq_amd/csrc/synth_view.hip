@@ -288,7 +288,10 @@ static int view_detect_describe(mods_ctx *c, const float *const *src_dev, int n_
   for (int i = 0; i < n_src; i++)
     if ((rc = mods_synth_view_dev(c, src_dev[i], w, h, stride, &g, doBlur, c->view_dev + i * vpx))) return rc;
   // DetectAffineKeypoints / DetectMSERs scale regionsNumber by the SynthImage fields |tilt|, zoom (scale-space-detector.cpp:20-21, extrema.cpp:201-202)
-  if ((rc = detect_any(c, c->view_dev, n_src, g.w_new, g.h_new, g.w_new, det, g.tilt, g.zoom))) return rc;
+  // (detection masks live in the original image: the gate tests the centres describe_run_view's reprojection will write)
+  DetGateFrame frame;
+  (void)view_region_frame(g.H, g.w_new, g.h_new, w, h, &frame);
+  if ((rc = detect_any(c, c->view_dev, n_src, g.w_new, g.h_new, g.w_new, det, g.tilt, g.zoom, &frame))) return rc;
   if ((rc = describe_run_view(c, {c->view_dev}, n_src, g.w_new, g.h_new, desc, g.H, w, h, nullptr))) return rc;
   // every count and the error flag of the view in ONE round trip (pinned host words; three synchronisations before)
   int *hc = c->host_counts;
