@@ -143,6 +143,7 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
                                  * accept, compaction and emit - in two scopes, the host reads the length of the pair list between them */
        MODS_STAGE_LOCAL_AFFINE, /* the local affine consistency filter (mods_filter_local_affine, mods_ctx_local_affine): prep, both sweeps,
                                    keep and compaction */
+       MODS_STAGE_REPROJECT_H,  /* the post-pass of a homography view (reproject_regions_h_kernel): reprojection, tests and compaction */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -407,6 +408,59 @@ int mods_view_fetch(mods_ctx *ctx, const mods_view_geom *geom, float *dst_host);
  * cv::GaussianBlur(Size(kx,ky), sx, sy, BORDER_REFLECT_101) */
 int mods_warp_affine(mods_ctx *ctx, const float *src, int w, int h, const double *M, int dw, int dh, float cval, float *dst);
 int mods_gauss_blur_xy(mods_ctx *ctx, const float *src, int w, int h, int kx, int ky, double sx, double sy, float *dst);
+
+/* ---- homography views ------------------------------------------------------------------------
+ * A view through an arbitrary homography, and its regions carried back with a per-region linearisation: GenerateSynthImageByH,
+ * ReprojectByHReal, ReprojectRegionsBackReal and linH (synth-detection.cpp:519-629, 1498-1518), which the reference began and
+ * never wired in.  The views above are affine only; these entry points are their projective counterparts and share none of
+ * their kernels (csrc/view_h.hip).
+ *
+ * The warp.  H is row-major and maps original -> view; G = adj(H) / det(H) (the closed form used throughout this library);
+ * d0 = (H6 cx + H7 cy) + H8 at (cx, cy) = ((w - 1) / 2, (h - 1) / 2).  MODS_E_ARG when det(H) == 0, d0 == 0 or an entry of H is
+ * not finite.  For the destination pixel (x, y), every operation in fp64 with one rounding:
+ *     W = (G6 x + G7 y) + G8;   unless W d0 > 0 the pixel is cval (it lies on or behind the horizon);
+ *     t = 32 / W;  fX = ((G0 x + G1 y) + G2) t;  fY = ((G3 x + G4 y) + G5) t;   a NaN makes the pixel cval;
+ *     fX, fY are clamped to [INT_MIN, INT_MAX];  X = (int)rint(fX), Y = (int)rint(fY);
+ *     sx = X >> 5, sy = Y >> 5, fx = (X & 31) / 32.f, fy = (Y & 31) / 32.f,
+ * and from there what mods_warp_affine does: the weights (1 - fy)(1 - fx), (1 - fy) fx, fy (1 - fx), fy fx in fp32, the sum
+ * v0 w0 + v1 w1 + v2 w2 + v3 w3 in that order, taps outside the source reading cval.  Nothing is stepped along a row.
+ * The contract is shaped after cv::warpPerspective(INTER_LINEAR, BORDER_CONSTANT); parity with OpenCV is unpinned, and the
+ * W d0 > 0 rule is a deliberate difference: OpenCV mirrors the far side of the horizon into the image, this warp writes cval.
+ *
+ * mods_view_geometry_h (host only, no device): H, identity = 0, tilt = zoom = 1, w_rot x h_rot = w x h; w_new / h_new =
+ * floor(xmax) / floor(ymax) of the images of the corners (0, 0), (0, h), (w, 0), (w, h), each coordinate truncated to an integer
+ * first as the reference's cv::Point does, clipped to clip_w x clip_h (both > 0) and to >= 0; a corner with den d0 <= 0 is
+ * MODS_E_ARG.  Blur: sigma_x = sigma_y = initSigma / 4, ksize = floor(8 sigma + 1), made odd, at least 3.
+ * mods_warp_perspective: host pointers, dense rows - the warp alone.
+ * mods_synth_view_h_dev: the isotropic BORDER_REFLECT_101 blur when doBlur (on a dense copy: w h <= max_w max_h batch), then
+ * the warp with cval = 128 into dst_dev (geom->w_new x geom->h_new, dense).
+ * mods_detect_describe_view_h_dev: synthesise -> detect -> orient and describe the view as a plain image in its own frame
+ * (border tests in the view frame) -> one pass over the finished regions of slot 0 and their HalfRootSIFT twins.  For a region
+ * (x, y, A, s): den = (G6 x + G7 y) + G8, dropped unless den d0 > 0; rx = ((G0 x + G1 y) + G2) / den, ry likewise; L = linH(x, y,
+ * G); A' = L A; s, the response and the descriptor stay.  Kept iff 0 < rx < w, 0 < ry < h, its measurement box (the affine views'
+ * box, (int)(k_sigma s)) does not touch the border of the original, and - when slot 0 has a detection mask, which must be w x h -
+ * (rx, ry) is on it by mods_detection_mask_test's rule.  The detector itself runs unmasked here: unlike with the gate of the
+ * other entry points, off-mask regions still used detector budget (regionsNumber, the count modes).  The survivors keep their
+ * order, id = the new position; slot 0 holds them in the ORIGINAL frame, ready for mods_imgrep_append_ctx[_half].  A view under
+ * 16 x 16 yields no regions, one larger than the context is MODS_E_ARG.
+ * mods_rematch_under_h_dev: the second stage of a two-stage match.  H: a verified img1 -> img2 homography.  Image 1 is seen
+ * through H (clipped to w2 x h2) and its regions join rep1; with both != 0 image 2 is seen through inv(H) (clipped to w1 x h1)
+ * and its regions join rep2; then the banks go through exactly what mods_match_verify_reps runs.  par->ransac.useF must name a
+ * homography model (0 or 3; mods_match_verify_reps itself has no image size for 3), else MODS_E_ARG.  Detection masks are
+ * numbered as in the pair entry points: the mask of image 0 filters the regions of image 1's view, that of image 1 those of
+ * image 2's.
+ * mods_test_warp_perspective_strided / mods_test_reproject_regions_h: the test seams - the warp of a host image with a row
+ * stride, and the post-pass over n host regions (in / out; `half`: their twins or NULL) through slot 0, whose mask applies. */
+int mods_view_geometry_h(int w, int h, const double *H, int clip_w, int clip_h, double initSigma, mods_view_geom *out);
+int mods_warp_perspective(mods_ctx *ctx, const float *src, int w, int h, const double *H, int dw, int dh, float cval, float *dst);
+int mods_synth_view_h_dev(mods_ctx *ctx, const float *src_dev, int w, int h, int stride, const mods_view_geom *geom, int doBlur,
+                          float *dst_dev);
+int mods_detect_describe_view_h_dev(mods_ctx *ctx, const float *src_dev, int w, int h, int stride, const double *H, int clip_w, int clip_h,
+                                    double initSigma, int doBlur, const mods_hessaff_params *det, const mods_describe_params *desc,
+                                    mods_view_geom *geom_out, int *n_detected, int *n_regions);
+int mods_test_warp_perspective_strided(mods_ctx *ctx, const float *src, int w, int h, int stride, const double *H, int dw, int dh, float cval,
+                                       float *dst);
+int mods_test_reproject_regions_h(mods_ctx *ctx, const double *H, int ow, int oh, mods_region *regions, mods_region *half, int n, int *n_out);
 
 /* ---- B4: matching ------------------------------------------------------------------------------
  * Replaces  int MatchFlannFGINN(const AffineRegionList &q, const AffineRegionList &t,
@@ -813,6 +867,11 @@ int mods_multi_assign(const double *areas, int n, int n_dev, int *owner);
  * k1 / k2 files of an earlier run); one matching + duplicate filtering + verification pass, no detection. */
 int mods_match_verify_reps(mods_ctx *ctx, mods_imgrep *rep1, mods_imgrep *rep2, double fginn_ratio, const mods_pair_params *par,
                            mods_ladder_result *res, double *matches_out, int max_matches);
+/* The rematch step under a verified H ("homography views" above): img1_dev, img2_dev dense fp32 in HBM; the context must hold
+ * both images and both views (max_w max_h >= w1 h1 and >= w2 h2). */
+int mods_rematch_under_h_dev(mods_ctx *ctx, const float *img1_dev, int w1, int h1, const float *img2_dev, int w2, int h2, const double *H,
+                             int both, double initSigma, int doBlur, const mods_pair_params *par, mods_imgrep *rep1, mods_imgrep *rep2,
+                             double fginn_ratio, mods_ladder_result *res, double *matches_out, int max_matches);
 /* plain device-memory helpers for callers that do not link a HIP runtime themselves (the mods CLI) */
 int mods_host_alloc(size_t bytes, void **out);     /* pinned host memory */
 int mods_host_free(void *p);

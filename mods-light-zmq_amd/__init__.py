@@ -20,7 +20,7 @@ STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
 # MODS_STAGE_* added after that list was pinned by its users: their indices follow it
-STAGES_LATER = ["local_affine"]
+STAGES_LATER = ["local_affine", "reproject_h"]
 
 
 def stage_index(name):
@@ -202,6 +202,15 @@ class ViewGeom(C.Structure):
 def view_geometry(w, h, tilt, phi, zoom=1.0, init_sigma=0.2):
     g = ViewGeom()
     _check(lib().mods_view_geometry(w, h, C.c_double(tilt), C.c_double(phi), C.c_double(zoom), C.c_double(init_sigma), C.byref(g)))
+    return g
+
+
+def view_geometry_h(w, h, H, clip_w=None, clip_h=None, init_sigma=0.2):
+    """mods_view_geometry_h: the geometry of the view of a w x h image through the homography H (original -> view), its size
+    clipped to clip_w x clip_h (default: the image's own); no device needed"""
+    g = ViewGeom()
+    Hc = np.ascontiguousarray(H, np.float64).ravel()
+    _check(lib().mods_view_geometry_h(w, h, _vp(Hc), clip_w or w, clip_h or h, C.c_double(init_sigma), C.byref(g)))
     return g
 
 
@@ -718,6 +727,51 @@ class Context:
                                                    C.c_double(zoom), C.c_double(init_sigma), do_blur, C.byref(det),
                                                    C.byref(desc), C.byref(g), C.byref(nd), C.byref(nr)))
         return g, nd.value, nr.value
+
+    # ---- homography views (include/mods_hip.h, "homography views")
+    def warp_perspective(self, img, H, dw, dh, cval=128.0, stride=None):
+        """mods_warp_perspective: img (h x w) through H (original -> view) into dh x dw.  stride: the warp reads the first w columns
+        of img's rows, which then are `stride` floats apart (mods_test_warp_perspective_strided)"""
+        a = np.ascontiguousarray(img, np.float32)
+        Hc = np.ascontiguousarray(H, np.float64).ravel()
+        out = np.empty((dh, dw), np.float32)
+        if stride is None:
+            _check(lib().mods_warp_perspective(self.h, _fp(a), a.shape[1], a.shape[0], _vp(Hc), dw, dh, C.c_float(cval), _fp(out)))
+        else:
+            w = a.shape[1]
+            padded = np.full((a.shape[0], stride), np.float32(np.nan), np.float32)   # the gap is never read
+            padded[:, :w] = a
+            _check(lib().mods_test_warp_perspective_strided(self.h, _fp(padded), w, a.shape[0], stride, _vp(Hc), dw, dh, C.c_float(cval),
+                                                            _fp(out)))
+        return out
+
+    def synth_view_h_dev(self, src_ptr, w, h, geom, dst_ptr, do_blur=1, stride=None):
+        _check(lib().mods_synth_view_h_dev(self.h, C.c_void_p(src_ptr), w, h, stride or w, C.byref(geom), do_blur, C.c_void_p(dst_ptr)))
+
+    def detect_describe_view_h_dev(self, src_ptr, w, h, H, clip_w=None, clip_h=None, init_sigma=0.2, do_blur=1, det=None, desc=None,
+                                   stride=None):
+        """One homography view of the w x h image at src_ptr (HBM): returns (geom, n_detected, n_regions); the regions (original
+        frame) stay in slot 0 of the context (regions_fetch(0))."""
+        det = det or HessAffParams.default()
+        desc = desc or DescribeParams.default()
+        Hc = np.ascontiguousarray(H, np.float64).ravel()
+        g = ViewGeom()
+        nd, nr = C.c_int(), C.c_int()
+        _check(lib().mods_detect_describe_view_h_dev(self.h, C.c_void_p(src_ptr), w, h, stride or w, _vp(Hc), clip_w or w, clip_h or h,
+                                                     C.c_double(init_sigma), do_blur, C.byref(det), C.byref(desc), C.byref(g),
+                                                     C.byref(nd), C.byref(nr)))
+        return g, nd.value, nr.value
+
+    def reproject_regions_h(self, regions, H, ow, oh, half=None):
+        """mods_test_reproject_regions_h: the post-pass of a homography view over host regions (REGION_DTYPE, view frame) and
+        optionally their HalfRootSIFT twins; returns the survivors in the original frame (and the twins' survivors when given)"""
+        r = np.ascontiguousarray(regions, REGION_DTYPE).copy()
+        hh = None if half is None else np.ascontiguousarray(half, REGION_DTYPE).copy()
+        Hc = np.ascontiguousarray(H, np.float64).ravel()
+        n = C.c_int()
+        _check(lib().mods_test_reproject_regions_h(self.h, _vp(Hc), ow, oh, _vp(r) if len(r) else None,
+                                                   _vp(hh) if hh is not None and len(hh) else None, len(r), C.byref(n)))
+        return (r[:n.value].copy(), hh[:n.value].copy()) if hh is not None else r[:n.value].copy()
 
     def view_pixels(self, geom):
         """Host copy of the last synthesised view."""
@@ -1608,6 +1662,20 @@ def match_verify_reps(ctx, rep1, rep2, fginn_ratio=0.8, params=None, max_matches
     m = np.zeros((max(max_matches, 1), 4), np.float64)
     _check(lib().mods_match_verify_reps(ctx.h, rep1.h, rep2.h, C.c_double(fginn_ratio), C.byref(params), C.byref(res),
                                         m.ctypes.data_as(C.c_void_p) if max_matches else None, max_matches))
+    return res, m[:min(res.n_inliers, max_matches)]
+
+
+def rematch_under_h_dev(ctx, img1_ptr, w1, h1, img2_ptr, w2, h2, H, rep1, rep2, both=0, init_sigma=0.2, do_blur=1, fginn_ratio=0.8,
+                        params=None, max_matches=0):
+    """mods_rematch_under_h_dev: image 1 seen through the verified H (img1 -> img2) is detected and described, its regions join
+    rep1 (both: image 2 through inv(H) joins rep2), and the banks are matched and verified as match_verify_reps does."""
+    params = params or PairParams.default()
+    Hc = np.ascontiguousarray(H, np.float64).ravel()
+    res = LadderResult()
+    m = np.zeros((max(max_matches, 1), 4), np.float64)
+    _check(lib().mods_rematch_under_h_dev(ctx.h, C.c_void_p(img1_ptr), w1, h1, C.c_void_p(img2_ptr), w2, h2, _vp(Hc), int(both),
+                                          C.c_double(init_sigma), int(do_blur), C.byref(params), rep1.h, rep2.h, C.c_double(fginn_ratio),
+                                          C.byref(res), m.ctypes.data_as(C.c_void_p) if max_matches else None, max_matches))
     return res, m[:min(res.n_inliers, max_matches)]
 
 

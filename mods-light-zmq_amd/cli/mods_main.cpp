@@ -75,6 +75,11 @@ struct Config {
   // the verified model (mods_match_guided_reps) and the de-duplicated result is what the matches file holds
   int guided = 0, guided_max_dist = 0, guided_one_to_one = 1;
   double guided_radius = 0, guided_ratio = 0.9;
+  // [Matching] rematchUnderH (no counterpart in the reference's live path; it began GenerateSynthImageByH and never called it):
+  // under ver_type 0, once the step loop has verified an H, image 1 is seen through it, detected and described, its regions join
+  // bank 1 (2: image 2 through inv(H) joins bank 2 as well) and the banks are matched and verified once more; every output
+  // then comes from that pass
+  int rematch = 0;
   // [OverlapMatching] doOverlapMatch / overlapError (io_mods.cpp:685-687) and matchOriented (ours): with ver_type 1 every detector's
   // banks go through mods_match_overlap_reps under the ground-truth H and the count is printed as mods.cpp:522-523 does
   int overlap = 0, overlap_oriented = 1;
@@ -228,6 +233,8 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->guided_max_dist = (int)ini.GetInteger("Matching", "guidedMaxDist", 0);
   cfg->guided_one_to_one = (int)ini.GetInteger("Matching", "guidedOneToOne", 1);
   if (cfg->guided != 0 && cfg->guided != 1) { std::cerr << "[Matching] guidedMatching must be 0 or 1" << std::endl; return 1; }
+  cfg->rematch = (int)ini.GetInteger("Matching", "rematchUnderH", 0);
+  if (cfg->rematch < 0 || cfg->rematch > 2) { std::cerr << "[Matching] rematchUnderH must be 0, 1 (image 1 through H) or 2 (both images)" << std::endl; return 1; }
   if (!std::isfinite(cfg->guided_radius) || !(cfg->guided_radius > 0)) { std::cerr << "[Matching] guidedRadius must be a positive number of pixels, not " << cfg->guided_radius << std::endl; return 1; }
   if (!(cfg->guided_ratio > 0 && cfg->guided_ratio <= 1)) { std::cerr << "[Matching] guidedRatio must lie in (0, 1], not " << cfg->guided_ratio << std::endl; return 1; }
   if (cfg->guided_max_dist < 0) { std::cerr << "[Matching] guidedMaxDist must not be negative (0 = no cap)" << std::endl; return 1; }
@@ -911,6 +918,36 @@ int main(int argc, char **argv) {
                                           cfg.groups.empty() ? nullptr : cfg.groups.data(), cfg.group_pos, (int)cfg.steps.size() / n_det, n_det, cfg.min_matches,
                                           &cfg.pair, reps1.data(), reps2.data(), &res, matches.data(), 1 << 20))
     return fail("matching");
+  // [Matching] rematchUnderH: the second stage under the H the step loop verified (mods_rematch_under_h_dev); the matches, the H
+  // file, the log counts and the images below are that pass's
+  int rematch_added[2] = {0, 0}, rematch_before = -1;
+  if (cfg.rematch) {
+    if (pre_extracted || multi) std::cerr << "Note: [Matching] rematchUnderH is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
+    else if (ver_type != 0 || cfg.pair.ransac.useF != 0)
+      std::cerr << "Note: [Matching] rematchUnderH is ignored unless LO-RANSAC verifies a homography (verification type 0, aContrario = 0)" << std::endl;
+    else if (!hessian_only) std::cerr << "Note: [Matching] rematchUnderH is ignored with several detectors or groups (it extends the one HessianAffine bank)" << std::endl;
+    else {
+      bool have_h = res.n_inliers > 0 && res.steps_done > 0;
+      bool all_m1 = true;
+      for (int i = 0; i < 9; i++) { if (!std::isfinite(res.H[i])) have_h = false; if (res.H[i] != -1.0) all_m1 = false; }
+      if (!have_h || all_m1) { if (cfg.verbose) std::cerr << "Rematch under H: no verified model, skipped" << std::endl; }
+      else {
+        const mods_ladder_step &last = steps[(size_t)res.steps_done - 1];
+        const int n1 = mods_imgrep_count(reps1[0]), n2 = mods_imgrep_count(reps2[0]);
+        mods_ladder_result again;
+        if (mods_rematch_under_h_dev(ctx, (const float *)d1, img1.w, img1.h, (const float *)d2, img2.w, img2.h, res.H, cfg.rematch == 2, last.initSigma,
+                                     last.doBlur, &cfg.pair, reps1[0], reps2[0], first_ratio, &again, matches.data(), 1 << 20))
+          return fail("rematchUnderH");
+        rematch_added[0] = mods_imgrep_count(reps1[0]) - n1; rematch_added[1] = mods_imgrep_count(reps2[0]) - n2;
+        rematch_before = res.n_inliers;
+        res.n_described[0] = again.n_described[0]; res.n_described[1] = again.n_described[1];
+        res.n_tentatives = again.n_tentatives; res.n_unique = again.n_unique; res.n_inliers = again.n_inliers;
+        res.ransac_samples = again.ransac_samples; res.ransac_lo = again.ransac_lo; res.ransac_rejects = again.ransac_rejects;
+        for (int i = 0; i < 9; i++) res.H[i] = again.H[i];
+        res.ms_match += again.ms_match; res.ms_duplicates += again.ms_duplicates; res.ms_ransac += again.ms_ransac;
+      }
+    }
+  }
   // [Matching] guidedMatching = 1: the banks of every detector, in detector order, searched again under the verified model; the
   // joint list goes through the duplicate filter and replaces the rows of the matches file (the log rows stay the reference's)
   int n_guided = -1, n_guided_unique = 0;
@@ -992,6 +1029,8 @@ int main(int argc, char **argv) {
       }
       std::cerr << res.n_inliers << " RANSAC correspondences got" << std::endl;
     }
+    if (rematch_before >= 0) std::cerr << "Rematch under H: +" << rematch_added[0] << " | +" << rematch_added[1] << " regions, " << rematch_before
+                                       << " verified before, " << res.n_inliers << " after" << std::endl;
     if (n_guided >= 0) std::cerr << "Guided matching (radius " << cfg.guided_radius << ", ratio " << cfg.guided_ratio << "): " << n_guided
                                  << " correspondences, " << n_guided_unique << " after duplicate filtering" << std::endl;
   }
