@@ -663,6 +663,9 @@ int mods_test_host_errfn(int type, const double *u6, int len, const double *H, i
 int mods_test_host_u2h(const double *u6, const int *inl, int n, int reference_form, double *H);
 int mods_test_host_cov(const double *u6, const int *inl, int n, int reference_form, double *Cv);
 int mods_test_host_inlidxs(const double *err, int len, double th, int lanes, int *inl, unsigned *I, double *J);
+/* the operands of HDsSym / HDsSymMax of a model H, as every scored hypothesis record carries them (Htools.c:206-221): Hinv = H
+ * transposed as stored, H1 = minv(Hinv) (left as the inversion leaves it when H is singular) */
+int mods_test_host_sym_prepare(const double *H, double *Hinv, double *H1);
 /* mods_test_host_cov also takes reference_form 2 (the 30 folded sums in scalar code) and 100 + lanes (the sums through the SIMD
  * table of that width).  The checks LORANSACFiltering runs behind the homography (H -> inv(H^T), NaiveHCheck, H_LAF_check;
  * matching.cpp:745-805, 1014-1043, 250-308) over the correspondences with inl[i] != 0: lanes 0 = the scalar statement, 1 / 4 / 8 =
@@ -711,6 +714,33 @@ unsigned mods_test_inner_h2(unsigned seed, double *H, const double *u, unsigned 
  * after the call, prof10 (optional) = the call's breakdown (10 doubles, ransac_f_host.hpp: g_rfth_prof) */
 unsigned mods_test_rfth2(unsigned seed, const double *u, const unsigned char *hinl, double th, const double *H, unsigned len, double *F,
                          int simd, int *next_rand, double *prof10);
+/* test seams of the scoring and counting kernels behind exp_ransacHcustom / exp_ransacFcustom (csrc/ransac.hip, ransac_f.hip; they
+ * need a device).  Each one works in the calling thread's scoring workspace and goes through the function the control loop itself
+ * calls (gpu_score, gpu_score_f, gpu_upload_aux + gpu_count_pairs_begin / _end, gpu_count_models), so whatever that function
+ * chooses per launch - the grid, the gain kernel of the round's width, the buffer slot - is chosen here as it is in a run.  A seam
+ * leaves the workspace as a scoring round of a run leaves it (device counters zero), so seam calls and whole runs may alternate
+ * on one thread.  tests/ransac_score_ref.py restates what they compute.
+ *   score_h : one scoring round of n models h (n x 9, column-major as exp_ransacHcustom carries them) over u6 (len x 6), the
+ *             records filled as the run fills them (h, then Hinv = h transposed as stored and H1 = minv(Hinv), Htools.c:206-221).
+ *             err_type 0 Sampson, 1 symmetric sum, 2 symmetric max; do_sym: count the symmetric check too.  d_out[n][len] = every
+ *             error row, J_out[n] = the MSAC scores (the sequential sums of the gains in correspondence order), counts_out[n][2] =
+ *             {#(d <= th), #(d1 + d2 <= th_check), 0 without do_sym}, hyp27_out[n][27] (optional) = the records as uploaded.
+ *             n <= 16 runs the 16-column gain kernel, as a run's first batch does.
+ *   score_f : the same for n matrices f (n x 9, as exp_ransacFcustom carries them); err_type 0 Sampson, 1 symmetric epipolar;
+ *             counts_out[n][2] = {#(d <= th), #(symmetric d <= th_check)}.
+ *   count_pairs : the plane-and-parallax candidates of rFtH (DegUtils.c:353-382) given as index pairs into the n off-plane
+ *             correspondences uN (n x 6) and their plane-transferred form us (n x 6), Ht = H transposed: F = ([e]x Ht)^T made on
+ *             the device, counts[j] = #{i < n : FDs(uN_i, F_j) < limit}.  Two blocks (k0, k1 pairs, 1 .. 2048 each, indices < n)
+ *             are counted in slots 0 and 1 with both in flight, as rFtH queues them.
+ *   count_models : counts[j] = #{i < len : FDs(u6_i, Fs_j) < limit} for k matrices Fs (k x 9), as innerFH's rounds count theirs.
+ * MODS_E_ARG for null, empty or out-of-range input, MODS_E_NODEVICE, MODS_E_HIP. */
+int mods_test_ransac_score_h(const double *u6, int len, const double *h, int n, int err_type, int do_sym, double th, double th_check,
+                             double *d_out, double *J_out, int *counts_out, double *hyp27_out);
+int mods_test_ransac_score_f(const double *u6, int len, const double *f, int n, int err_type, int do_sym, double th, double th_check,
+                             double *d_out, double *J_out, int *counts_out);
+int mods_test_ransac_count_pairs(const double *uN, const double *us, int n, const double *Ht, double limit, const unsigned *pairs0, int k0,
+                                 const unsigned *pairs1, int k1, unsigned *counts0, unsigned *counts1);
+int mods_test_ransac_count_models(const double *u6, int len, const double *Fs, int k, double limit, unsigned *counts);
 
 /* ---- whole hot path for one image pair ---------------------------------------------------------
  * The step loop body of mods.cpp:202-383 for one step of HessianAffine + RootSIFT on identity views:

@@ -963,8 +963,9 @@ def list_search_grid(search, n_q, n_t, forced_splits=0):
     return out[0], out[1], out[2]
 
 
-def ransac_h(u6, th_sq, conf=0.99, max_sam=1000000, err="sampson", sym_check=1, seed_time=12345):
-    """exp_ransacHcustom exactly as LORANSACFiltering calls it (matching.cpp:731)."""
+def ransac_h(u6, th_sq, conf=0.99, max_sam=1000000, err="sampson", sym_check=1, seed_time=12345, errfn=None):
+    """exp_ransacHcustom exactly as LORANSACFiltering calls it (matching.cpp:731).  errfn: a ctypes callback with HDs's signature
+    passed in place of the library's own function - a foreign error function, which the run evaluates on the host."""
     L = lib()
     L.exp_ransacHcustom.restype = Score
     ransac_pin_seed(seed_time)
@@ -975,6 +976,8 @@ def ransac_h(u6, th_sq, conf=0.99, max_sam=1000000, err="sampson", sym_check=1, 
     data_out = np.zeros(max(18 * n, 8), np.int32)
     resids = C.POINTER(C.c_double)()
     f = [C.cast(getattr(L, name), C.c_void_p) for name in _ERR[err]]
+    if errfn is not None:
+        f[0] = C.cast(errfn, C.c_void_p)
     S = L.exp_ransacHcustom(u.ctypes.data_as(C.c_void_p), n, C.c_double(th_sq), C.c_double(conf), max_sam,
                             H.ctypes.data_as(C.c_void_p), inl.ctypes.data_as(C.c_void_p), 4,
                             data_out.ctypes.data_as(C.c_void_p), 1, C.c_uint(0), C.byref(resids), f[0], f[1], f[2],
@@ -986,8 +989,9 @@ def ransac_h(u6, th_sq, conf=0.99, max_sam=1000000, err="sampson", sym_check=1, 
 _FERR = {"sampson": ("FDs", "exFDs"), "symm": ("FDsSym", "exFDsSym")}
 
 
-def ransac_f(u6, th_sq, conf=0.99, max_sam=100000, err="sampson", sym_check=0, do_lo=1, inl_limit=0, seed_time=12345):
-    """exp_ransacFcustom exactly as LORANSACFiltering calls it (matching.cpp:722)."""
+def ransac_f(u6, th_sq, conf=0.99, max_sam=100000, err="sampson", sym_check=0, do_lo=1, inl_limit=0, seed_time=12345, errfn=None):
+    """exp_ransacFcustom exactly as LORANSACFiltering calls it (matching.cpp:722).  errfn: a ctypes callback with FDs's signature
+    passed in place of the library's own function (evaluated on the host)."""
     L = lib()
     L.exp_ransacFcustom.restype = C.c_int
     ransac_pin_seed(seed_time)
@@ -1000,12 +1004,79 @@ def ransac_f(u6, th_sq, conf=0.99, max_sam=100000, err="sampson", sym_check=0, d
     resids = C.POINTER(C.c_double)()
     Ih = C.c_int(0)
     fds, exfds = (C.cast(getattr(L, name), C.c_void_p) for name in _FERR[err])
+    if errfn is not None:
+        fds = C.cast(errfn, C.c_void_p)
     I = L.exp_ransacFcustom(u.ctypes.data_as(C.c_void_p), n, C.c_double(th_sq), C.c_double(conf), max_sam,
                             F.ctypes.data_as(C.c_void_p), inl.ctypes.data_as(C.c_void_p), data_out.ctypes.data_as(C.c_void_p),
                             do_lo, C.c_uint(inl_limit), C.byref(resids), Hb.ctypes.data_as(C.c_void_p), C.byref(Ih), exfds, fds,
                             sym_check)
     C.CDLL(None).free(resids)
     return dict(I=I, F=F, inl=inl[:n], samples=int(data_out[0]), lo=int(data_out[1]), Ih=Ih.value, hist=data_out[2:n + 3].copy())
+
+
+def _score_round(fn, u6, models, err_type, do_sym, th, th_check, with_records):
+    u = np.ascontiguousarray(u6, np.float64)
+    m = np.ascontiguousarray(models, np.float64).reshape(-1, 9)
+    if u.ndim != 2 or u.shape[1] != 6:
+        raise ValueError("u6 must be len x 6 (x1 y1 1 x2 y2 1)")
+    n, ln = len(m), len(u)
+    d = np.zeros((n, ln), np.float64)
+    J = np.zeros(n, np.float64)
+    counts = np.zeros((n, 2), np.int32)
+    args = [_vp(u), ln, _vp(m), n, int(err_type), int(do_sym), C.c_double(th), C.c_double(th_check), _vp(d), _vp(J), _vp(counts)]
+    rec = np.zeros((n, 27), np.float64) if with_records else None
+    if with_records:
+        args.append(_vp(rec))
+    _check(fn(*args))
+    out = dict(d=d, J=J, I=counts[:, 0].copy(), Isym=counts[:, 1].copy())
+    if with_records:
+        out.update(h=rec[:, 0:9].copy(), Hinv=rec[:, 9:18].copy(), H1=rec[:, 18:27].copy())
+    return out
+
+
+def host_sym_prepare(h):
+    """mods_test_host_sym_prepare: (Hinv, H1) of a model h[9] as a scored record carries them; needs no device."""
+    h = np.ascontiguousarray(h, np.float64).reshape(9)
+    Hinv, H1 = np.zeros(9), np.zeros(9)
+    _check(lib().mods_test_host_sym_prepare(_vp(h), _vp(Hinv), _vp(H1)))
+    return Hinv, H1
+
+
+def ransac_test_score_h(u6, h, err_type, do_sym, th, th_check):
+    """mods_test_ransac_score_h: one scoring round of the models h (n x 9, column-major) over u6 through the calling thread's
+    workspace and gpu_score.  err_type 0 Sampson, 1 symmetric sum, 2 symmetric max.  Returns dict(d [n][len], J, I, Isym, and the
+    records as uploaded: h, Hinv, H1 [n][9] each)."""
+    return _score_round(lib().mods_test_ransac_score_h, u6, h, err_type, do_sym, th, th_check, True)
+
+
+def ransac_test_score_f(u6, f, err_type, do_sym, th, th_check):
+    """mods_test_ransac_score_f: the same for matrices f (n x 9) through gpu_score_f; err_type 0 Sampson, 1 symmetric epipolar."""
+    return _score_round(lib().mods_test_ransac_score_f, u6, f, err_type, do_sym, th, th_check, False)
+
+
+def ransac_test_count_pairs(uN, us, Ht, limit, pairs0, pairs1):
+    """mods_test_ransac_count_pairs: counts of two blocks of plane-and-parallax candidates (k x 2 indices into the off-plane set
+    each), slot 0 and slot 1 in flight together."""
+    uN = np.ascontiguousarray(uN, np.float64); us = np.ascontiguousarray(us, np.float64)
+    Ht = np.ascontiguousarray(Ht, np.float64).reshape(9)
+    p0 = np.ascontiguousarray(pairs0, np.uint32).reshape(-1, 2); p1 = np.ascontiguousarray(pairs1, np.uint32).reshape(-1, 2)
+    if uN.shape != us.shape or uN.ndim != 2 or uN.shape[1] != 6:
+        raise ValueError("uN and us must be n x 6")
+    c0, c1 = np.zeros(len(p0), np.uint32), np.zeros(len(p1), np.uint32)
+    _check(lib().mods_test_ransac_count_pairs(_vp(uN), _vp(us), len(uN), _vp(Ht), C.c_double(limit), _vp(p0), len(p0), _vp(p1), len(p1),
+                                              _vp(c0), _vp(c1)))
+    return c0, c1
+
+
+def ransac_test_count_models(u6, Fs, limit):
+    """mods_test_ransac_count_models: #{i : FDs(u6_i, Fs_j) < limit} of k matrices (k x 9) through gpu_count_models."""
+    u = np.ascontiguousarray(u6, np.float64)
+    F = np.ascontiguousarray(Fs, np.float64).reshape(-1, 9)
+    if u.ndim != 2 or u.shape[1] != 6:
+        raise ValueError("u6 must be len x 6")
+    c = np.zeros(len(F), np.uint32)
+    _check(lib().mods_test_ransac_count_models(_vp(u), len(u), _vp(F), len(F), C.c_double(limit), _vp(c)))
+    return c
 
 
 def loransac_h(u6, laf, params=None, seed_time=12345):

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(const double *__restr
     if (err_type != ERR_SAMPSON || do_sym) hsym_dev(uu, sh.Hinv, sh.H1, &d1, &d2);
     if (err_type == ERR_SAMPSON) d = hds_dev(uu, sh.h);
     else if (err_type == ERR_SYMSUM) d = d1 + d2;
-    else d = d1 > d2 ? d1 : d2;     // MAX(d1,d2), Htools.c:12,281
+    else d = d1 < d2 ? d2 : d1;     // MAX(d1,d2) as Htools.c:15 writes it: a NaN d2 leaves d1, a NaN d1 stays
     d_out[(size_t)k * len + i] = d;
     gain[(size_t)i * kstride + k] = trunc_quad_dev(d, th);
     inl = d <= th;
@@ -259,7 +259,7 @@ void HDsSym(const double *lin, const double *u, const double *H, double *p, int 
 void HDsSymMax(const double *lin, const double *u, const double *H, double *p, int len) {
   (void)lin;
   rs::SymH s; rs::sym_prepare(H, &s);
-  for (int i = 0; i < len; i++) { double d1, d2; rs::hsym_point(u + 6 * i, &s, &d1, &d2); p[i] = d1 > d2 ? d1 : d2; }
+  for (int i = 0; i < len; i++) { double d1, d2; rs::hsym_point(u + 6 * i, &s, &d1, &d2); p[i] = d1 < d2 ? d2 : d1; }   // MAX as Htools.c:15 writes it (NaN halves)
 }
 void HDsi(const double *lin, const double *u6, const double *H, double *p, int len, int *pts, int ni) {
   (void)lin; (void)len;
@@ -273,7 +273,7 @@ void HDsiSym(const double *lin, const double *u6, const double *H, double *p, in
 void HDsiSymMax(const double *lin, const double *u6, const double *H, double *p, int len, int *pts, int ni) {
   (void)lin; (void)len;
   rs::SymH s; rs::sym_prepare(H, &s);
-  for (int i = 0; i < ni; i++) { double d1, d2; rs::hsym_point(u6 + 6 * pts[i], &s, &d1, &d2); p[i] = d1 > d2 ? d1 : d2; }
+  for (int i = 0; i < ni; i++) { double d1, d2; rs::hsym_point(u6 + 6 * pts[i], &s, &d1, &d2); p[i] = d1 < d2 ? d2 : d1; }   // MAX as Htools.c:15 writes it (NaN halves)
 }
 // HDsidx / HDsSymidx / HDsSymidxMax are passed through LORANSACFiltering but never invoked on the
 // live path (exp_ranH.c uses them only under __LSBL_MCE__); exported for link compatibility.
@@ -304,6 +304,32 @@ int mods_ransac_warmup(int device, int len) {
 int mods_ransac_set_device(int device) { std::lock_guard<std::mutex> lk(g_cfg_mutex); g_ransac_device = device; return MODS_OK; }
 // seed >= 0: every call behaves as if time(NULL) returned `seed`; < 0: back to the wall clock
 void mods_ransac_pin_seed(long seed) { std::lock_guard<std::mutex> lk(g_cfg_mutex); g_pinned_seed = seed; }
+
+// test seam: one scoring round of n models h (n x 9, as exp_ransacHcustom carries them) over u6 through the calling thread's workspace,
+// filled and launched as ransac_h_run does it; every row, score and count of the round comes back, and the records as uploaded
+int mods_test_ransac_score_h(const double *u6, int len, const double *h, int n, int err_type, int do_sym, double th, double th_check,
+                             double *d_out, double *J_out, int *counts_out, double *hyp27_out) {
+  if (!u6 || !h || !d_out || !J_out || !counts_out || len < 1 || n < 1 || err_type < ERR_SAMPSON || err_type > ERR_SYMMAX) return MODS_E_ARG;
+  RansacGpu *ws = ransac_gpu();
+  if (!ws) return MODS_E_NODEVICE;
+  if (!ransac_ws_reserve(ws, len, n)) return MODS_E_HIP;
+  if (hipMemcpyAsync(ws->u_dev, u6, sizeof(double) * 6 * len, hipMemcpyHostToDevice, ws->stream) != hipSuccess ||
+      mods::stream_wait(ws->stream) != hipSuccess) { set_error("upload of the correspondences failed"); return MODS_E_HIP; }
+  HypDev *hyp_host = (HypDev *)ws->hyp_host.get();
+  for (int k = 0; k < n; k++) {
+    HypDev &hd = hyp_host[k];
+    memcpy(hd.h, h + 9 * (size_t)k, sizeof(hd.h));
+    rs::SymH sh; rs::sym_prepare(hd.h, &sh);
+    memcpy(hd.Hinv, sh.Hinv, sizeof(hd.Hinv)); memcpy(hd.H1, sh.H1, sizeof(hd.H1));
+  }
+  if (hyp27_out) memcpy(hyp27_out, hyp_host, sizeof(HypDev) * (size_t)n);
+  if (!gpu_score(ws, len, n, err_type, do_sym, th, th_check)) return MODS_E_HIP;
+  memcpy(J_out, ws->J_host, sizeof(double) * (size_t)n);
+  memcpy(counts_out, ws->counts_host(), sizeof(int) * 2 * (size_t)n);
+  for (int k = 0; k < n; k++)
+    if (!ransac_fetch_row(ws, len, k, d_out + (size_t)k * len)) return MODS_E_HIP;
+  return MODS_OK;
+}
 
 }  // extern "C"
 
@@ -542,6 +568,13 @@ int mods_test_host_errfn(int type, const double *u6, int len, const double *H, i
   ErrFn f = {type == 0 ? ERR_SAMPSON : type == 1 ? ERR_SYMSUM : ERR_SYMMAX, nullptr, &pts};
   f(u6, H, d.data(), len);
   memcpy(out, d.data(), sizeof(double) * len);
+  return MODS_OK;
+}
+// the operands of the symmetric errors as every scored record carries them (Htools.c:206-221): Hinv = H transposed as stored, H1 = minv(Hinv)
+int mods_test_host_sym_prepare(const double *H, double *Hinv, double *H1) {
+  if (!H || !Hinv || !H1) return MODS_E_ARG;
+  rs::SymH s; rs::sym_prepare(H, &s);
+  memcpy(Hinv, s.Hinv, sizeof(s.Hinv)); memcpy(H1, s.H1, sizeof(s.H1));
   return MODS_OK;
 }
 // u2h (Htools.c:100-132) of the correspondences inl[0..n): reference_form 1 = lin_hgN + cov_mat as written there, 0 = cov_hgN

@@ -358,6 +358,49 @@ unsigned mods_test_rfth2(unsigned seed, const double *u, const unsigned char *hi
   return I;
 }
 
+// ---- test seams of the device kernels (include/mods_hip.h): the calling thread's workspace, the production launch functions ----
+static bool test_upload_u(RansacGpu *ws, const double *u6, int len) {
+  RS_CHECK(hipMemcpyAsync(ws->u_dev, u6, sizeof(double) * 6 * len, hipMemcpyHostToDevice, ws->stream));
+  RS_CHECK(mods::stream_wait(ws->stream));
+  return true;
+}
+int mods_test_ransac_score_f(const double *u6, int len, const double *f, int n, int err_type, int do_sym, double th, double th_check,
+                             double *d_out, double *J_out, int *counts_out) {
+  if (!u6 || !f || !d_out || !J_out || !counts_out || len < 1 || n < 1 || err_type < FERR_SAMPSON || err_type > FERR_SYM) return MODS_E_ARG;
+  RansacGpu *ws = ransac_gpu();
+  if (!ws) return MODS_E_NODEVICE;
+  if (!ransac_ws_reserve(ws, len, n) || !test_upload_u(ws, u6, len)) return MODS_E_HIP;
+  HypF *hyp_host = (HypF *)ws->hyp_host.get();
+  for (int k = 0; k < n; k++) memcpy(hyp_host[k].f, f + 9 * (size_t)k, sizeof(hyp_host[k].f));
+  if (!gpu_score_f(ws, len, n, err_type, do_sym, th, th_check)) return MODS_E_HIP;
+  memcpy(J_out, ws->J_host, sizeof(double) * (size_t)n);
+  memcpy(counts_out, ws->counts_host(), sizeof(int) * 2 * (size_t)n);
+  for (int k = 0; k < n; k++)
+    if (!ransac_fetch_row(ws, len, k, d_out + (size_t)k * len)) return MODS_E_HIP;
+  return MODS_OK;
+}
+int mods_test_ransac_count_pairs(const double *uN, const double *us, int n, const double *Ht, double limit, const unsigned *pairs0, int k0,
+                                 const unsigned *pairs1, int k1, unsigned *counts0, unsigned *counts1) {
+  // (a block is at most rFtH's 2048 candidates: the slots are never regrown with one of them in flight)
+  if (!uN || !us || !Ht || !pairs0 || !pairs1 || !counts0 || !counts1 || n < 1 || k0 < 1 || k1 < 1 || k0 > 2048 || k1 > 2048) return MODS_E_ARG;
+  for (int i = 0; i < 2 * k0; i++) if (pairs0[i] >= (unsigned)n) return MODS_E_ARG;
+  for (int i = 0; i < 2 * k1; i++) if (pairs1[i] >= (unsigned)n) return MODS_E_ARG;
+  RansacGpu *ws = ransac_gpu();
+  if (!ws) return MODS_E_NODEVICE;
+  if (!gpu_upload_aux(ws, uN, us, (unsigned)n)) return MODS_E_HIP;
+  if (!gpu_count_pairs_begin(ws, 0, (unsigned)n, pairs0, k0, Ht, limit)) return MODS_E_HIP;
+  if (!gpu_count_pairs_begin(ws, 1, (unsigned)n, pairs1, k1, Ht, limit)) { (void)hipStreamSynchronize(ws->stream); return MODS_E_HIP; }
+  const bool ok0 = gpu_count_pairs_end(ws, 0, k0, counts0), ok1 = gpu_count_pairs_end(ws, 1, k1, counts1);
+  return ok0 && ok1 ? MODS_OK : MODS_E_HIP;
+}
+int mods_test_ransac_count_models(const double *u6, int len, const double *Fs, int k, double limit, unsigned *counts) {
+  if (!u6 || !Fs || !counts || len < 1 || k < 1) return MODS_E_ARG;
+  RansacGpu *ws = ransac_gpu();
+  if (!ws) return MODS_E_NODEVICE;
+  if (!ransac_ws_reserve(ws, len, 96) || !test_upload_u(ws, u6, len)) return MODS_E_HIP;
+  return gpu_count_models(ws, len, Fs, k, limit, counts) ? MODS_OK : MODS_E_HIP;
+}
+
 }  // extern "C"
 
 namespace mods {

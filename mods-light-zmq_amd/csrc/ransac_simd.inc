@@ -49,7 +49,7 @@ static inline V hds_v(V u0, V u1, V u3, V u4, V u5, const double *H) {
 void hds_all(const double *const *soa, int n_pad, const double *H, double *d) {
   for (int i = 0; i < n_pad; i += VW) st(d + i, hds_v(ld(soa[0] + i), ld(soa[1] + i), ld(soa[2] + i), ld(soa[3] + i), ld(soa[4] + i), H));
 }
-// hsym_point (Htools.c:223-240); mode 0: d1 + d2, 1: max(d1, d2) as `d1 > d2 ? d1 : d2`
+// hsym_point (Htools.c:223-240); mode 0: d1 + d2, 1: MAX(d1, d2) as Htools.c:15 writes it, `d1 < d2 ? d2 : d1` (a NaN d2 leaves d1)
 void hsym_all(const double *const *soa, int n_pad, const double *H1, const double *Hinv, int mode, double *d) {
   for (int i = 0; i < n_pad; i += VW) {
     const V u0 = ld(soa[0] + i), u1 = ld(soa[1] + i), u3 = ld(soa[2] + i), u4 = ld(soa[3] + i);
@@ -65,7 +65,7 @@ void hsym_all(const double *const *soa, int n_pad, const double *H1, const doubl
     const V d2 = xd * xd + yd * yd;
     V r;
     if (mode == 0) r = d1 + d2;
-    else r = d1 > d2 ? d1 : d2;
+    else r = d1 < d2 ? d2 : d1;
     st(d + i, r);
   }
 }

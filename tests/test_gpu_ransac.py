@@ -42,7 +42,9 @@ def _compare(got, want):
 # len == 4 branch transposes a 9x9 stack buffer of which only 72 entries were written
 # (Htools.c:107-114): the reference's result depends on uninitialised memory there.
 @pytest.mark.parametrize("n,ratio,noise", [(12, 1.0, 0.1), (20, 0.8, 0.5), (21, 0.6, 0.5), (100, 0.5, 0.5), (500, 0.5, 0.5),
-                                           (500, 0.25, 1.0), (2000, 0.3, 0.8), (1000, 0.1, 0.5), (300, 0.0, 0.5)])
+                                           (500, 0.25, 1.0), (2000, 0.3, 0.8), (1000, 0.1, 0.5), (300, 0.0, 0.5),
+                                           # list lengths on the chunk edges of the two gain kernels (128 and 384 rows)
+                                           (128, 0.5, 0.5), (129, 0.5, 0.5), (384, 0.5, 0.5), (385, 0.5, 0.5)])
 @pytest.mark.parametrize("seed", [12345, 7])
 def test_ransac_h_matches_reference(pkg, n, ratio, noise, seed):
     u = make_corr(n, ratio, noise, seed + n)
@@ -51,6 +53,18 @@ def test_ransac_h_matches_reference(pkg, n, ratio, noise, seed):
         want = refdeg.ransac_h(u, 16.0, max_sam=max_sam, err=err, sym_check=sym, seed_time=seed)
         got = pkg.ransac_h(u, 16.0, max_sam=max_sam, err=err, sym_check=sym, seed_time=seed)
         _compare(got, want)
+
+
+@pytest.mark.skipif(not refdeg.available(), reason="oracle/_ref not built")
+@pytest.mark.parametrize("seed", [12345, 7])
+def test_ransac_h_stops_one_sample_into_a_batch(pkg, seed):
+    """max_sam = 73 ends the run one sample into the third scoring batch (8, then 64, then 128 samples); the reference accepts a
+    model within its 73 samples for every error type here, so each comparison compares one"""
+    u = make_corr(500, 0.25, 1.0, seed + 500)
+    for err, sym in (("sampson", 1), ("sampson", 0), ("symm_sum", 1), ("symm_max", 0)):
+        want = refdeg.ransac_h(u, 16.0, max_sam=73, err=err, sym_check=sym, seed_time=seed)
+        assert want["samples"] == 73 and want["I"] > 0
+        _compare(pkg.ransac_h(u, 16.0, max_sam=73, err=err, sym_check=sym, seed_time=seed), want)
 
 
 @pytest.mark.skipif(not refdeg.available(), reason="oracle/_ref not built")
