@@ -144,6 +144,8 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_LOCAL_AFFINE, /* the local affine consistency filter (mods_filter_local_affine, mods_ctx_local_affine): prep, both sweeps,
                                    keep and compaction */
        MODS_STAGE_REPROJECT_H,  /* the post-pass of a homography view (reproject_regions_h_kernel): reprojection, tests and compaction */
+       MODS_STAGE_SPATIAL_SELECT, /* the spatial selection of a count mode's cut (mods_ctx_spatial_selection): radius, ranking and
+                                     compaction, behind MODS_STAGE_SORT and outside it */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -1284,6 +1286,45 @@ int mods_ctx_domain_pooling_get(const mods_ctx *ctx, int *numScales, double *sta
 int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCoef, double endCoef);
 int mods_test_sift_pooled(mods_ctx *ctx, const float *patches, int K, int ps, int rootsift, int half, int photoNorm, double maxBinValue,
                           uint8_t *out128);
+
+/* ---- spatial selection of a count-limited detector's regions (ANMS) --------------------------------------------
+ * Brown, Szeliski and Winder, "Multi-image matching using multi-scale oriented patches", CVPR 2005: adaptive non-maximal
+ * suppression.  The count modes (FixedRegNumber, RelativeRegNumber, the scaled regionsNumber of a ladder view) keep a prefix of
+ * the list sorted by |response|; with the selection on they keep as many keys, the ones with the largest suppression radius.  No
+ * counterpart in the reference: this is the contract (restated in tests/spatial_select_ref.py and held to the bit).  Off by
+ * default; with it off every entry point launches what it launches without this section.
+ *   Input        one image's exported keys K[0 .. n): |response| descending, ties in processing order - the list a call with the
+ *                count unrestricted returns.  The index in that list is the only order used.  keep = min(n, regionsNumber of the
+ *                view) for FixedRegNumber, floor((double)relativeRegionsNumber * n) for RelativeRegNumber, clamped to [0, n].
+ *   Trivial      keep <= 0 or keep >= n: the result is the prefix cut's.
+ *   Radius       xf = (float)K[i].x, yf = (float)K[i].y, a = fabsf((float)K[i].response) (lossless: the fields hold floats),
+ *                c = (float)robustness:
+ *                  r2[i] = min over j != i with fl32(c * a[j]) > a[i] of fl32(fl32(dx * dx) + fl32(dy * dy)),
+ *                  dx = fl32(xf[i] - xf[j]), dy = fl32(yf[i] - yf[j]);  r2[i] = +inf when there is no such j.
+ *                Every operation is rounded to fp32 on its own (no fused multiply-add).  0 <= c <= 1, so only a stronger key
+ *                suppresses: c = 1 is plain ANMS, c = 0 suppresses nothing; c = 0.9 is the paper's value.
+ *   Selection    the keep indices with the largest r2, ties to the smaller index: ascending order of the unique key
+ *                ((uint64)~bits(r2) << 32) | i  (non-negative floats order like their bit patterns).
+ *   Output       the selected keys in increasing index order - still |response| descending - and key_count = keep.  Orientation,
+ *                description and everything behind them see that list.
+ * mods_ctx_spatial_selection: mode 0 off, 1 on, 2 on for the calls it covers (below) and silently off for the others (what a
+ * configuration with several detectors wants; the command line uses it); another mode, or a robustness outside [0, 1] or NaN, is
+ * MODS_E_ARG (checked before ctx).  With mode 1 a detect call whose mode is FixedTh, RelativeTh or NotLessThanRegions, or whose
+ * detectorType is MSER (it exports its own list), is MODS_E_ARG before anything is launched, the message naming the key.  Every
+ * entry point that detects on the context inherits the setting: mods_detect_hessian_affine[_dev], mods_detect_describe_dev[_u8],
+ * the view calls, the pair calls, the ladders of the context (whose views keep their scaled regionsNumber), the pipeline
+ * (mods_pipeline_spatial_selection: every worker's context, before the first submit - later: MODS_E_ARG); mods_multi does not
+ * (its contexts cut by response).  keep is computed on the device and no launch is sized by it, so a recorded detect + describe
+ * graph (mods_ctx_graphs) holds the selection; it is never replayed across a change of the setting.  The launches are timed as
+ * MODS_STAGE_SPATIAL_SELECT.
+ * mods_test_spatial_select: n_img lists keys_host[n_img][max_n] (n[b] keys each, sorted as above; n_img <= the context's batch)
+ * through the launches of a detect call with keep[b] as the count: out_idx[n_img][max_n] receives the selected indices, n_out[b]
+ * their number.  The compacted lists are compared with the input keys of those indices; a difference is MODS_E_HIP. */
+int mods_ctx_spatial_selection(mods_ctx *ctx, int mode, double robustness);
+int mods_ctx_spatial_selection_get(const mods_ctx *ctx, int *mode, double *robustness);
+int mods_pipeline_spatial_selection(mods_pipeline *p, int mode, double robustness);
+int mods_test_spatial_select(mods_ctx *ctx, const mods_affkey *keys_host, int n_img, const int *n, int max_n, const int *keep,
+                             double robustness, int *out_idx, int *n_out);
 
 /* ---- match and region images: an RGB canvas in HBM and a tile rasteriser ---------------------------------------
  * The reference draws with OpenCV (DrawRegions / DrawMatches, matching.cpp:1046-1574, called at mods.cpp:452-505); OpenCV's

@@ -20,7 +20,7 @@ STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
 # MODS_STAGE_* added after that list was pinned by its users: their indices follow it
-STAGES_LATER = ["local_affine", "reproject_h"]
+STAGES_LATER = ["local_affine", "reproject_h", "spatial_select"]
 
 
 def stage_index(name):
@@ -606,6 +606,32 @@ class Context:
         k, a, b = C.c_int(), C.c_double(), C.c_double()
         _check(lib().mods_ctx_domain_pooling_get(self.h, C.byref(k), C.byref(a), C.byref(b)))
         return k.value, a.value, b.value
+
+    def spatial_selection(self, mode=1, robustness=0.9):
+        """mods_ctx_spatial_selection (ANMS): the count modes keep the keys with the largest suppression radius instead of the
+        strongest ones; mode 0 off, 1 on, 2 on for the calls it covers and off for the others"""
+        _check(lib().mods_ctx_spatial_selection(self.h, int(mode), C.c_double(robustness)))
+
+    def spatial_selection_get(self):
+        """(mode, robustness) of the context"""
+        m, r = C.c_int(), C.c_double()
+        _check(lib().mods_ctx_spatial_selection_get(self.h, C.byref(m), C.byref(r)))
+        return m.value, r.value
+
+    def test_spatial_select(self, lists, keep, robustness=0.9):
+        """mods_test_spatial_select: sorted AFFKEY_DTYPE lists (one per image slot) and their keep counts through the launches of a
+        detect call; returns the selected indices of every list"""
+        n_img = len(lists)
+        max_n = max(1, max(len(k) for k in lists))
+        keys = np.zeros((n_img, max_n), AFFKEY_DTYPE)
+        for b, k in enumerate(lists):
+            keys[b, :len(k)] = k
+        n = (C.c_int * n_img)(*[len(k) for k in lists])
+        kp = (C.c_int * n_img)(*[int(v) for v in keep])
+        idx = np.full((n_img, max_n), -1, np.int32)
+        n_out = (C.c_int * n_img)()
+        _check(lib().mods_test_spatial_select(self.h, _vp(keys), n_img, n, max_n, kp, C.c_double(robustness), _vp(idx), n_out))
+        return [idx[b, :n_out[b]].copy() for b in range(n_img)]
 
     def detect_describe_dev_u8(self, dev_ptr, n_img, w, h, det=None, desc=None, stride=None):
         """detect_describe_dev for a batch of 8-bit grey images [n_img][h][stride] in HBM (stride in bytes, default w): the same regions,
@@ -1845,6 +1871,10 @@ class Pipeline:
     def u8_strip_calls(self):
         lib().mods_pipeline_u8_strip_calls.restype = C.c_long
         return int(lib().mods_pipeline_u8_strip_calls(self.h))
+
+    def spatial_selection(self, mode=1, robustness=0.9):
+        """mods_pipeline_spatial_selection: Context.spatial_selection on every GPU worker's context, before the first submit"""
+        _check(lib().mods_pipeline_spatial_selection(self.h, int(mode), C.c_double(robustness)))
 
     def set_domain_pooling(self, num_scales, start_coef=0.5, end_coef=1.5):
         """mods_pipeline_domain_pooling: Context.set_domain_pooling on every GPU worker's context, before the first submit"""

@@ -64,6 +64,10 @@ struct Config {
   std::string mask_fn[2];
   int use_mask_files = 0;
   int mutual_check = 0;            // [Matching] mutualCheck (no counterpart in the reference): mods_ctx_match_mutual
+  // [SpatialSelection] doSpatialSelection / robustness (no counterpart in the reference): the FixedRegNumber / RelativeRegNumber steps
+  // of the scale-space detectors keep the keys with the largest suppression radius (mods_ctx_spatial_selection, mode 2)
+  int spatial = 0;
+  double spatial_c = 0.9;
   // [SIFTDescriptor] domainSizePooling (the gate; no counterpart in the reference) with the reference's numScales / startCoef /
   // endCoef (io_mods.cpp:431-433, parsed there and never used): mods_ctx_domain_pooling
   int dsp = 0, dsp_scales = 3;
@@ -268,6 +272,18 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->use_mask_files = (int)ini.GetInteger("DetectionMask", "useMaskFiles", 0);
   cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
   if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
+  cfg->spatial = (int)ini.GetInteger("SpatialSelection", "doSpatialSelection", 0);
+  if (cfg->spatial != 0 && cfg->spatial != 1) { std::cerr << "[SpatialSelection] doSpatialSelection must be 0 or 1" << std::endl; return 1; }
+  if (cfg->spatial && ini.Has("SpatialSelection", "robustness")) {   // (with the gate 0 the key is ignored)
+    std::string r = ini.GetString("SpatialSelection", "robustness", "");
+    while (!r.empty() && isspace((unsigned char)r.back())) r.pop_back();
+    char *end = nullptr;
+    cfg->spatial_c = strtod(r.c_str(), &end);
+    if (r.empty() || end != r.c_str() + r.size() || !(cfg->spatial_c >= 0.0 && cfg->spatial_c <= 1.0)) {
+      std::cerr << "[SpatialSelection] robustness must be a number in [0, 1], not " << r << std::endl;
+      return 1;
+    }
+  }
   // [LocalAffineFiltering]: the filter of the list that goes to the verification, its parameters under the names of mods_local_affine_params
   // (the library checks them when the filter is switched on)
   {
@@ -801,6 +817,23 @@ int main(int argc, char **argv) {
   if (cfg.local_affine && mods_ctx_local_affine(ctx, &cfg.la_par)) return fail("[LocalAffineFiltering]");
   if (cfg.dsp && cfg.use_zmq) { std::cerr << "[SIFTDescriptor] domainSizePooling = 1 pools SIFT histograms: it cannot be combined with the [zmqDescriptor] descriptor" << std::endl; return 1; }
   if (cfg.dsp && mods_ctx_domain_pooling(ctx, cfg.dsp_scales, cfg.dsp_start, cfg.dsp_end)) return fail("domainSizePooling");
+  if (cfg.spatial) {
+    if (pre_extracted || getenv("MODS_DEVICES")) std::cerr << "Note: [SpatialSelection] is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
+    else {
+      std::string uncovered;
+      for (int d = 0; d < n_det; d++) {
+        const mods_hessaff_params &dp = cfg.det_params[d];
+        if (dp.detectorType == MODS_DET_MSER || (dp.mode != MODS_DET_FIXED_REG_NUMBER && dp.mode != MODS_DET_RELATIVE_REG_NUMBER))
+          uncovered += (uncovered.empty() ? "" : ", ") + cfg.det_names[d];
+      }
+      if (!uncovered.empty() && cfg.verbose)
+        std::cerr << "Note: [SpatialSelection] covers the FixedRegNumber / RelativeRegNumber steps of HessianAffine, DoG and HarrisAffine; run as before: "
+                  << uncovered << std::endl;
+      // mode 2: the calls the selection does not cover run without it
+      if (mods_ctx_spatial_selection(ctx, 2, cfg.spatial_c)) return fail("[SpatialSelection]");
+      if (cfg.verbose) std::cerr << "Spatial selection (ANMS): robustness " << cfg.spatial_c << std::endl;
+    }
+  }
   if (cfg.dsp && cfg.verbose) std::cerr << "Domain-size pooling: " << cfg.dsp_scales << " domains, " << cfg.dsp_start << " .. " << cfg.dsp_end << " x mrSize" << std::endl;
   // mods.cpp:133-189: createCLAHE() (8 x 8 tiles), setClipLimit(4), on the 8-bit grey image (convertTo(CV_8UC1) of the colour average,
   // or imread's grey bytes); ImageRepresentation then takes the float of the result.  Before everything else, so that every path

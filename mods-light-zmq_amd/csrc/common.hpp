@@ -238,6 +238,10 @@ struct mods_ctx {
   mods::PinnedBuf<char> pin_arena;   // pinned host staging of a batch's tentative lists (pair pipeline), lazily allocated
   mods_hessaff_params par;
   int reg_number_eff = -1;           // par.regionsNumber after the tilt / zoom scaling of DetectAffineKeypoints (scale-space-detector.cpp:20-21)
+  // spatial selection of the count modes' cut (mods_ctx_spatial_selection; spatial_select.hip): 0 off, 1 ANMS, 2 ANMS where the
+  // call's mode and detector allow it; its scratch is sort_keys and rank_dev, dead after the export
+  int spatial_mode = 0;
+  double spatial_c = 0.9;
   int last_w = 0, last_h = 0, last_n_img = 0;
   const float *last_img_dev = nullptr; int last_stride = 0;   // the batch the pyramid was built from (sampleFromImage)
   // orientation + description
@@ -440,6 +444,22 @@ int clahe_launch(mods_ctx *ctx, const unsigned char *src, int n_img, int w, int 
 // detect.hip
 int detect_run(mods_ctx *ctx);       // NMS -> localise -> dedup -> Baumberg -> sort, for the configured batch
 size_t nms_octave_mask_words(int w, int h, int border, int n_scales);   // ballot words of one image's NMS over one octave
+// ranks of the unique 64-bit keys ctx->sort_keys[n_img][max_cand] (key_count[b] of them per image) into ctx->rank_dev: by one
+// workgroup's sort or by counting, chosen by n_img
+int rank_keys_launch(mods_ctx *ctx, int n_img, const int *key_count);
+
+// The count a count mode's cut keeps of n keys (AffineDetector::prepareKeysForExport, scale-space-detector.hpp:150-166), before the
+// clamp to [0, n]
+__host__ __device__ inline int count_mode_keep(int mode, int n, int reg_number, float rel_reg_number) {
+  if (mode == MODS_DET_FIXED_REG_NUMBER) return n < reg_number ? n : reg_number;
+  if (mode == MODS_DET_RELATIVE_REG_NUMBER) return (int)floor((double)rel_reg_number * (double)n);
+  return n;
+}
+
+// spatial_select.hip: the cut of a count mode taken by suppression radius instead of by response (mods_ctx_spatial_selection), over
+// the exported lists in ctx->keys_dev; keep_list (device, per image) stands in for the mode's count when set (the test hook)
+int spatial_select_launch(mods_ctx *ctx, int n_img, int *key_count, int mode, int reg_number, float rel_reg_number, float robustness,
+                          const int *keep_list);
 
 int detection_mask_bind(mods_ctx *ctx, int n_img, int w, int h, const DetGateFrame *frame);   // the call's masks -> the gate's table; sets gate_active
 int launch_detection_mask_keys(mods_ctx *ctx, int n_img);   // the gate over the exported key lists (MSER)

@@ -1206,10 +1206,8 @@ __global__ __launch_bounds__(256) void select_keys_kernel(int max_cand, const mo
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    int keep = n;
+    int keep = count_mode_keep(mode, n, reg_number, rel_reg_number);
     if (mode == MODS_DET_RELATIVE_TH) keep = s_cnt;
-    else if (mode == MODS_DET_FIXED_REG_NUMBER) keep = min(n, reg_number);
-    else if (mode == MODS_DET_RELATIVE_REG_NUMBER) keep = (int)floor((double)rel_reg_number * (double)n);
     else if (mode == MODS_DET_NOT_LESS_THAN_REGIONS) keep = s_cnt < reg_number ? min(reg_number, n) : min(s_cnt, n);
     key_count[b] = max(0, min(keep, n));
   }
@@ -1250,6 +1248,25 @@ static void nms_plan_add(NmsPlan &pl, const NmsPlan &src, int e) {
   nms_plan_add(pl, src.oi[e], src.w[e], src.h[e], L, src.mask_off[e], src.blk_begin[e + 1] - src.blk_begin[e]);
 }
 
+int rank_keys_launch(mods_ctx *ctx, int n_img, const int *key_count) {
+  DetectConst k = {};
+  k.max_cand = ctx->max_cand;                  // (all the rank kernels read of it)
+  // rank array: the raw-hit half of sort_idx's accept list is dead by now; use the dedicated buffer
+  MODS_HIP_CHECK(hipMemsetAsync(ctx->rank_dev, 0, sizeof(int) * (size_t)ctx->max_cand * n_img, ctx->stream));
+  // images of up to RANK_SORT_MAX keys are ranked by one workgroup out of LDS, larger ones by the O(n^2) count.  The sort is the
+  // cheaper one for the GPU (one CU per image for ~0.2 ms: 105 barrier-separated passes) and the slower one for the caller: a call
+  // with a few images - one pair, a view of the ladder - has the GPU to itself, where the count over 4 096 workgroups takes a few
+  // microseconds; both give the same ranks (the keys are unique)
+  const int sort_max = n_img <= RANK_COUNT_MAX_IMG ? 0 : RANK_SORT_MAX;
+  if (sort_max > 0) {
+    static DynLdsOnce once;
+    MODS_HIP_CHECK(dyn_lds_once(once, (const void *)rank_sort_kernel, 160 * 1024, ctx->device));
+    hipLaunchKernelGGL(rank_sort_kernel, dim3(n_img), dim3(1024), RANK_SORT_MAX * 10, ctx->stream, k, ctx->sort_keys, key_count, ctx->rank_dev);
+  }
+  hipLaunchKernelGGL(rank_count_kernel, dim3(64, 32, n_img), dim3(256), 0, ctx->stream, k, ctx->sort_keys, key_count, ctx->rank_dev, sort_max);
+  return MODS_OK;
+}
+
 static int detect_run_stages(mods_ctx *ctx);
 int detect_run(mods_ctx *ctx) {
   const int rc = detect_run_stages(ctx);
@@ -1261,6 +1278,8 @@ static int detect_run_stages(mods_ctx *ctx) {
   const PyramidDev &P = ctx->pyr;
   const mods_hessaff_params &par = ctx->par;
   const int n_img = ctx->last_n_img;
+  // (detect_any has refused the modes and detectors the selection does not cover, or switched it off for the call)
+  const bool spatial = ctx->spatial_mode != 0 && (par.mode == MODS_DET_FIXED_REG_NUMBER || par.mode == MODS_DET_RELATIVE_REG_NUMBER);
   DetectConst k;
   k.border = par.border;
   k.n_scales = par.numberOfScales;
@@ -1389,26 +1408,17 @@ static int detect_run_stages(mods_ctx *ctx) {
   }
   {
     StageScope ts(ctx, MODS_STAGE_SORT);
-    // rank array: the raw-hit half of sort_idx's accept list is dead by now; use the dedicated buffer
-    MODS_HIP_CHECK(hipMemsetAsync(ctx->rank_dev, 0, sizeof(int) * (size_t)ctx->max_cand * n_img, ctx->stream));
-    // images of up to RANK_SORT_MAX keys are ranked by one workgroup out of LDS, larger ones by the O(n^2) count.  The sort is the
-    // cheaper one for the GPU (one CU per image for ~0.2 ms: 105 barrier-separated passes) and the slower one for the caller: a call
-    // with a few images - one pair, a view of the ladder - has the GPU to itself, where the count over 4 096 workgroups takes a few
-    // microseconds; both give the same ranks (the keys are unique)
-    const int sort_max = n_img <= RANK_COUNT_MAX_IMG ? 0 : RANK_SORT_MAX;
-    if (sort_max > 0) {
-      static DynLdsOnce once;
-      MODS_HIP_CHECK(dyn_lds_once(once, (const void *)rank_sort_kernel, 160 * 1024, ctx->device));
-      hipLaunchKernelGGL(rank_sort_kernel, dim3(n_img), dim3(1024), RANK_SORT_MAX * 10, ctx->stream, k, ctx->sort_keys, key_count, ctx->rank_dev);
-    }
-    hipLaunchKernelGGL(rank_count_kernel, dim3(64, 32, n_img), dim3(256), 0, ctx->stream, k, ctx->sort_keys, key_count, ctx->rank_dev, sort_max);
+    { const int rrc = rank_keys_launch(ctx, n_img, key_count); if (rrc) return rrc; }
     hipLaunchKernelGGL(export_kernel, dim3(256, n_img), dim3(256), 0, ctx->stream, k, ctx->cand, ctx->sort_idx, key_count,
                        ctx->rank_dev, ctx->keys_dev);
-    if (par.mode != MODS_DET_FIXED_TH)
+    if (par.mode != MODS_DET_FIXED_TH && !spatial)
       hipLaunchKernelGGL(select_keys_kernel, dim3(n_img), dim3(256), 0, ctx->stream, ctx->max_cand, ctx->keys_dev, key_count, par.mode,
                          par.relativeThreshold, par.threshold, ctx->reg_number_eff, par.relativeRegionsNumber);
     MODS_HIP_CHECK(hipGetLastError());
   }
+  // the count modes' cut by suppression radius (mods_ctx_spatial_selection) in the place of select_keys_kernel's prefix
+  if (spatial)
+    return spatial_select_launch(ctx, n_img, key_count, par.mode, ctx->reg_number_eff, par.relativeRegionsNumber, (float)ctx->spatial_c, nullptr);
   return MODS_OK;
 }
 

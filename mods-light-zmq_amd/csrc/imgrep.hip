@@ -366,6 +366,10 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
       wk->shape_net = c->shape_net; wk->shape_q8 = c->shape_q8; wk->shape_mr = c->shape_mr; wk->shape_ps = c->shape_ps;
       wk->ori_net = c->ori_net; wk->ori_q8 = c->ori_q8; wk->ori_mr = c->ori_mr; wk->ori_ps = c->ori_ps;
       wk->ext_net = c->ext_net; wk->ext_q8 = c->ext_q8; wk->ext_mr = c->ext_mr; wk->ext_ps = c->ext_ps;
+      if (wk->spatial_mode != c->spatial_mode || wk->spatial_c != c->spatial_c) {     // mods_ctx_spatial_selection of the owner
+        wk->spatial_mode = c->spatial_mode; wk->spatial_c = c->spatial_c;
+        mods::dev_state_changed(wk);
+      }
     }
     mods::Buf<mods_region> &A = c->helper_stage[k];
     size_t used = 0;

@@ -472,6 +472,15 @@ int mser_detect(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int 
 int detect_any(mods_ctx *c, const float *img_dev, int n_img, int w, int h, int stride, const mods_hessaff_params *par, double tilt, double zoom,
                const DetGateFrame *frame) {
   int rc;
+  if (c->spatial_mode == 1) {      // mods_ctx_spatial_selection: the cut of the two count modes of the scale-space detectors only
+    if (par->detectorType == MODS_DET_MSER) { set_error("spatial_selection: detectorType = MSER is not covered (MSER exports its own list); switch the selection off for this call"); return MODS_E_ARG; }
+    if (par->mode != MODS_DET_FIXED_REG_NUMBER && par->mode != MODS_DET_RELATIVE_REG_NUMBER) {
+      static const char *const names[] = {"FixedTh", "RelativeTh", "FixedRegNumber", "RelativeRegNumber", "NotLessThanRegions"};
+      set_error("spatial_selection: mode = %s cuts by a threshold, the selection needs a count (mode = FixedRegNumber or RelativeRegNumber)",
+                par->mode >= 0 && par->mode <= MODS_DET_NOT_LESS_THAN_REGIONS ? names[par->mode] : "?");
+      return MODS_E_ARG;
+    }
+  }
   if ((rc = detection_mask_bind(c, n_img, w, h, frame))) return rc;
   if (par->detectorType == MODS_DET_MSER) return mser_detect(c, img_dev, n_img, w, h, stride, par, tilt, zoom);
   if ((rc = pyramid_configure(c, w, h, n_img, par))) return rc;

@@ -240,6 +240,19 @@ int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCo
   return MODS_OK;
 }
 
+// the spatial selection of every detection of the pipeline (mods_ctx_spatial_selection on the workers' contexts)
+int mods_pipeline_spatial_selection(mods_pipeline *p, int mode, double robustness) {
+  if (mode < 0 || mode > 2 || !(robustness >= 0.0 && robustness <= 1.0)) {
+    set_error("pipeline: spatial_selection mode %d (0, 1 or 2), robustness %g (0 <= robustness <= 1)", mode, robustness);
+    return MODS_E_ARG;
+  }
+  if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: spatial_selection after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) { const int rc = mods_ctx_spatial_selection(c, mode, robustness); if (rc) return rc; }
+  return MODS_OK;
+}
+
 // the local affine consistency filter of every list of the pipeline (mods_ctx_local_affine on the workers' contexts)
 int mods_pipeline_local_affine(mods_pipeline *p, const mods_local_affine_params *par) {
   LaConst k;
