@@ -217,6 +217,35 @@ int mods_gauss_blur(mods_ctx *ctx, const float *src, int w, int h, float sigma, 
 int mods_hessian_response(mods_ctx *ctx, const float *src, int w, int h, float norm, float *dst);
 int mods_resize_half(mods_ctx *ctx, const float *src, int w, int h, float *dst, int *dw, int *dh);
 
+/* ---- a doubled first octave (PyramidParams::upscaleInputImage, structures.hpp:116-117; pyramid.cpp:504-509) -----------------
+ * Lowe's "octave -1" for HessianAffine, DoG and HarrisAffine: the scale space starts at the doubled image, at pixel distance 0.5,
+ * and the input is assumed to carry a blur of 1.0 instead of 0.5.  The reference's doubleImage (helpers.cpp:733-765) cannot be a
+ * contract - it indexes with the byte step as an element offset, skips no column at a row's end, leaves the last row and column
+ * unwritten, and no .ini key ever sets the switch - so the contract is this library's own (that function's evident intent),
+ * restated in tests/upscale_ref.py and held to the bit; parity with the reference is unpinned.
+ *
+ * double_image(I), I of h x w fp32, is D of 2h x 2w.  With r' = min(r + 1, h - 1), c' = min(c + 1, w - 1), a = I[r, c],
+ * b = I[r, c'], c_ = I[r', c], d = I[r', c'], every operation in fp32 with one rounding and in this order:
+ *     D[2r,     2c    ] = a                      D[2r,     2c + 1] = 0.5f * (a + b)
+ *     D[2r + 1, 2c    ] = 0.5f * (a + c_)        D[2r + 1, 2c + 1] = 0.25f * (((a + b) + c_) + d)
+ *
+ * With the switch on, octave 0 is D (2w x 2h, pixelDistance 0.5; mods_pyramid_dims(ctx, 0) reports it) and the later octaves
+ * follow from it by the usual rule, so octave 1 has the input's size but is decimated from level numberOfScales of octave 0.  The
+ * initial blur runs only if initialSigma > 1.0, with sigma = sqrtf(initialSigma^2 - 1.0f); otherwise level 0 is D itself.  Level
+ * sigmas and everything behind the planes are unchanged: keys and regions are in image coordinates, mods_affkey.octave counts
+ * from the doubled octave, sampleFromImage still samples the input image at pixel distance 1.  A call whose doubled image would
+ * have 2^25 pixels or more (4 w h >= 2^25) is MODS_E_ARG, before anything is allocated.  MSER ignores the switch; mods_multi has
+ * none.  A context that never turns it on allocates nothing for it.
+ *
+ * mode: 0 off (default), 1 on, 2 on with the first level made in two launches (double, then blur: what mode 1's single launch,
+ * which doubles in the blur's window loader, is tested against; the planes of the two are equal to the bit).  Changing the mode
+ * is a change of device state: no recorded launch chain (mods_ctx_graphs) is replayed across it.  The view workers of a step
+ * loop take their owner's mode.  mods_pipeline_upscale_input: every worker's context, before the first submit (later: MODS_E_ARG).
+ * mods_upscale2x: double_image of one host image, dst holds 2w x 2h floats. */
+int mods_ctx_upscale_input(mods_ctx *ctx, int mode);
+int mods_ctx_upscale_input_get(const mods_ctx *ctx, int *mode);
+int mods_upscale2x(mods_ctx *ctx, const float *src, int w, int h, float *dst);
+
 /* ---- B3: orientation + description ---------------------------------------------------------
  * [DominantOrientation] and [SIFTDescriptor] keys (io_mods.cpp:731-740, 423-436). */
 typedef struct mods_describe_params {
@@ -1323,6 +1352,7 @@ int mods_test_sift_pooled(mods_ctx *ctx, const float *patches, int K, int ps, in
 int mods_ctx_spatial_selection(mods_ctx *ctx, int mode, double robustness);
 int mods_ctx_spatial_selection_get(const mods_ctx *ctx, int *mode, double *robustness);
 int mods_pipeline_spatial_selection(mods_pipeline *p, int mode, double robustness);
+int mods_pipeline_upscale_input(mods_pipeline *p, int mode);   /* mods_ctx_upscale_input of every worker, before the first submit */
 int mods_test_spatial_select(mods_ctx *ctx, const mods_affkey *keys_host, int n_img, const int *n, int max_n, const int *keep,
                              double robustness, int *out_idx, int *n_out);
 

@@ -451,6 +451,13 @@ class Context:
         _check(lib().mods_resize_half(self.h, _fp(a), a.shape[1], a.shape[0], _fp(out), C.byref(dw), C.byref(dh)))
         return out[:dw.value * dh.value].reshape(dh.value, dw.value).copy()
 
+    def upscale2x(self, img):
+        """mods_upscale2x: double_image of the contract in mods_hip.h (restated in tests/upscale_ref.py), h x w -> 2h x 2w"""
+        a = np.ascontiguousarray(img, np.float32)
+        out = np.empty((2 * a.shape[0], 2 * a.shape[1]), np.float32)
+        _check(lib().mods_upscale2x(self.h, _fp(a), a.shape[1], a.shape[0], _fp(out)))
+        return out
+
     # ---- detector
     def detect_hessian_affine(self, img, params=None, max_out=1 << 18):
         params = params or HessAffParams.default()
@@ -611,6 +618,16 @@ class Context:
         """mods_ctx_spatial_selection (ANMS): the count modes keep the keys with the largest suppression radius instead of the
         strongest ones; mode 0 off, 1 on, 2 on for the calls it covers and off for the others"""
         _check(lib().mods_ctx_spatial_selection(self.h, int(mode), C.c_double(robustness)))
+
+    def upscale_input(self, mode=1):
+        """mods_ctx_upscale_input: the scale-space detectors start at the doubled image (pixel distance 0.5, assumed blur 1.0);
+        mode 0 off, 1 on, 2 on with the first level made in two launches (what mode 1 is tested against)"""
+        _check(lib().mods_ctx_upscale_input(self.h, int(mode)))
+
+    def upscale_input_get(self):
+        m = C.c_int()
+        _check(lib().mods_ctx_upscale_input_get(self.h, C.byref(m)))
+        return m.value
 
     def spatial_selection_get(self):
         """(mode, robustness) of the context"""
@@ -1875,6 +1892,10 @@ class Pipeline:
     def spatial_selection(self, mode=1, robustness=0.9):
         """mods_pipeline_spatial_selection: Context.spatial_selection on every GPU worker's context, before the first submit"""
         _check(lib().mods_pipeline_spatial_selection(self.h, int(mode), C.c_double(robustness)))
+
+    def upscale_input(self, mode=1):
+        """mods_pipeline_upscale_input: Context.upscale_input on every GPU worker's context, before the first submit"""
+        _check(lib().mods_pipeline_upscale_input(self.h, int(mode)))
 
     def set_domain_pooling(self, num_scales, start_coef=0.5, end_coef=1.5):
         """mods_pipeline_domain_pooling: Context.set_domain_pooling on every GPU worker's context, before the first submit"""

@@ -68,6 +68,9 @@ struct Config {
   // of the scale-space detectors keep the keys with the largest suppression radius (mods_ctx_spatial_selection, mode 2)
   int spatial = 0;
   double spatial_c = 0.9;
+  // [HessianAffine] upscaleInputImage (PyramidParams::upscaleInputImage, structures.hpp:116-117; no .ini key of the reference sets it):
+  // the scale-space detectors of the run start at the doubled image (mods_ctx_upscale_input)
+  int upscale = 0;
   // [SIFTDescriptor] domainSizePooling (the gate; no counterpart in the reference) with the reference's numScales / startCoef /
   // endCoef (io_mods.cpp:431-433, parsed there and never used): mods_ctx_domain_pooling
   int dsp = 0, dsp_scales = 3;
@@ -272,6 +275,12 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->use_mask_files = (int)ini.GetInteger("DetectionMask", "useMaskFiles", 0);
   cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
   if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
+  cfg->upscale = (int)ini.GetInteger("HessianAffine", "upscaleInputImage", 0);
+  if (cfg->upscale != 0 && cfg->upscale != 1) { std::cerr << "[HessianAffine] upscaleInputImage must be 0 or 1" << std::endl; return 1; }
+  for (const char *sec : {"DoG", "HarrisAffine"})     // one switch per context: [HessianAffine]'s value holds for the three detectors
+    if (ini.Has(sec, "upscaleInputImage") && (int)ini.GetInteger(sec, "upscaleInputImage", 0) != cfg->upscale)
+      std::cerr << "Note: [" << sec << "] upscaleInputImage differs from [HessianAffine]'s, which applies to every scale-space detector of the run ("
+                << cfg->upscale << ")" << std::endl;
   cfg->spatial = (int)ini.GetInteger("SpatialSelection", "doSpatialSelection", 0);
   if (cfg->spatial != 0 && cfg->spatial != 1) { std::cerr << "[SpatialSelection] doSpatialSelection must be 0 or 1" << std::endl; return 1; }
   if (cfg->spatial && ini.Has("SpatialSelection", "robustness")) {   // (with the gate 0 the key is ignored)
@@ -832,6 +841,13 @@ int main(int argc, char **argv) {
       // mode 2: the calls the selection does not cover run without it
       if (mods_ctx_spatial_selection(ctx, 2, cfg.spatial_c)) return fail("[SpatialSelection]");
       if (cfg.verbose) std::cerr << "Spatial selection (ANMS): robustness " << cfg.spatial_c << std::endl;
+    }
+  }
+  if (cfg.upscale) {
+    if (pre_extracted || getenv("MODS_DEVICES")) std::cerr << "Note: [HessianAffine] upscaleInputImage is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
+    else {
+      if (mods_ctx_upscale_input(ctx, 1)) return fail("upscaleInputImage");
+      if (cfg.verbose) std::cerr << "Doubled first octave (upscaleInputImage): HessianAffine, DoG and HarrisAffine start at twice the image's size" << std::endl;
     }
   }
   if (cfg.dsp && cfg.verbose) std::cerr << "Domain-size pooling: " << cfg.dsp_scales << " domains, " << cfg.dsp_start << " .. " << cfg.dsp_end << " x mrSize" << std::endl;

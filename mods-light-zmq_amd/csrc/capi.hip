@@ -1276,6 +1276,37 @@ int mods_gauss_blur(mods_ctx *c, const float *src, int w, int h, float sigma, fl
   return MODS_OK;
 }
 
+int mods_upscale2x(mods_ctx *c, const float *src, int w, int h, float *dst) {
+  if (!c || !src || !dst || w <= 0 || h <= 0) { set_error("upscale2x: bad argument"); return MODS_E_ARG; }
+  if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("image larger than the context"); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  const size_t n = (size_t)w * h;
+  MODS_HIP_CHECK(mods::reserve_pool(c, c->up_tmp, 4 * n, 4 * n));
+  MODS_HIP_CHECK(hipMemcpyAsync(c->input_dev, src, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+  int rc = launch_upscale2x(c, c->input_dev, c->up_tmp, w, h, 1);
+  if (rc) return rc;
+  MODS_HIP_CHECK(hipMemcpyAsync(dst, c->up_tmp, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, c->stream));
+  MODS_HIP_CHECK(mods::stream_wait(c->stream));
+  return MODS_OK;
+}
+
+// A doubled first octave for the scale-space detectors of this context (pyramid.hip: pyramid_configure, pyramid_build_levels)
+int mods_ctx_upscale_input(mods_ctx *c, int mode) {
+  if (!c) { set_error("upscale_input: null context"); return MODS_E_ARG; }
+  if (mode < 0 || mode > 2) { set_error("upscale_input: mode %d (0 off, 1 on, 2 on with the unfused first level)", mode); return MODS_E_ARG; }
+  if (c->upscale_mode != mode) {
+    c->upscale_mode = mode;
+    mods::dev_state_changed(c);              // (recorded launch chains are not replayed across the change)
+  }
+  return MODS_OK;
+}
+
+int mods_ctx_upscale_input_get(const mods_ctx *c, int *mode) {
+  if (!c || !mode) { set_error("upscale_input_get: null argument"); return MODS_E_ARG; }
+  *mode = c->upscale_mode;
+  return MODS_OK;
+}
+
 int mods_hessian_response(mods_ctx *c, const float *src, int w, int h, float norm, float *dst) {
   if ((size_t)w * h > (size_t)c->max_w * c->max_h) { set_error("image larger than the context"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipSetDevice(c->device));

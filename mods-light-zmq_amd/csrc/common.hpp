@@ -242,6 +242,10 @@ struct mods_ctx {
   // call's mode and detector allow it; its scratch is sort_keys and rank_dev, dead after the export
   int spatial_mode = 0;
   double spatial_c = 0.9;
+  // a doubled first octave for the scale-space detectors (mods_ctx_upscale_input; pyramid.hip): 0 off, 1 on, 2 on with the first
+  // level unfused (the doubled batch goes through up_tmp: reserved by the first call that needs it, also mods_upscale2x's output)
+  int upscale_mode = 0;
+  mods::Buf<float> up_tmp;
   int last_w = 0, last_h = 0, last_n_img = 0;
   const float *last_img_dev = nullptr; int last_stride = 0;   // the batch the pyramid was built from (sampleFromImage)
   // orientation + description
@@ -430,6 +434,7 @@ int pyramid_join_side(mods_ctx *ctx);   // joins a forked pyramid's side stream 
 int launch_gauss_blur(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img, float sigma);
 int launch_hessian_response(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img, float norm);
 int launch_resize_half(mods_ctx *ctx, const float *src, float *dst, int w, int h, int dw, int dh, int n_img);
+int launch_upscale2x(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img);   // double_image: [n_img][h][w] -> [n_img][2h][2w]
 void resize_half_dims(int w, int h, int *dw, int *dh);
 int gauss_ksize(float sigma);
 void gauss_kernel_host(int n, double sigma, float *out);

@@ -370,6 +370,10 @@ static int run_view_jobs(mods_ctx *c, const float *img1_dev, int w1, int h1, con
         wk->spatial_mode = c->spatial_mode; wk->spatial_c = c->spatial_c;
         mods::dev_state_changed(wk);
       }
+      if (wk->upscale_mode != c->upscale_mode) {                                       // mods_ctx_upscale_input of the owner
+        wk->upscale_mode = c->upscale_mode;
+        mods::dev_state_changed(wk);
+      }
     }
     mods::Buf<mods_region> &A = c->helper_stage[k];
     size_t used = 0;

@@ -240,6 +240,16 @@ int mods_pipeline_domain_pooling(mods_pipeline *p, int numScales, double startCo
   return MODS_OK;
 }
 
+// a doubled first octave for every scale-space detection of the pipeline (mods_ctx_upscale_input on the workers' contexts)
+int mods_pipeline_upscale_input(mods_pipeline *p, int mode) {
+  if (!p) { set_error("pipeline: null handle"); return MODS_E_ARG; }
+  if (mode < 0 || mode > 2) { set_error("pipeline: upscale_input mode %d (0, 1 or 2)", mode); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: upscale_input after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) { const int rc = mods_ctx_upscale_input(c, mode); if (rc) return rc; }
+  return MODS_OK;
+}
+
 // the spatial selection of every detection of the pipeline (mods_ctx_spatial_selection on the workers' contexts)
 int mods_pipeline_spatial_selection(mods_pipeline *p, int mode, double robustness) {
   if (mode < 0 || mode > 2 || !(robustness >= 0.0 && robustness <= 1.0)) {

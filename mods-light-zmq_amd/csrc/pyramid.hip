@@ -6,6 +6,8 @@
 //   HessianResponse                      detectors/affinedetectors/pyramid.cpp:196-254
 //   octave loop, sigma schedule          pyramid.cpp:428-529
 //   cv::resize(.., 0.5, 0.5, LINEAR)     pyramid.cpp:476
+//   upscaleInputImage / doubleImage      pyramid.cpp:504-509, helpers.cpp:733-765 (the switch is the reference's, double_image a
+//                                        contract of this library: include/mods_hip.h, mods_ctx_upscale_input)
 // Arithmetic contract (shared with the CPU oracle): fp32, built with -ffp-contract=off so that every fusion is
 // written out.  cv::GaussianBlur as an FMA build of OpenCV evaluates it (the variant that reproduces the reference's
 // README counts exactly, tools/readme_count_hunt.py): row pass s = k[0]*S[0]; s = fma(k[j], S[j], s) left to right
@@ -217,7 +219,11 @@ __device__ __forceinline__ void store_f4_at(float *base, unsigned byte_off, floa
 #ifndef BLUR_COLJ_MIN_TH
 #define BLUR_COLJ_MIN_TH 32   // the outward column pass pays with 4 outputs per thread; the 16-row tiles (2 outputs) read their 2R + 2 rows up front
 #endif
-template <int R, int FB_TH, int OV, bool RESP>
+// UP = true is the first level of a doubled first octave (mods_ctx_upscale_input): the w x h plane that is blurred is double_image
+// (the contract in include/mods_hip.h, upscale2x_kernel below) of the (w / 2) x (h / 2) image at `src`, and only load_window knows:
+// it reads the one or two source rows behind a doubled row and expands them in registers to the window the row pass takes, so the
+// doubled image never goes to HBM.  Everything behind the window is the code of UP = false.
+template <int R, int FB_TH, int OV, bool RESP, bool UP = false>
 __global__ __launch_bounds__(256, (R <= 4 ? BLUR_OCC_LO : BLUR_OCC_HI)) void gauss_blur_fast_kernel(const float *__restrict__ src, float *__restrict__ dst, int w, int h,
                                                               BlurTaps taps, float *__restrict__ resp, float norm2) {
   constexpr int N = 2 * R + 1;
@@ -244,7 +250,8 @@ __global__ __launch_bounds__(256, (R <= 4 ? BLUR_OCC_LO : BLUR_OCC_HI)) void gau
   const int img = wg / (tiles_x * tiles_y);
   const int trem = wg - img * tiles_x * tiles_y;
   const int tyi = trem / tiles_x, txi = trem - tyi * tiles_x;
-  src += plane * img;
+  if constexpr (UP) src += (size_t)(w >> 1) * (h >> 1) * img;
+  else src += plane * img;
   dst += plane * img;
   const int x0 = txi * SX, y0 = tyi * SY;
   // LDS column swizzle (16-byte units of a strip row).  At OV = 2 a thread writes the units 2 rc and 2 rc + 1: the eight lanes that
@@ -264,6 +271,60 @@ __global__ __launch_bounds__(256, (R <= 4 ? BLUR_OCC_LO : BLUR_OCC_HI)) void gau
   auto load_window = [&](int ly, float *win) {
     int gy = y0 - R + ly;
     gy = gy < 0 ? 0 : (gy > h - 1 ? h - 1 : gy);
+    if constexpr (UP) {
+      // Doubled row gy = 2 r (+ 1) comes from the source rows r and min(r + 1, hs - 1); the window's 4 NV doubled columns start at
+      // an even source column c0 (tile origins and window offsets are multiples of 4) and take the 2 NV + 1 source columns from
+      // c0 on, clamped into the row.  Window element e = 2 i (+ 1): an even doubled column is a (rows averaged on an odd row), an
+      // odd one the contract's 0.5f * (a + b) or 0.25f * (((a + b) + c_) + d).  BORDER_REPLICATE of the doubled plane: an element
+      // left of it is its column 0 (the even form of source column 0, where the clamp put every such i), one right of it its last,
+      // odd, column (the odd form of source column ws - 1 with b = a, d = c_: the clamp again).
+      const int ws = w >> 1, hs = h >> 1;
+      const int r0 = gy >> 1, r1 = r0 + 1 < hs ? r0 + 1 : hs - 1;
+      const bool odd = gy & 1;
+      const int gx0 = xg - 4 * R4, c0 = gx0 >> 1;           // (gx0 is a multiple of 4, negative ones too: the shift is exact)
+      constexpr int NS = 2 * NV + 1;
+      const unsigned rowa = (unsigned)r0 * (unsigned)ws * 4u, rowc = (unsigned)r1 * (unsigned)ws * 4u;
+      float sa[NS], sb[NS];
+      if (fast_x) {      // doubled columns gx0 .. gx0 + 4 NV - 1 inside the row: source columns c0 .. c0 + 2 NV - 1 are, the last one may not be
+        const int cl = c0 + 2 * NV < ws ? c0 + 2 * NV : ws - 1;
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+          const float2 q = *(const float2 *)(srcb + (rowa + (unsigned)(c0 + 2 * v) * 4u));
+          sa[2 * v] = q.x; sa[2 * v + 1] = q.y;
+        }
+        sa[2 * NV] = *(const float *)(srcb + (rowa + (unsigned)cl * 4u));
+        if (odd) {
+#pragma unroll
+          for (int v = 0; v < NV; v++) {
+            const float2 q = *(const float2 *)(srcb + (rowc + (unsigned)(c0 + 2 * v) * 4u));
+            sb[2 * v] = q.x; sb[2 * v + 1] = q.y;
+          }
+          sb[2 * NV] = *(const float *)(srcb + (rowc + (unsigned)cl * 4u));
+        } else {
+#pragma unroll
+          for (int i = 0; i < NS; i++) sb[i] = sa[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NS; i++) {
+          int cs = c0 + i;
+          cs = cs < 0 ? 0 : (cs > ws - 1 ? ws - 1 : cs);
+          sa[i] = *(const float *)(srcb + (rowa + (unsigned)cs * 4u));
+          sb[i] = odd ? *(const float *)(srcb + (rowc + (unsigned)cs * 4u)) : sa[i];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 4 * NV; e++) {
+        const int i = e >> 1;
+        const float a = sa[i], b = sa[i + 1], c_ = sb[i], d = sb[i + 1];
+        const float ev = odd ? 0.5f * (a + c_) : a;
+        const float od = odd ? 0.25f * (((a + b) + c_) + d) : 0.5f * (a + b);
+        const int gx = gx0 + e;
+        const bool odd_col = fast_x ? (e & 1) != 0 : (gx >= w || (gx >= 0 && (e & 1)));
+        win[e] = odd_col ? od : ev;
+      }
+      return;
+    }
     const unsigned rowb = (unsigned)gy * (unsigned)w * 4u;
     if (fast_x) {
       const unsigned b0 = rowb + (unsigned)(xg - 4 * R4) * 4u;
@@ -584,6 +645,22 @@ __global__ __launch_bounds__(256) void resize_half_kernel(const float *__restric
   dst[(size_t)dy * dw + dx] = decimated_at(src, w, h, dx, dy);
 }
 
+// double_image (the contract in include/mods_hip.h; the evident intent of the reference's doubleImage, helpers.cpp:733-765, whose
+// indexing cannot be the contract: DESIGN section 8): a thread makes the 2 x 2 doubled pixels of one source pixel, with
+// r' = min(r + 1, h - 1), c' = min(c + 1, w - 1).  [n_img][h][w] -> [n_img][2h][2w]; grid = (ceil(w/64), ceil(h/4), n_img), block = 256.
+__global__ __launch_bounds__(256) void upscale2x_kernel(const float *__restrict__ src, float *__restrict__ dst, int w, int h) {
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int r = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (c >= w || r >= h) return;
+  src += (size_t)w * h * blockIdx.z;
+  dst += (size_t)4 * w * h * blockIdx.z;
+  const int r1 = r + 1 < h ? r + 1 : h - 1, c1 = c + 1 < w ? c + 1 : w - 1;
+  const float a = src[(size_t)r * w + c], b = src[(size_t)r * w + c1], c_ = src[(size_t)r1 * w + c], d = src[(size_t)r1 * w + c1];
+  float *o = dst + (size_t)(2 * r) * (2 * w) + 2 * c;      // (an even element offset in a plane of even size: 8-byte aligned)
+  *(float2 *)o = make_float2(a, 0.5f * (a + b));
+  *(float2 *)(o + 2 * w) = make_float2(0.5f * (a + c_), 0.25f * (((a + b) + c_) + d));
+}
+
 // The same decimation, and the Hessian response of the decimated plane (the first level of the next octave) from the block's
 // tile in LDS: the 64 x 4 outputs of a block and the ring of decimated values around them (recomputed, 396 instead of 256
 // values per block).  One launch instead of two per octave - the response launches of the small octaves cost 7-8 us each for
@@ -865,7 +942,8 @@ static int upload_taps(mods_ctx *ctx, int slot, float sigma, int *n_out) {
   return MODS_OK;
 }
 
-template <int R>
+// UP: `src` is the (w / 2) x (h / 2) batch whose doubled planes are blurred (the fused first level; with the response only)
+template <int R, bool UP = false>
 static void launch_fast_blur(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img, const BlurTaps &taps, float *resp,
                              float norm2) {
 #ifndef BLUR_OV_BIG
@@ -879,8 +957,8 @@ static void launch_fast_blur(mods_ctx *ctx, const float *src, float *dst, int w,
     const size_t lds = sizeof(float) * (size_t)(BLUR_TH_BIG + 2 * R) * FB_TW;
     if (resp) {
       const int tilesB = blur_resp_tiles(w, FB_TW - 4, 4) * blur_resp_tiles(h, BLUR_TH_BIG - 2, 2) * n_img;
-      hipLaunchKernelGGL((gauss_blur_fast_kernel<R, BLUR_TH_BIG, BLUR_OV_BIG, true>), dim3(tilesB), dim3(256), lds, ctx->stream, src, dst, w, h, taps, resp, norm2);
-    } else {
+      hipLaunchKernelGGL((gauss_blur_fast_kernel<R, BLUR_TH_BIG, BLUR_OV_BIG, true, UP>), dim3(tilesB), dim3(256), lds, ctx->stream, src, dst, w, h, taps, resp, norm2);
+    } else if constexpr (!UP) {
       const int tilesB = ((w + FB_TW - 1) / FB_TW) * ((h + BLUR_TH_BIG - 1) / BLUR_TH_BIG) * n_img;
       hipLaunchKernelGGL((gauss_blur_fast_kernel<R, BLUR_TH_BIG, BLUR_OV_BIG, false>), dim3(tilesB), dim3(256), lds, ctx->stream, src, dst, w, h, taps, nullptr, 0.f);
     }
@@ -888,8 +966,8 @@ static void launch_fast_blur(mods_ctx *ctx, const float *src, float *dst, int w,
     const size_t lds = sizeof(float) * (size_t)(16 + 2 * R) * FB_TW;
     if (resp) {
       const int tiles16 = blur_resp_tiles(w, FB_TW - 4, 4) * blur_resp_tiles(h, 16 - 2, 2) * n_img;
-      hipLaunchKernelGGL((gauss_blur_fast_kernel<R, 16, 1, true>), dim3(tiles16), dim3(256), lds, ctx->stream, src, dst, w, h, taps, resp, norm2);
-    } else {
+      hipLaunchKernelGGL((gauss_blur_fast_kernel<R, 16, 1, true, UP>), dim3(tiles16), dim3(256), lds, ctx->stream, src, dst, w, h, taps, resp, norm2);
+    } else if constexpr (!UP) {
       const int tiles16 = ((w + FB_TW - 1) / FB_TW) * ((h + 15) / 16) * n_img;
       hipLaunchKernelGGL((gauss_blur_fast_kernel<R, 16, 1, false>), dim3(tiles16), dim3(256), lds, ctx->stream, src, dst, w, h, taps, nullptr, 0.f);
     }
@@ -898,10 +976,18 @@ static void launch_fast_blur(mods_ctx *ctx, const float *src, float *dst, int w,
 
 // blur of one level; resp != nullptr: the Hessian response of the blurred plane (norm = sigma^2 of the level) comes out of the
 // same launch (register-blocked kernel only; the generic kernel falls back to a separate response launch)
-static int blur_with_slot(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img, int slot, int n, float *resp = nullptr,
-                          float norm = 0.f) {
+// what the register-blocked kernel covers (16-byte row loads; 32-bit byte offsets inside a plane)
+static bool fast_blur_covers(const mods_ctx *ctx, int w, int h, int slot, int n) {
   const int r = n / 2;
-  if (r >= 1 && r <= 8 && ctx->taps_host_n[slot] == n && w >= 4 && (size_t)w * h < ((size_t)1 << 29)) {   // (16-byte row loads; 32-bit byte offsets inside a plane)
+  return r >= 1 && r <= 8 && ctx->taps_host_n[slot] == n && w >= 4 && (size_t)w * h < ((size_t)1 << 29);
+}
+// up: `src` holds the (w / 2) x (h / 2) images whose doubled planes are blurred (the fused first level of a doubled first octave:
+// with resp, and only where fast_blur_covers - the caller asks)
+static int blur_with_slot(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img, int slot, int n, float *resp = nullptr,
+                          float norm = 0.f, bool up = false) {
+  const int r = n / 2;
+  if (up && !(resp && fast_blur_covers(ctx, w, h, slot, n))) { set_error("fused doubled first level outside the fast blur's cover"); return MODS_E_ARG; }
+  if (fast_blur_covers(ctx, w, h, slot, n)) {
     BlurTaps taps;
     for (int i = 0; i < 17; i++) taps.t[i] = i < n ? ctx->taps_host[slot][i] : 0.f;
     // (the two tile instantiations are timed separately: launches of the small planes are launch-size bound)
@@ -909,6 +995,18 @@ static int blur_with_slot(mods_ctx *ctx, const float *src, float *dst, int w, in
     // algorithmic bytes of the launch by SURVEY 8d's unfused model: 8 B/px for the blur (+ 8 B/px for the response)
     StageScope ts(ctx, big_tiles ? MODS_STAGE_BLUR : MODS_STAGE_BLUR_SMALL, (resp ? 16.0 : 8.0) * w * h * n_img);
     const float norm2 = norm * norm;
+    if (up) {
+      switch (r) {
+        case 1: launch_fast_blur<1, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        case 2: launch_fast_blur<2, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        case 3: launch_fast_blur<3, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        case 4: launch_fast_blur<4, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        case 5: launch_fast_blur<5, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        case 6: launch_fast_blur<6, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        case 7: launch_fast_blur<7, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+        default: launch_fast_blur<8, true>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
+      }
+    } else
     switch (r) {
       case 1: launch_fast_blur<1>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
       case 2: launch_fast_blur<2>(ctx, src, dst, w, h, n_img, taps, resp, norm2); break;
@@ -1004,6 +1102,15 @@ static int launch_resize_half_resp(mods_ctx *ctx, const float *src, float *dst, 
   return MODS_OK;
 }
 
+// double_image of a batch: [n_img][h][w] -> [n_img][2h][2w]
+int launch_upscale2x(mods_ctx *ctx, const float *src, float *dst, int w, int h, int n_img) {
+  dim3 grid((w + 63) / 64, (h + 3) / 4, n_img);
+  StageScope ts(ctx, MODS_STAGE_RESIZE, 20.0 * w * h * n_img);
+  hipLaunchKernelGGL(upscale2x_kernel, grid, dim3(256), 0, ctx->stream, src, dst, w, h);
+  MODS_HIP_CHECK(hipGetLastError());
+  return MODS_OK;
+}
+
 int launch_resize_half(mods_ctx *ctx, const float *src, float *dst, int w, int h, int dw, int dh, int n_img) {
   dim3 grid((dw + 63) / 64, (dh + 3) / 4, n_img);
   StageScope ts(ctx, MODS_STAGE_RESIZE, 5.0 * w * h * n_img);
@@ -1015,6 +1122,16 @@ int launch_resize_half(mods_ctx *ctx, const float *src, float *dst, int w, int h
 // ---------------------------------------------------------------------------------------
 // scale-space layout + build
 // ---------------------------------------------------------------------------------------
+// The first level of a doubled first octave (mods_ctx_upscale_input) with an initial blur comes from one launch that doubles in
+// its window loader (gauss_blur_fast_kernel, UP): the Hessian detector in mode 1, at the radii that kernel covers (fast_blur_covers;
+// the slot holds the taps once they are uploaded).  Otherwise upscale2x_kernel writes the doubled batch to up_tmp first (mode 2,
+// DoG / Harris, a wider blur such as initialSigma = 3.2).
+static bool upscale_first_level_fused(const mods_ctx *ctx, const mods_hessaff_params &par, int w, int h) {
+  if (ctx->upscale_mode != 1 || par.detectorType != MODS_DET_HESSIAN || !(par.initialSigma > 1.0f)) return false;
+  const int r = gauss_ksize(sqrtf(par.initialSigma * par.initialSigma - 1.0f)) / 2;
+  return r >= 1 && r <= 8 && 2 * w >= 4 && 4 * (size_t)w * h < ((size_t)1 << 29);
+}
+
 // Computes the octave ladder (pyramid.cpp:520-528) and carves the planes out of the pools.
 int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff_params *par) {
   if (w <= 0 || h <= 0 || n_img <= 0 || n_img > ctx->batch) { set_error("bad image batch %dx%d x%d (ctx batch %d)", w, h, n_img, ctx->batch); return MODS_E_ARG; }
@@ -1027,12 +1144,16 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
   // Response() has no iiDoG form for Hessian / Harris: those branches are commented out in the reference and run off the end
   // of a non-void function (pyramid.cpp:130-136, 148-156)
   if (par->iiDoGMode && par->detectorType != MODS_DET_DOG) { set_error("iiDoGMode exists for the DoG detector only"); return MODS_E_ARG; }
+  // a doubled first octave (mods_ctx_upscale_input; pyramid.cpp:504-509): the ladder starts at double_image of the input, at
+  // pixel distance 0.5.  Its planes must fit the order key (detect.hip: ORDER_POS_BITS); refused here, before any pool grows
+  const bool up = ctx->upscale_mode != 0;
+  if (up && 4 * (size_t)w * h >= ((size_t)1 << 25)) { set_error("upscale_input: the doubled %dx%d image has 2^25 pixels or more", w, h); return MODS_E_ARG; }
   PyramidDev &P = ctx->pyr;
   P.n_levels = n_levels;
   P.n_oct = 0;
   const int minSize = 2 * par->border + 2;
-  int cw = w, ch = h;
-  float pd = 1.0f;
+  int cw = up ? 2 * w : w, ch = up ? 2 * h : h;
+  float pd = up ? 0.5f : 1.0f;
   size_t plane_elems = 0, omap_elems = 0, mask_words = 0;
   const float sigmaStep = det_pow2f(1.0f / (float)par->numberOfScales);
   while (ch > minSize && cw > minSize) {
@@ -1074,7 +1195,7 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
   }
   if (par->detectorType != MODS_DET_HESSIAN) {
     MODS_HIP_CHECK(ctx->alt_taps_dev.reserve((size_t)kMaxLevels * kAltTapStride));
-    const size_t need = 4 * (size_t)w * h * n_img;
+    const size_t need = (up ? 16 : 4) * (size_t)w * h * n_img;   // 4 planes of the first octave's size
     MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->alt_planes, need, need));
     for (int l = 0; l < n_levels; l++) {
       const float sigma = alt_response_sigma(*par, P.oct[0].sigma[l]);
@@ -1088,6 +1209,12 @@ int pyramid_configure(mods_ctx *ctx, int w, int h, int n_img, const mods_hessaff
       MODS_HIP_CHECK(mods::copy_wait(ctx->stream, ctx->alt_taps_dev + (size_t)l * kAltTapStride, taps.data(), sizeof(float) * n, hipMemcpyHostToDevice));
       ctx->alt_ntap[l] = n; ctx->alt_sigma[l] = sigma;
     }
+  }
+  // the doubled images of the batch, where the first level does not make them on the fly (pyramid_build_levels: an initial blur
+  // that is not fused)
+  if (up && par->initialSigma > 1.0f && !upscale_first_level_fused(ctx, *par, w, h)) {
+    const size_t need = 4 * (size_t)w * h * n_img;
+    MODS_HIP_CHECK(mods::reserve_pool(ctx, ctx->up_tmp, need, need));
   }
   ctx->par = *par;
   ctx->reg_number_eff = par->regionsNumber;   // identity view; mods_detect_describe_view_dev rescales it
@@ -1144,7 +1271,8 @@ static int pyramid_build_levels(mods_ctx *ctx, const float *img_dev, int stride)
   // tap tables: slot 0 = initial blur, slot l = increment to level l
   int ntap[kMaxLevels + 1];
   const float sigmaStep = det_pow2f(1.0f / (float)S);
-  const float curSigma0 = 0.5f;
+  const bool up = ctx->upscale_mode != 0;             // octave 0 is the doubled input (pyramid_configure)
+  const float curSigma0 = up ? 1.0f : 0.5f;           // the blur the input is assumed to have (pyramid.cpp:504-509)
   bool initial_blur = par.initialSigma > curSigma0;
   if (initial_blur) {
     float sigma = sqrtf(par.initialSigma * par.initialSigma - curSigma0 * curSigma0);
@@ -1163,10 +1291,23 @@ static int pyramid_build_levels(mods_ctx *ctx, const float *img_dev, int stride)
                                     (size_t)h * n_img, hipMemcpyDeviceToDevice, ctx->stream));
     src0 = packed;
   }
+  // a doubled first octave: the doubled batch goes straight into level 0 where there is no initial blur, into up_tmp in front of
+  // an unfused one, and nowhere when the blur launch doubles in its loader
+  const int ow = P.oct[0].w, oh = P.oct[0].h;         // w x h, or 2w x 2h
+  const bool up_fused = up && upscale_first_level_fused(ctx, par, w, h);
+  if (up && !up_fused) {
+    float *dbl = P.oct[0].blur[0];
+    if (initial_blur) {
+      if (ctx->up_tmp.capacity() < (size_t)ow * oh * n_img) { set_error("upscale_input: no room for the doubled batch"); return MODS_E_CAPACITY; }
+      dbl = ctx->up_tmp;
+    }
+    if ((rc = launch_upscale2x(ctx, src0, dbl, w, h, n_img))) return rc;
+    src0 = dbl;
+  }
   if (par.detectorType != MODS_DET_HESSIAN) {   // DoG / Harris: plain blurs, the response of every level from its own launches
     if (initial_blur) {
-      if ((rc = blur_with_slot(ctx, src0, P.oct[0].blur[0], w, h, n_img, 0, ntap[0]))) return rc;
-    } else {
+      if ((rc = blur_with_slot(ctx, src0, P.oct[0].blur[0], ow, oh, n_img, 0, ntap[0]))) return rc;
+    } else if (!up) {
       MODS_HIP_CHECK(hipMemcpyAsync(P.oct[0].blur[0], src0, sizeof(float) * (size_t)w * h * n_img, hipMemcpyDeviceToDevice, ctx->stream));
     }
     for (int oi = 0; oi < P.n_oct; oi++) {
@@ -1186,8 +1327,8 @@ static int pyramid_build_levels(mods_ctx *ctx, const float *img_dev, int stride)
   // every blur launch also writes the Hessian response of its output (fused kernel): the separate response launch is left for
   // the first level of the octaves that start from a decimated plane
   if (initial_blur) {
-    if ((rc = blur_with_slot(ctx, src0, P.oct[0].blur[0], w, h, n_img, 0, ntap[0], P.oct[0].resp[0], P.oct[0].sigma[0] * P.oct[0].sigma[0]))) return rc;
-  } else {
+    if ((rc = blur_with_slot(ctx, src0, P.oct[0].blur[0], ow, oh, n_img, 0, ntap[0], P.oct[0].resp[0], P.oct[0].sigma[0] * P.oct[0].sigma[0], up_fused))) return rc;
+  } else if (!up) {
     MODS_HIP_CHECK(hipMemcpyAsync(P.oct[0].blur[0], src0, sizeof(float) * (size_t)w * h * n_img, hipMemcpyDeviceToDevice, ctx->stream));
   }
   // Octave k + 1 needs only level S of octave k.  With a batch of large planes the octaves from the third on (6 % of the pixels, but
@@ -1198,7 +1339,7 @@ static int pyramid_build_levels(mods_ctx *ctx, const float *img_dev, int stride)
   // join: the side chain then only had one blur launch to hide under, 1.436 against 1.416 ms; with octave 1 - all of it, or its
   // last level and its NMS - on the side stream as well the side chain is the longer one: 1.05-1.06 against 0.99-1.01 ms.)  mods_ctx_pyramid_streams(ctx, 1)
   // keeps one stream.
-  const bool fork = ctx->pyr_streams >= 2 && P.n_oct >= 2 && S < P.n_levels - 1 && (size_t)w * h * n_img >= ((size_t)4 << 20);
+  const bool fork = ctx->pyr_streams >= 2 && P.n_oct >= 2 && S < P.n_levels - 1 && (size_t)ow * oh * n_img >= ((size_t)4 << 20);
   ctx->pyr_side = false;
   ctx->pyr_forked = false;
   // the octaves from `first_lds` on fit LDS and are built by pyramid_lds_kernel in one launch
