@@ -146,6 +146,8 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_REPROJECT_H,  /* the post-pass of a homography view (reproject_regions_h_kernel): reprojection, tests and compaction */
        MODS_STAGE_SPATIAL_SELECT, /* the spatial selection of a count mode's cut (mods_ctx_spatial_selection): radius, ranking and
                                      compaction, behind MODS_STAGE_SORT and outside it */
+       MODS_STAGE_KNN,          /* a k-nearest-neighbour search (mods_match_knn[_dev|_reps]): pack, sweep and merge */
+       MODS_STAGE_KNN_SWEEP,    /* the matrix-core kernel of that search alone (knn_sweep_kernel, i8 MFMA), inside MODS_STAGE_KNN */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -517,6 +519,32 @@ int mods_match_dev(mods_ctx *ctx, int img_q, int img_t, double ratio, double con
  * it; tests use it to know which tile-loop variant a list length reaches. */
 int mods_match_grid(int n_q, int n_t, int out[3]);
 
+/* Exact k-nearest-neighbour search (what cv::DescriptorMatcher::knnMatch and FLANN's knnSearch give; the reference calls the
+ * latter with nn = 50).  For every query i and K = min(k, n_t), row i of the result holds the K trains with the smallest keys
+ * (d, t) in increasing key order: d = the exact integer squared L2 distance over the 128 descriptor bytes (0 .. 8 323 200), t = the
+ * train's index in the list it was given in; ties in d go to the lower index, as in mods_match_fginn.  Positions K .. k-1 of a row
+ * hold index -1 and distance INT_MAX.  Nothing depends on a summation or visiting order: the result is defined to the bit.  FLANN's
+ * own order among equal distances is not pinned against this one.
+ * idx_out, d2_out: [n_q][k] ints on the host; either may be null, not both.
+ * mods_match_knn       host lists, staged as mods_match_fginn stages them
+ * mods_match_knn_dev   the region lists the context holds after mods_detect_describe_dev (img_q == img_t is allowed: the nearest
+ *                      train of a region is then itself, or an equal descriptor at a lower index)
+ * mods_match_knn_reps  queries [q_begin, q_end) of a bank; rows are relative to q_begin, train indices refer to the full bank
+ * Refusals (MODS_E_ARG, before any device call): a null context, list or bank, both outputs null, k < 1 or k > 64, a negative
+ * count, q_begin > q_end or a range outside the bank, an image index outside the last described batch; a list longer than the
+ * context's capacity: MODS_E_CAPACITY.  n_q == 0: MODS_OK, nothing is written; n_t == 0: MODS_OK, every row is padding.
+ * State: the search has buffers of its own, reserved on first use.  It leaves the matcher's "last search" (what
+ * mods_match_fetch_internal and the fetch entry points read), the guided and the overlap buffers alone, and it ignores
+ * mods_ctx_match_mutual.  Timers: MODS_STAGE_KNN, MODS_STAGE_KNN_SWEEP.
+ * mods_match_knn_grid: {query blocks, train splits, 32-row train tiles per split} of the sweep for these sizes (n_q, n_t >= 0) and a
+ * forced split count (0: the library's choice; at most 64 splits and never more than the list has tiles; trailing splits of a forced
+ * count may be empty).  Host arithmetic only.  mods_ctx_knn_splits sets that forced count for a context (0: the library chooses); a
+ * testing knob, the result never depends on it.  A negative count: MODS_E_ARG. */
+int mods_match_knn(mods_ctx *ctx, const mods_region *q, int n_q, const mods_region *t, int n_t, int k, int *idx_out, int *d2_out);
+int mods_match_knn_dev(mods_ctx *ctx, int img_q, int img_t, int k, int *idx_out, int *d2_out);
+int mods_match_knn_grid(int n_q, int n_t, int k, int forced_splits, int out[3]);
+int mods_ctx_knn_splits(mods_ctx *ctx, int splits);
+
 /* Replaces  void DuplicateFiltering(TentativeCorrespListExt &in, const double r, const int mode)
  * (matching.cpp:2615-2679).  Host-side, in place on (tent, u6); mode 0 = keep order (MODE_RANDOM),
  * 1 = best FGINN ratio first, 2 = best distance first (configuration.hpp:31-34); equal keys keep
@@ -860,6 +888,8 @@ int mods_imgrep_append_host(mods_imgrep *rep, const mods_region *src, int n);
 int mods_imgrep_fetch(mods_imgrep *rep, int begin, int count, mods_region *out);
 int mods_match_reps(mods_ctx *ctx, const mods_imgrep *q, int q_begin, int q_end, const mods_imgrep *t, double ratio,
                     double contradDist, int nn, mods_tentative *out, double *u6_out, double *laf_out, int max_out, int *n_out);
+/* the k nearest trains of the bank's queries [q_begin, q_end): section B4, mods_match_knn */
+int mods_match_knn_reps(mods_ctx *ctx, const mods_imgrep *q, int q_begin, int q_end, const mods_imgrep *t, int k, int *idx_out, int *d2_out);
 /* img1_dev, img2_dev: dense fp32 images in HBM; the context needs max_w = max_h >= ceil(hypot(w, h)) of the larger image. */
 int mods_match_ladder_dev(mods_ctx *ctx, const float *img1_dev, int w1, int h1, const float *img2_dev, int w2, int h2,
                           const mods_ladder_step *steps, int n_steps, int min_matches, const mods_pair_params *par,

@@ -20,7 +20,7 @@ STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
 # MODS_STAGE_* added after that list was pinned by its users: their indices follow it
-STAGES_LATER = ["local_affine", "reproject_h", "spatial_select"]
+STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep"]
 
 
 def stage_index(name):
@@ -861,6 +861,31 @@ class Context:
         """mods_ctx_overlap_splits: train splits of the overlap sweeps (0 = automatic); the result does not depend on it."""
         _check(lib().mods_ctx_overlap_splits(self.h, int(splits)))
 
+    def match_knn(self, q, t, k):
+        """mods_match_knn: the k nearest trains of every query of two host region lists, by exact squared L2 distance over the
+        descriptor bytes, ties to the lower index; returns (dist[n_q, k] int32, index[n_q, k] int32), rows in (d, index) order,
+        padded with (INT_MAX, -1) where the train list is shorter than k."""
+        q = np.ascontiguousarray(q); t = np.ascontiguousarray(t)
+        return _knn_rows(len(q), k, lambda idx, d2: lib().mods_match_knn(self.h, _vp(q) if len(q) else None, len(q),
+                                                                         _vp(t) if len(t) else None, len(t), int(k), idx, d2))
+
+    def match_knn_dev(self, img_q, img_t, k):
+        """mods_match_knn_dev: the same on the region lists of images img_q / img_t that the last detect_describe_dev left in HBM."""
+        n = C.c_int()
+        _check(lib().mods_regions_fetch(self.h, int(img_q), None, 0, C.byref(n)))
+        return _knn_rows(n.value, k, lambda idx, d2: lib().mods_match_knn_dev(self.h, int(img_q), int(img_t), int(k), idx, d2))
+
+    def match_knn_reps(self, rep_q, rep_t, k, q_begin=0, q_end=None):
+        """mods_match_knn_reps: queries [q_begin, q_end) of ImgRep rep_q against all of ImgRep rep_t; rows are relative to q_begin,
+        indices refer to the full bank."""
+        q_end = len(rep_q) if q_end is None else q_end
+        return _knn_rows(max(q_end - q_begin, 0), k, lambda idx, d2: lib().mods_match_knn_reps(
+            self.h, rep_q.h, int(q_begin), int(q_end), rep_t.h, int(k), idx, d2))
+
+    def knn_splits(self, n):
+        """mods_ctx_knn_splits: train splits of the k-NN sweep (0 = automatic); the result does not depend on it."""
+        _check(lib().mods_ctx_knn_splits(self.h, int(n)))
+
     def clahe(self, img_u8, clip_limit=4.0, tiles=(8, 8)):
         """mods_clahe: CLAHE of one 8-bit grey image [h, w] (host in, host out); tiles = (tiles_x, tiles_y)"""
         a = np.ascontiguousarray(img_u8, np.uint8)
@@ -996,6 +1021,23 @@ def match_grid(n_q, n_t):
     out = (C.c_int * 3)()
     _check(lib().mods_match_grid(int(n_q), int(n_t), out))
     return out[0], out[1], out[2]
+
+
+def knn_grid(n_q, n_t, k, forced_splits=0):
+    """mods_match_knn_grid: (query blocks, train splits, tiles per split) of the sweep of an n_q x n_t k-NN search (forced_splits as
+    Context.knn_splits sets them); needs no device."""
+    out = (C.c_int * 3)()
+    _check(lib().mods_match_knn_grid(int(n_q), int(n_t), int(k), int(forced_splits), out))
+    return out[0], out[1], out[2]
+
+
+def _knn_rows(n_q, k, call):
+    """room for the rows of a k-NN search; call(idx, d2) fills them and returns its code; returns (dist, index)"""
+    k = int(k)
+    dist = np.zeros((n_q, max(k, 1)), np.int32)
+    index = np.zeros((n_q, max(k, 1)), np.int32)
+    _check(call(index.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p)))
+    return dist, index
 
 
 def list_search_grid(search, n_q, n_t, forced_splits=0):

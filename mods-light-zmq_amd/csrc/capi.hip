@@ -970,6 +970,35 @@ int mods_match_dev(mods_ctx *c, int img_q, int img_t, double ratio, double contr
   return mods_match_fetch_internal(c, out, u6_out, laf_out, max_out, n_out);
 }
 
+// The k nearest trains of every query (knn.hip), host lists staged as mods_match_fginn stages them.  The matcher's scratch and its
+// "last search" are not touched: the search packs into buffers of its own
+int mods_match_knn(mods_ctx *c, const mods_region *q, int n_q, const mods_region *t, int n_t, int k, int *idx_out, int *d2_out) {
+  if (!c || (n_q > 0 && !q) || (n_t > 0 && !t)) { set_error("match_knn: null argument"); return MODS_E_ARG; }
+  if (n_q < 0 || n_t < 0) { set_error("match_knn: negative count (%d queries, %d trains)", n_q, n_t); return MODS_E_ARG; }
+  int rc = knn_check("match_knn", k, idx_out, d2_out);
+  if (rc) return rc;
+  if (n_q > c->max_cand || n_t > c->max_cand) { set_error("match_knn: list larger than the context capacity"); return MODS_E_CAPACITY; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  if (n_q > 0 && n_t > 0) {
+    MODS_HIP_CHECK(mods::reserve_scratch(c, c->m_regs, 2 * (size_t)c->max_cand, 2 * (size_t)c->max_cand));
+    MODS_HIP_CHECK(hipMemcpyAsync(c->m_regs, q, sizeof(mods_region) * n_q, hipMemcpyHostToDevice, c->stream));
+    MODS_HIP_CHECK(hipMemcpyAsync(c->m_regs + c->max_cand, t, sizeof(mods_region) * n_t, hipMemcpyHostToDevice, c->stream));
+  }
+  return knn_search(c, "match_knn", c->m_regs, n_q, c->m_regs + c->max_cand, n_t, k, idx_out, d2_out);
+}
+
+int mods_match_knn_dev(mods_ctx *c, int img_q, int img_t, int k, int *idx_out, int *d2_out) {
+  if (!c) { set_error("match_knn_dev: null context"); return MODS_E_ARG; }
+  int rc = knn_check("match_knn_dev", k, idx_out, d2_out);
+  if (rc) return rc;
+  const int nb = (int)c->last_region_counts.size();
+  if (img_q < 0 || img_q >= nb || img_t < 0 || img_t >= nb) { set_error("match_knn_dev: image index outside the last described batch"); return MODS_E_ARG; }
+  if (c->last_region_counts[img_q] > c->max_cand || c->last_region_counts[img_t] > c->max_cand) { set_error("match_knn_dev: list larger than the context capacity"); return MODS_E_CAPACITY; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  return knn_search(c, "match_knn_dev", c->regions_dev + (size_t)img_q * c->max_cand, c->last_region_counts[img_q],
+                    c->regions_dev + (size_t)img_t * c->max_cand, c->last_region_counts[img_t], k, idx_out, d2_out);
+}
+
 // DuplicateFiltering, matching.cpp:2615-2679: optional stable sort, then the first correspondence
 // (in list order) of every group whose two endpoints lie within r of each other survives.  A uniform
 // grid over the first-image points (cell = r) bounds the candidates to the 3x3 neighbourhood; the

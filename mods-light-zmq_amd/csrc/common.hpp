@@ -344,6 +344,16 @@ struct mods_ctx {
   bool mu_last_checked = false;      // the last single search of the context went through the check
   mods::Buf<int4> mu_cand;
   mods::PinnedBuf<int> mu_count;
+  // k-nearest-neighbour search (knn.hip), its own buffers, reserved on first use: the packed lists (queries first: descriptors;
+  // norms, seeds, parity words and the pack kernel's two counters; centres), the sorted keys every (train split, query) leaves, the
+  // result rows on the device (d2 | idx) and their pinned twin; kn_splits: mods_ctx_knn_splits
+  mods::Buf<int8_t> kn_desc;
+  mods::Buf<int> kn_c;
+  mods::Buf<double2> kn_xy;
+  mods::Buf<unsigned long long> kn_part;
+  mods::Buf<int> kn_out;
+  mods::PinnedBuf<int> kn_host;
+  int kn_splits = 0;
   // local affine consistency filter (local_affine.hip; mods_ctx_local_affine): off by default.  la_buf: the SoA scratch, counters and
   // places of the lists of one set of launches; la_io: source and kept list of the host-list entry point; la_count: list lengths in and
   // out, pinned; the counts of the last filtered list
@@ -482,6 +492,12 @@ int match_run_distance(mods_ctx *ctx, const mods_region *q_dev, int n_q, const m
 int match_ensure_buffers(mods_ctx *ctx, int n_sets = 1);
 int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, const int *n_q, const mods_region *const *t_dev, const int *n_t,
                     mods_tentative *const *tent_out, int *const *count_out, double ratio, double contradDist, int nn);   // <= 16 searches in one set of launches
+
+// knn.hip: the K = min(k, n_t) nearest trains of every query of two device lists, in (d, t) order, into host rows [n_q][k] (either
+// may be null); checks its arguments, waits for the stream
+int knn_search(mods_ctx *ctx, const char *who, const mods_region *q_dev, int n_q, const mods_region *t_dev, int n_t, int k, int *idx_out,
+               int *d2_out);
+int knn_check(const char *who, int k, const int *idx_out, const int *d2_out);   // the refusals that need no context
 
 // dedup.hip
 constexpr int DUP_MAX_JOBS = 64;

@@ -207,6 +207,18 @@ int mods_match_reps_any(mods_ctx *c, const mods_imgrep *q, int q_begin, int q_en
   return MODS_OK;
 }
 
+// The k nearest trains of queries [q_begin, q_end) of bank `q` in bank `t` (knn.hip): rows are relative to q_begin, train indices
+// refer to the full bank
+int mods_match_knn_reps(mods_ctx *c, const mods_imgrep *q, int q_begin, int q_end, const mods_imgrep *t, int k, int *idx_out, int *d2_out) {
+  if (!c || !q || !t) { set_error("match_knn_reps: null argument"); return MODS_E_ARG; }
+  int rc = knn_check("match_knn_reps", k, idx_out, d2_out);
+  if (rc) return rc;
+  if (q_begin < 0 || q_end > q->n || q_begin > q_end) { set_error("match_knn_reps: bad query range [%d, %d) of %d", q_begin, q_end, q->n); return MODS_E_ARG; }
+  if (q_end - q_begin > c->max_cand || t->n > c->max_cand) { set_error("match_knn_reps: list larger than the context capacity"); return MODS_E_CAPACITY; }
+  MODS_HIP_CHECK(hipSetDevice(c->device));
+  return knn_search(c, "match_knn_reps", q->reg + q_begin, q_end - q_begin, t->reg, t->n, k, idx_out, d2_out);
+}
+
 // ---- the step loop of mods.cpp:202-383 on one GPU ---------------------------------------------------------------
 // img1_dev / img2_dev: dense fp32 images in HBM (the two images may differ in size).  Every step adds the step's new views of both images to the two region
 // banks, matches bank 1 against bank 2, filters duplicates, verifies, and stops once the verified

@@ -30,10 +30,7 @@ namespace mods {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-// Accumulator seed of a train row: acc = dot - floor(ct/2) + MATCH_BIAS.  dot lies in [-2^21, 2^21] and ct in [2^21, 2^22], so the
-// seeded accumulators of real rows lie in [1, 5*2^20 + 1] (23 bits, never negative); the rows past the end of the list inside the last
-// tile carry zero descriptors and the seed 0: their accumulators are exactly 0, below every real one.
-constexpr int MATCH_BIAS = (1 << 22) + 1;
+// (MATCH_BIAS, the accumulator seed's offset: match_types.hpp)
 
 // Packs one region list for the matcher: int8 descriptors (v-128), c = sum v^2 - 256*sum(v-128),
 // centre coordinates.  grid = ceil(n/4), block = 256 (one wave per region).
@@ -72,7 +69,6 @@ __global__ __launch_bounds__(256) void match_pack_kernel(const mods_region *__re
 // consecutive regions - one tile of the distance kernels, two lanes per region - and WRITES the tile's parity word (the single-list kernel ORs bits into
 // words that a launch before it had to clear), block (0, 0) clears the two counters of the search.  Three dispatches fewer per search.
 // grid = (ceil(max(n_q, n_t) / 32 / 4), 2, searches), block 256
-struct PackList { const mods_region *reg; int n; int8_t *desc; int *cvec; int *c2neg; unsigned int *parity; double2 *xy; };
 __global__ __launch_bounds__(256) void match_pack2_kernel(MatchJobs J, PackList lq, PackList lt, int max_n, int *__restrict__ count2) {
   const int job = blockIdx.z;
   PackList L = blockIdx.y == 0 ? lq : lt;       // (reg and n of the lists come from the job table)
@@ -903,6 +899,17 @@ int match_ensure_buffers(mods_ctx *ctx, int n_sets) {
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_c, 0, S * st.s_c * sizeof(int), ctx->stream));
   ctx->m_sets = n_sets;
   return MODS_OK;
+}
+
+// The pack launch of one search into arrays of the caller's choice (knn.hip packs into buffers of its own); counters: the two
+// ints the kernel clears
+void match_pack_lists(mods_ctx *ctx, const mods_region *q_dev, int n_q, const mods_region *t_dev, int n_t, const PackList &lq, const PackList &lt,
+                      int *counters) {
+  MatchJobs J;
+  memset(&J, 0, sizeof(J));
+  J.n_jobs = 1; J.n_q[0] = n_q; J.n_t[0] = n_t; J.q_reg[0] = q_dev; J.t_reg[0] = t_dev; J.count_out[0] = counters;
+  hipLaunchKernelGGL(match_pack2_kernel, dim3((std::max(std::max(n_q, n_t), 1) + 127) / 128, 2, 1), dim3(256), 0, ctx->stream, J, lq, lt, ctx->max_cand,
+                     counters + 1);
 }
 
 // One launch instead of three memsets per search: tentative counter, pass-2 list counter and the parity words the pack kernels

@@ -36,6 +36,17 @@ template <class T> __device__ __forceinline__ T *set_by(T *p, int job, size_t st
   return (T *)((C *)p + (size_t)job * stride_bytes);
 }
 
+// Accumulator seed of a train row: acc = dot - floor(ct/2) + MATCH_BIAS.  dot lies in [-2^21, 2^21] and ct in [2^21, 2^22], so the
+// seeded accumulators of real rows lie in [1, 5*2^20 + 1] (23 bits, never negative); the rows past the end of the list inside the last
+// tile carry zero descriptors and the seed 0: their accumulators are exactly 0, below every real one.
+constexpr int MATCH_BIAS = (1 << 22) + 1;
+
+// where match_pack2_kernel leaves one packed list: int8 descriptors (v - 128), c = sum v^2 - 256 * sum (v - 128), the accumulator
+// seeds, one parity word (c & 1) per 32-row tile, the centres
+struct PackList { const mods_region *reg; int n; int8_t *desc; int *cvec; int *c2neg; unsigned int *parity; double2 *xy; };
+void match_pack_lists(mods_ctx *ctx, const mods_region *q_dev, int n_q, const mods_region *t_dev, int n_t, const PackList &lq, const PackList &lt,
+                      int *counters);   // match.hip
+
 struct QueryMid {        // per query state between the passes
   int i0, d0, dstar, pad;
   double x0, y0;
