@@ -148,6 +148,8 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
                                      compaction, behind MODS_STAGE_SORT and outside it */
        MODS_STAGE_KNN,          /* a k-nearest-neighbour search (mods_match_knn[_dev|_reps]): pack, sweep and merge */
        MODS_STAGE_KNN_SWEEP,    /* the matrix-core kernel of that search alone (knn_sweep_kernel, i8 MFMA), inside MODS_STAGE_KNN */
+       MODS_STAGE_DISTRACTOR,   /* the distractor-database veto of a search (mods_ctx_distractor_db): gather, sweep, fold and the ratio pass */
+       MODS_STAGE_DISTRACTOR_SWEEP, /* the matrix-core kernel of that veto alone (descdb_sweep_kernel, i8 MFMA), inside MODS_STAGE_DISTRACTOR */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -1246,6 +1248,67 @@ int mods_match_overlap_area_reps(mods_ctx *ctx, const mods_imgrep *q, const mods
 int mods_ctx_match_mutual(mods_ctx *ctx, int mode);
 int mods_match_mutual_counts(mods_ctx *ctx, int *n_forward, int *n_kept);
 int mods_pipeline_match_mutual(mods_pipeline *p, int mode);
+
+/* ---- distractor descriptor database of the FGINN ratio test --------------------------------------------
+ * MatchFlannFGINNPlusDB (matching/matching.cpp:461-572, field d2byDB of matching.hpp:48), which the reference defines and never
+ * calls: the FGINN walk plus a second opinion from a database B of unrelated descriptors.  csrc/distractor.hip; restated in
+ * tests/distractor_ref.py.  Off by default: with no database attached every search is what it was, to the bit and to the launch.
+ * With d(a, b) the exact integer squared L2 distance over the 128 descriptor bytes, quot(x, y) = (double)((float)x / (float)y)
+ * (0/0 is NaN, x/0 is +inf), sq = ratio * ratio in fp64 and M >= 1 rows in B, for every tentative (q, t) of the forward search:
+ *   d0 = d(q, t) (field d1), dj = the distance the tentative was emitted with (field d2), dDB = min over the rows b of B of d(q, b);
+ *   rDB = quot(d0, dDB), r = quot(d0, dj), r' = (r < rDB) ? rDB : r   (std::max(ratio, ratioDB) of line 547: a NaN rDB leaves r);
+ *   the tentative is dropped when !(r' <= sq) - that is rDB > sq; dDB = 0 with d0 > 0 drops it - and otherwise kept with
+ *   ratio = sqrt(r') in fp64, every other field, u6 and laf as the forward search wrote them.
+ * Survivors stay in query order, nothing is re-assigned.  dDB is a minimum of integers: nothing depends on order, splits or launch
+ * geometry.  Parity with FLANN's tie order is unpinned, as for the matcher; nothing else is approximate.
+ * The veto is part of the search: the mutual check (independent of it), the local affine filter, duplicate filtering and
+ * verification see the vetoed list, n_tentatives and the "last search" fetch entry points report it.  Honoured by every FGINN search
+ * of a context: mods_match_fginn, mods_match_dev, mods_match_reps[_any] (slices allowed: the test is per tentative),
+ * mods_match_pair_dev, mods_match_verify_reps, mods_rematch_under_h_dev, the single-GPU ladder entry points and a pipeline's grouped
+ * searches.  A context holds two slots: one database for whole descriptors (whatever fills `desc`) and one that the ladder's
+ * HalfRootSIFT searches take; a search whose kind has no database runs unvetoed.  An empty database (M = 0) equals none.  The Hamming
+ * matcher (mods_match_distance), mods_match_knn*, guided and overlap matching ignore the databases; the multi-GPU entry points
+ * (mods_multi_*, mods_match_ladder_multi) have no switch: their searches are unvetoed.
+ *
+ * A mods_descdb is immutable, lives on one device and is shared by any number of contexts, pipelines and threads of that device, as
+ * a mods_net is.  It is packed once at creation into what the distance kernels stream (int8 rows v - 128 in 32-row tiles of 4096
+ * bytes, accumulator seeds, a parity word per tile; rows past the end zero); no search packs it again.  Capacity: 2^24 rows
+ * (MODS_E_CAPACITY beyond).  References: the creator holds one, every context slot it is attached to holds one (released by
+ * attaching something else, by null, or by mods_ctx_destroy).  mods_descdb_destroy gives up the creator's reference; the memory
+ * is freed when the last reference goes, so destroying a database a live context uses is deferred, never refused.
+ *   mods_descdb_create            from n host rows of 128 bytes (n = 0 allowed)
+ *   mods_descdb_create_from_reps  from the descriptors of n_reps banks of ctx's device, in order
+ *   mods_descdb_min_dist          dDB of n host descriptors (INT_MAX per row for M = 0)
+ *   mods_filter_distractor        the veto on a host list, in place: tent/u6/laf of n tentatives whose q index the n_q regions q;
+ *                                 d_db_out[n_out] (may be null) = dDB of the survivors
+ *   mods_ctx_distractor_db        attaches (or, with null, detaches) the two slots
+ *   mods_distractor_counts        of the last single search: the forward list's length (after a mutual check, before the veto) and
+ *                                 what the veto kept; equal when that search was not vetoed.  Waits for the stream
+ *   mods_distractor_fetch         dDB of that search's survivors, in list order (*n = 0 when it was not vetoed).  A vetoed batch of
+ *                                 searches on the same context in between (a pipeline worker's batch of pairs) takes the
+ *                                 scratch both calls read: after it they answer as for a search that was not vetoed, until the
+ *                                 next single search
+ *   mods_pipeline_distractor_db   the whole-descriptor slot of every worker's context, before the first submit (later: MODS_E_ARG)
+ *   mods_descdb_grid              {query blocks, database splits, 32-row tiles per split} of the sweep of n_queries queries against m
+ *                                 rows with a forced split count (0: the library chooses; trailing splits may be empty).  Host
+ *                                 arithmetic only
+ *   mods_ctx_descdb_splits        that forced count for a context: a testing knob, the result never depends on it
+ * Refusals are MODS_E_ARG with a mods_last_error text, before any device call: null pointers, negative counts, a database of another
+ * device, a tentative whose q is outside the list.  Timers: MODS_STAGE_DISTRACTOR, MODS_STAGE_DISTRACTOR_SWEEP. */
+typedef struct mods_descdb mods_descdb;
+int mods_descdb_create(int device, const uint8_t *desc_host, long n, mods_descdb **out);
+int mods_descdb_create_from_reps(mods_ctx *ctx, const struct mods_imgrep *const *reps, int n_reps, mods_descdb **out);
+long mods_descdb_count(const mods_descdb *db);
+void mods_descdb_destroy(mods_descdb *db);
+int mods_descdb_min_dist(mods_ctx *ctx, const mods_descdb *db, const uint8_t *desc_host, int n, int *d2_out);
+int mods_filter_distractor(mods_ctx *ctx, const mods_descdb *db, const mods_region *q, int n_q, double ratio, mods_tentative *tent,
+                           double *u6, double *laf, int n, int *d_db_out, int *n_out);
+int mods_ctx_distractor_db(mods_ctx *ctx, const mods_descdb *full_or_null, const mods_descdb *half_or_null);
+int mods_distractor_counts(mods_ctx *ctx, int *n_forward, int *n_kept);
+int mods_distractor_fetch(mods_ctx *ctx, int *d_db_out, int max, int *n);
+int mods_pipeline_distractor_db(mods_pipeline *p, const mods_descdb *full_or_null);
+int mods_descdb_grid(long m, int n_queries, int forced_splits, int out[3]);
+int mods_ctx_descdb_splits(mods_ctx *ctx, int splits);
 
 /* ---- local affine consistency of neighbouring tentatives ----------------------------------------------
  * No counterpart in the reference, which uses the local affine frames of a tentative only in the LAF checks on RANSAC's result.

@@ -20,7 +20,7 @@ STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
 # MODS_STAGE_* added after that list was pinned by its users: their indices follow it
-STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep"]
+STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep", "distractor", "distractor_sweep"]
 
 
 def stage_index(name):
@@ -597,6 +597,30 @@ class Context:
         of the per-input diagnostics keep (bool), neighbours, support, backed (int32)"""
         return filter_local_affine(self, tent, u6, laf, params)
 
+    def set_distractor_db(self, full=None, half=None):
+        """mods_ctx_distractor_db: the DescDB every FGINN search of whole descriptors is vetoed by, and the one the ladder's
+        HalfRootSIFT searches take; None detaches a slot.  The context keeps a reference to what it holds."""
+        _check(lib().mods_ctx_distractor_db(self.h, full.h if full is not None else None, half.h if half is not None else None))
+        self._distractor = (full, half)
+
+    def distractor_counts(self):
+        """(forward tentatives, tentatives the distractor databases kept) of the context's last single search"""
+        nf, nk = C.c_int(), C.c_int()
+        _check(lib().mods_distractor_counts(self.h, C.byref(nf), C.byref(nk)))
+        return nf.value, nk.value
+
+    def distractor_fetch(self, cap=None):
+        """mods_distractor_fetch: dDB of the last single search's survivors, in list order (empty when it was not vetoed)"""
+        cap = self.distractor_counts()[1] if cap is None else cap
+        out = np.zeros(max(cap, 1), np.int32)
+        n = C.c_int()
+        _check(lib().mods_distractor_fetch(self.h, _vp(out), int(cap), C.byref(n)))
+        return out[:n.value].copy()
+
+    def descdb_splits(self, n):
+        """mods_ctx_descdb_splits: database splits of the distractor sweep (0 = automatic); the result does not depend on it."""
+        _check(lib().mods_ctx_descdb_splits(self.h, int(n)))
+
     def match_mutual_counts(self):
         """(forward tentatives, tentatives the mutual check kept) of the context's last single search"""
         nf, nk = C.c_int(), C.c_int()
@@ -1029,6 +1053,78 @@ def knn_grid(n_q, n_t, k, forced_splits=0):
     out = (C.c_int * 3)()
     _check(lib().mods_match_knn_grid(int(n_q), int(n_t), int(k), int(forced_splits), out))
     return out[0], out[1], out[2]
+
+
+def descdb_grid(m, n_queries, forced_splits=0):
+    """mods_descdb_grid: (query blocks, database splits, tiles per split) of the distractor sweep of n_queries queries against m rows
+    (forced_splits as Context.descdb_splits sets them); needs no device."""
+    out = (C.c_int * 3)()
+    _check(lib().mods_descdb_grid(C.c_long(int(m)), int(n_queries), int(forced_splits), out))
+    return out[0], out[1], out[2]
+
+
+class DescDB:
+    """mods_descdb_*: an immutable database of distractor descriptors on one device, packed once for the distance kernels; any number
+    of contexts and pipelines of the device may share it (Context.set_distractor_db, Pipeline.set_distractor_db).  desc: (n, 128)
+    uint8, n = 0 allowed; or DescDB.from_reps(ctx, reps) from the descriptors of ImgRep banks."""
+
+    def __init__(self, desc=None, device=0, _handle=None):
+        self.h = C.c_void_p()
+        self.device = device
+        if _handle is not None:
+            self.h = _handle
+            return
+        d = np.ascontiguousarray(desc if desc is not None else np.zeros((0, 128), np.uint8))
+        if d.dtype != np.uint8 or d.ndim != 2 or d.shape[1] != 128:
+            raise ModsError("DescDB: descriptors of shape %s and type %s, (n, 128) uint8 expected" % (tuple(d.shape), d.dtype))
+        _check(lib().mods_descdb_create(int(device), _vp(d) if len(d) else None, C.c_long(len(d)), C.byref(self.h)))
+
+    @staticmethod
+    def from_reps(ctx, reps):
+        h = C.c_void_p()
+        arr = (C.c_void_p * max(len(reps), 1))(*[r.h for r in reps])
+        _check(lib().mods_descdb_create_from_reps(ctx.h, arr, len(reps), C.byref(h)))
+        return DescDB(_handle=h)
+
+    def __len__(self):
+        lib().mods_descdb_count.restype = C.c_long
+        return int(lib().mods_descdb_count(self.h))
+
+    def close(self):
+        """gives up this object's reference; a context that holds the database keeps it alive"""
+        if self.h:
+            lib().mods_descdb_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def min_dist(self, ctx, desc):
+        """mods_descdb_min_dist: the exact squared L2 distance of every row of desc (n, 128) uint8 to its nearest database row
+        (INT_MAX for an empty database)"""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 128)
+        out = np.zeros(max(len(d), 1), np.int32)
+        _check(lib().mods_descdb_min_dist(ctx.h, self.h, _vp(d) if len(d) else None, len(d), _vp(out)))
+        return out[:len(d)].copy()
+
+
+def filter_distractor(ctx, db, q, tent, u6, laf, ratio=0.8):
+    """mods_filter_distractor on copies of the three arrays: the veto of DescDB db on a host list whose q indices name rows of the
+    region list q; returns (tent, u6, laf, dDB) of the survivors in list order"""
+    q = np.ascontiguousarray(q)
+    tent = np.ascontiguousarray(tent, TENT_DTYPE).copy()
+    u6 = np.ascontiguousarray(u6, np.float64).reshape(-1, 6).copy()
+    laf = np.ascontiguousarray(laf, np.float64).reshape(-1, 14).copy()
+    n = len(tent)
+    ddb = np.zeros(max(n, 1), np.int32)
+    n_out = C.c_int()
+    _check(lib().mods_filter_distractor(ctx.h, db.h, _vp(q) if len(q) else None, len(q), C.c_double(ratio), _vp(tent) if n else None,
+                                        _vp(u6) if n else None, _vp(laf) if n else None, n, _vp(ddb), C.byref(n_out)))
+    k = n_out.value
+    return tent[:k], u6[:k], laf[:k], ddb[:k]
 
 
 def _knn_rows(n_q, k, call):
@@ -1922,6 +2018,11 @@ class Pipeline:
     def set_match_mutual(self, mode):
         """before the first submit"""
         _check(lib().mods_pipeline_match_mutual(self.h, int(mode)))
+
+    def set_distractor_db(self, full=None):
+        """mods_pipeline_distractor_db: the DescDB every search of the pipeline is vetoed by (None: none), before the first submit"""
+        _check(lib().mods_pipeline_distractor_db(self.h, full.h if full is not None else None))
+        self._distractor = full
 
     def set_u8_kernels(self, mask):
         """Context.set_u8_kernels on every GPU worker's context, before the first submit"""

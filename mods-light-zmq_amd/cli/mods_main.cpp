@@ -64,6 +64,9 @@ struct Config {
   std::string mask_fn[2];
   int use_mask_files = 0;
   int mutual_check = 0;            // [Matching] mutualCheck (no counterpart in the reference): mods_ctx_match_mutual
+  // [Matching] distractorDB / distractorDBHalf = a.npz[,b.npz...]: keypoint files of this program whose descriptors make the distractor
+  // databases of the FGINN searches (mods_ctx_distractor_db; MatchFlannFGINNPlusDB, which the reference never calls); absent: none
+  std::string distractor_db, distractor_db_half;
   // [SpatialSelection] doSpatialSelection / robustness (no counterpart in the reference): the FixedRegNumber / RelativeRegNumber steps
   // of the scale-space detectors keep the keys with the largest suppression radius (mods_ctx_spatial_selection, mode 2)
   int spatial = 0;
@@ -273,6 +276,8 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->mask_fn[0] = ini.GetString("DetectionMask", "mask1", "");
   cfg->mask_fn[1] = ini.GetString("DetectionMask", "mask2", "");
   cfg->use_mask_files = (int)ini.GetInteger("DetectionMask", "useMaskFiles", 0);
+  cfg->distractor_db = ini.GetString("Matching", "distractorDB", "");
+  cfg->distractor_db_half = ini.GetString("Matching", "distractorDBHalf", "");
   cfg->mutual_check = (int)ini.GetInteger("Matching", "mutualCheck", 0);
   if (cfg->mutual_check < 0 || cfg->mutual_check > 2) { std::cerr << "[Matching] mutualCheck must be 0, 1 or 2" << std::endl; return 1; }
   cfg->upscale = (int)ini.GetInteger("HessianAffine", "upscaleInputImage", 0);
@@ -625,6 +630,34 @@ mods_net *load_net(int device, int kind, const std::string &prefix, std::string 
   return net;
 }
 
+// The descriptors of a comma-separated list of keypoint files (member descs, (n, 128) u1, as SaveRegionsNPZ writes it), in the order
+// given, for a distractor database; `key` names the configuration key in the messages
+bool read_distractor_descs(const std::string &list, const char *key, std::vector<unsigned char> *out) {
+  out->clear();
+  size_t at = 0;
+  while (at <= list.size()) {
+    size_t end = list.find(',', at);
+    if (end == std::string::npos) end = list.size();
+    std::string fn = list.substr(at, end - at);
+    at = end + 1;
+    while (!fn.empty() && isspace((unsigned char)fn.back())) fn.pop_back();
+    while (!fn.empty() && isspace((unsigned char)fn.front())) fn.erase(fn.begin());
+    if (fn.empty()) continue;
+    std::map<std::string, modscli::NpyArray> z;
+    std::string err;
+    if (!modscli::npz_read(fn, &z, &err)) { std::cerr << "[Matching] " << key << ": " << fn << ": " << err << std::endl; return false; }
+    if (!z.count("descs")) { std::cerr << "[Matching] " << key << ": " << fn << ": no array descs" << std::endl; return false; }
+    const modscli::NpyArray &ds = z["descs"];
+    if (ds.descr != "|u1" || ds.shape.size() != 2) { std::cerr << "[Matching] " << key << ": " << fn << ": descs must be uint8 (n x 128)" << std::endl; return false; }
+    if (ds.shape[1] != 128) {
+      std::cerr << "[Matching] " << key << ": " << fn << ": descriptors of dimension " << ds.shape[1] << " (a distractor database holds 128-byte descriptors)" << std::endl;
+      return false;
+    }
+    out->insert(out->end(), (const unsigned char *)ds.data.data(), (const unsigned char *)ds.data.data() + ds.shape[0] * 128);
+  }
+  return true;
+}
+
 // PreLoadRegionsNPZ, imagerepresentation.cpp:1355-1503: xy, scales, responses, descs and either A, angles (degrees) or neither
 // (upright circles); det_kp = reproj_kp
 bool read_regions_npz(const std::string &fn, std::vector<mods_region> *out) {
@@ -805,6 +838,21 @@ int main(int argc, char **argv) {
     if (masks_ignored) std::cerr << "Note: [DetectionMask] is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
   }
 
+  // [Matching] distractorDB / distractorDBHalf: read and checked before anything else runs
+  std::vector<unsigned char> distractor_descs[2];
+  {
+    const std::string *lists[2] = {&cfg.distractor_db, &cfg.distractor_db_half};
+    const char *keys[2] = {"distractorDB", "distractorDBHalf"};
+    bool ignored = false;
+    for (int s = 0; s < 2; s++) {
+      if (lists[s]->find_first_not_of(" \t\r\n,") == std::string::npos) continue;
+      if (getenv("MODS_DEVICES")) { ignored = true; continue; }
+      if (!read_distractor_descs(*lists[s], keys[s], &distractor_descs[s])) return 1;
+      if (cfg.verbose) std::cerr << "[Matching] " << keys[s] << ": " << distractor_descs[s].size() / 128 << " descriptors" << std::endl;
+    }
+    if (ignored) std::cerr << "Note: [Matching] distractorDB / distractorDBHalf are ignored with MODS_DEVICES (the multi-GPU ladder has no distractor databases)" << std::endl;
+  }
+
   if (mods_device_count() <= 0) { std::cerr << "mods: no MI355X / HIP device available (" << mods_last_error() << "); this build has no CPU path" << std::endl; return 1; }
   const int device = getenv("MODS_DEVICE") ? atoi(getenv("MODS_DEVICE")) : 0;
   const double diag = std::ceil(std::max(std::hypot((double)img1.w, (double)img1.h), std::hypot((double)img2.w, (double)img2.h))) + 2;
@@ -823,6 +871,16 @@ int main(int argc, char **argv) {
     if (!det_mask[i].empty() && mods_ctx_detection_mask(ctx, i, det_mask[i].data(), i ? img2.w : img1.w, i ? img2.h : img1.h, i ? img2.w : img1.w))
       return fail("[DetectionMask]");
   if (cfg.mutual_check && mods_ctx_match_mutual(ctx, cfg.mutual_check)) return fail("mutualCheck");
+  {
+    // the context keeps its references; the creator's go at once
+    mods_descdb *dbs[2] = {nullptr, nullptr};
+    for (int s = 0; s < 2; s++)
+      if (!distractor_descs[s].empty() && mods_descdb_create(device, distractor_descs[s].data(), (long)(distractor_descs[s].size() / 128), &dbs[s]))
+        return fail(s ? "distractorDBHalf" : "distractorDB");
+    const int drc = (dbs[0] || dbs[1]) ? mods_ctx_distractor_db(ctx, dbs[0], dbs[1]) : 0;
+    for (int s = 0; s < 2; s++) { mods_descdb_destroy(dbs[s]); distractor_descs[s] = std::vector<unsigned char>(); }
+    if (drc) return fail("distractorDB");
+  }
   if (cfg.local_affine && mods_ctx_local_affine(ctx, &cfg.la_par)) return fail("[LocalAffineFiltering]");
   if (cfg.dsp && cfg.use_zmq) { std::cerr << "[SIFTDescriptor] domainSizePooling = 1 pools SIFT histograms: it cannot be combined with the [zmqDescriptor] descriptor" << std::endl; return 1; }
   if (cfg.dsp && mods_ctx_domain_pooling(ctx, cfg.dsp_scales, cfg.dsp_start, cfg.dsp_end)) return fail("domainSizePooling");

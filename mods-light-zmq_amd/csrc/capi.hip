@@ -251,6 +251,7 @@ mods_ctx::~mods_ctx() {
     for (auto &e : t.pool) (void)hipEventDestroy(e);
   }
   mser_release(this);
+  distractor_release(this);
   for (mods_ctx *h : helpers) if (h) mods_ctx_destroy(h);
   (void)hipSetDevice(device);
   dd_graph_drop(this);

@@ -354,6 +354,20 @@ struct mods_ctx {
   mods::Buf<int> kn_out;
   mods::PinnedBuf<int> kn_host;
   int kn_splits = 0;
+  // distractor databases of the FGINN searches (distractor.hip; mods_ctx_distractor_db): the attached databases (a reference each),
+  // which of them the next search takes (dr_half_search: set around a HalfRootSIFT search by its caller), the scratch of the veto
+  // per set of the matcher - compact packed queries, norms, their query indices, dDB per query, dDB per survivor, 16 counters - and
+  // the forward counts, pinned; the staging of the host entry points; dr_splits: mods_ctx_descdb_splits
+  const mods_descdb *dr_db[2] = {nullptr, nullptr};
+  bool dr_half_search = false;
+  bool dr_last_vetoed = false;       // the last single search of the context went through the veto
+  mods::Buf<int8_t> dr_desc;
+  mods::Buf<int> dr_int;
+  mods::PinnedBuf<int> dr_count;
+  mods::Buf<unsigned char> dr_stage;
+  mods::Buf<int> dr_out;
+  mods::PinnedBuf<int> dr_host;
+  int dr_splits = 0;
   // local affine consistency filter (local_affine.hip; mods_ctx_local_affine): off by default.  la_buf: the SoA scratch, counters and
   // places of the lists of one set of launches; la_io: source and kept list of the host-list entry point; la_count: list lengths in and
   // out, pinned; the counts of the last filtered list
@@ -498,6 +512,18 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
 int knn_search(mods_ctx *ctx, const char *who, const mods_region *q_dev, int n_q, const mods_region *t_dev, int n_t, int k, int *idx_out,
                int *d2_out);
 int knn_check(const char *who, int k, const int *idx_out, const int *d2_out);   // the refusals that need no context
+
+// distractor.hip: the database veto of one grouped launch, in two parts around the emit kernels (match.hip: match_run_group; the
+// pointers are those of set 0).  distractor_db_of: the database the context's next search takes, null for none
+struct MatchJobs; struct MatchConst;
+const mods_descdb *distractor_db_of(const mods_ctx *ctx);
+int distractor_stage(mods_ctx *ctx, const mods_descdb *db, const MatchJobs &J, const MatchConst &k, int max_q, size_t pad, const void *mid,
+                     const unsigned long long *key_ge, const unsigned long long *key_lt, const int *n_lt, int *bad, const int8_t *qd,
+                     const int *qc);
+int distractor_finish(mods_ctx *ctx, const MatchJobs &J, int max_q, size_t pad);
+void distractor_release(mods_ctx *ctx);    // the context's references (its destructor)
+// imgrep.hip: what a bank holds, for the files that do not see the struct
+void imgrep_view(const mods_imgrep *r, const mods_region **reg, int *n, int *device, hipStream_t *stream);
 
 // dedup.hip
 constexpr int DUP_MAX_JOBS = 64;

@@ -31,6 +31,10 @@ struct mods_imgrep {
 
 namespace mods {
 
+void imgrep_view(const mods_imgrep *r, const mods_region **reg, int *n, int *device, hipStream_t *stream) {
+  *reg = r->reg; *n = r->n; *device = r->device; *stream = r->stream;
+}
+
 // AddRegionsToList: id and parent_id are shifted by the size of the list they are appended to
 __global__ void __launch_bounds__(256) shift_ids_kernel(mods_region *reg, int n, int shift) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -227,12 +231,18 @@ int mods_match_knn_reps(mods_ctx *c, const mods_imgrep *q, int q_begin, int q_en
 // One FGINN search of bank q against bank t into a host list (MatchFlannFGINN of one (detector, descriptor) pair,
 // correspondencebank.cpp:288-340)
 // distance > 0: MatchFLANNDistance (Hamming, threshold `distance`) instead of the FGINN search
-static int match_into(mods_ctx *c, mods_imgrep *q, mods_imgrep *t, double ratio, const mods_pair_params *par, TentList *out, double distance = 0) {
+// half: a search of HalfRootSIFT lists, which takes the context's half slot of the distractor databases (mods_ctx_distractor_db)
+static int match_into(mods_ctx *c, mods_imgrep *q, mods_imgrep *t, double ratio, const mods_pair_params *par, TentList *out, double distance = 0,
+                      bool half = false) {
   int rc, m = 0;
   out->clear();
   if (!q || !t) return MODS_OK;
   if (distance > 0) rc = match_run_distance(c, q->reg, q->n, t->reg, t->n, distance);
-  else rc = match_run(c, q->reg, q->n, t->reg, t->n, ratio, par->contradDist, par->nn);
+  else {
+    c->dr_half_search = half;
+    rc = match_run(c, q->reg, q->n, t->reg, t->n, ratio, par->contradDist, par->nn);
+    c->dr_half_search = false;
+  }
   if (rc) return rc;
   MODS_HIP_CHECK(mods::stream_wait(c->stream));
   m = read_slot(c->m_count, count_slot());
@@ -293,7 +303,7 @@ static int match_verify_banks(mods_ctx *c, mods_imgrep *rep1, mods_imgrep *rep2,
   std::vector<TentList> lists[2];
   lists[0].resize(1); lists[1].resize(1);
   if (fginn_ratio > 0 && (rc = match_into(c, rep1, rep2, fginn_ratio, par, &lists[0][0]))) return rc;
-  if (fginn_ratio_half > 0 && (rc = match_into(c, rep1h, rep2h, fginn_ratio_half, par, &lists[1][0]))) return rc;
+  if (fginn_ratio_half > 0 && (rc = match_into(c, rep1h, rep2h, fginn_ratio_half, par, &lists[1][0], 0, true))) return rc;
   gather_tentatives(c, lists);
   res->ms_match += now_ms() - t1;
   return verify_gathered(c, par, res, 0, 0);   // banks only: no image size (useF = 2 / 3 are refused)
@@ -586,7 +596,7 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
           if (a && a->n && (rc = mods_imgrep_append_dev(gb.q, a->reg, a->n))) return rc;
           if (b && b->n && (rc = mods_imgrep_append_dev(gb.t, b->reg, b->n))) return rc;
         }
-        if (ratio > 0 && (rc = match_into(c, gb.q, gb.t, ratio, par, &out))) return rc;
+        if (ratio > 0 && (rc = match_into(c, gb.q, gb.t, ratio, par, &out, 0, desc == 1))) return rc;   // (the joined HalfRootSIFT lists take the half slot)
         if (dist > 0 && (rc = match_into(c, gb.q, gb.t, 0, par, &out, dist))) return rc;
       }
     }
@@ -603,7 +613,7 @@ int mods_match_ladder_groups_dev(mods_ctx *c, const float *img1_dev, int w1, int
       if (st.fginn_ratio_half >= 0) {
         lists[1][slot_of(d)].clear();
         if (st.dist_threshold_half > 0 && pd[d].h1) { if ((rc = match_into(c, pd[d].h1, pd[d].h2, 0, par, &lists[1][slot_of(d)], st.dist_threshold_half))) return rc; }
-        else if (st.fginn_ratio_half > 0 && (rc = match_into(c, pd[d].h1, pd[d].h2, st.fginn_ratio_half, par, &lists[1][slot_of(d)]))) return rc;
+        else if (st.fginn_ratio_half > 0 && (rc = match_into(c, pd[d].h1, pd[d].h2, st.fginn_ratio_half, par, &lists[1][slot_of(d)], 0, true))) return rc;
       }
     }
     gather_tentatives(c, lists);

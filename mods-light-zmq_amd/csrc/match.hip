@@ -958,6 +958,7 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
   }
   const unsigned G = (unsigned)n_jobs;
   const size_t n = match_pad(ctx);
+  const mods_descdb *ddb = distractor_db_of(ctx);
   int8_t *qd = ctx->m_desc, *td = ctx->m_desc + n * 128;
   int *qc = ctx->m_c, *tc = ctx->m_c + n, *qc2 = ctx->m_c + 2 * n, *tc2 = ctx->m_c + 3 * n;
   unsigned int *qpar = (unsigned int *)(ctx->m_c + 4 * n), *tpar = qpar + n / 32 + 2;
@@ -993,13 +994,22 @@ int match_run_group(mods_ctx *ctx, int n_jobs, const mods_region *const *q_dev, 
     }
     // the mutual check (mods_ctx_match_mutual; mutual.hip) marks the accepted queries that fail it in bad[]
     if (ctx->mutual_mode && (rc = mutual_stage(ctx, J, k, max_q, n, ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qd, qc, qxy, td, tc))) return rc;
+    // the distractor database of this kind of search (mods_ctx_distractor_db; distractor.hip) marks the accepted queries it vetoes in
+    // bad[], and rewrites the survivors' ratios behind the emit kernels
+    if (ddb && (rc = distractor_stage(ctx, ddb, J, k, max_q, n, ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qd, qc))) return rc;
     int *block_counts = (int *)(ctx->m_int + 2 * n);
     hipLaunchKernelGGL(match_emit_count_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, block_counts);
     hipLaunchKernelGGL(match_emit_kernel, dim3(max_eb, G), dim3(EMIT_T), 0, ctx->stream, J, k, (const QueryMid *)ctx->m_mid.get(), key_ge, key_lt, n_lt, bad, qxy, txy,
                        block_counts, ctx->max_cand);
+    if (ddb && (rc = distractor_finish(ctx, J, max_q, n))) return rc;
   }
   MODS_HIP_CHECK(hipGetLastError());
-  if (n_jobs == 1 && count_out[0] == ctx->m_count.get() + count_slot()) ctx->mu_last_checked = ctx->mutual_mode && max_q > 0;
+  if (n_jobs == 1 && count_out[0] == ctx->m_count.get() + count_slot()) {
+    ctx->mu_last_checked = ctx->mutual_mode && max_q > 0;
+    ctx->dr_last_vetoed = ddb && max_q > 0;
+  } else if (ddb && max_q > 0) {
+    ctx->dr_last_vetoed = false;     // the veto of a batch's searches took the scratch of set 0: what the last single search left there is gone
+  }
   return MODS_OK;
 }
 
@@ -1066,6 +1076,7 @@ int match_run_distance(mods_ctx *ctx, const mods_region *q_dev, int n_q, const m
   if (k.max_distance < 0) { set_error("match: negative distance threshold"); return MODS_E_ARG; }
   MODS_HIP_CHECK(hipMemsetAsync(ctx->m_count, 0, sizeof(int), ctx->stream));
   ctx->mu_last_checked = false;      // (the distance matcher is never checked)
+  ctx->dr_last_vetoed = false;       // (... and never vetoed by a distractor database)
   if (n_q == 0 || n_t == 0) return MODS_OK;
   const size_t n = match_pad(ctx);
   int8_t *qd = ctx->m_desc, *td = ctx->m_desc + n * 128;

@@ -211,6 +211,16 @@ int mods_pipeline_match_mutual(mods_pipeline *p, int mode) {
   return MODS_OK;
 }
 
+// the whole-descriptor distractor database of every search of the pipeline (mods_ctx_distractor_db on the workers' contexts, each of
+// which takes a reference)
+int mods_pipeline_distractor_db(mods_pipeline *p, const mods_descdb *full) {
+  if (!p) { set_error("pipeline: null pipeline"); return MODS_E_ARG; }
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->submitted) { set_error("pipeline: distractor_db after the first submit"); return MODS_E_ARG; }
+  for (auto *c : p->ctxs) { const int rc = mods_ctx_distractor_db(c, full, nullptr); if (rc) return rc; }
+  return MODS_OK;
+}
+
 // which kernels of every description sample from which form of a batch's 8-bit images (mods_ctx_u8_kernels on the workers' contexts;
 // a mask with strip bits reserves the strip copy here, ahead of the first batch)
 int mods_pipeline_u8_kernels(mods_pipeline *p, int mask) {
