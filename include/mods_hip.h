@@ -150,6 +150,7 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_KNN_SWEEP,    /* the matrix-core kernel of that search alone (knn_sweep_kernel, i8 MFMA), inside MODS_STAGE_KNN */
        MODS_STAGE_DISTRACTOR,   /* the distractor-database veto of a search (mods_ctx_distractor_db): gather, sweep, fold and the ratio pass */
        MODS_STAGE_DISTRACTOR_SWEEP, /* the matrix-core kernel of that veto alone (descdb_sweep_kernel, i8 MFMA), inside MODS_STAGE_DISTRACTOR */
+       MODS_STAGE_REFINE,       /* the least-squares refinement of a correspondence list (mods_refine_matches[_dev]): its one kernel */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -1540,6 +1541,83 @@ int mods_draw_matches(mods_ctx *ctx, const mods_canvas *src1, const mods_canvas 
  * order of its matches_out: up to max rows x y a11 a12 a21 a22 s of region 1, then of region 2; *n = how many there are */
 int mods_ctx_verified_lafs(mods_ctx *ctx, double *laf14, int max, int *n);
 int mods_multi_verified_lafs(mods_multi *m, double *laf14, int max, int *n);
+
+/* ---- refinement of correspondences by affine least-squares matching -------------------------------------------
+ * Gruen, "Adaptive least squares correlation", 1985; the photometric refinement of Barath et al., "Making affine correspondences
+ * work in camera geometry computation", ECCV 2020.  No counterpart in the reference: this is the contract (csrc/refine.hip,
+ * restated in tests/lsm_ref.py).  The pixel window of one image is registered onto the other by an iterated Gauss-Newton fit of a
+ * translation and a 2 x 2 affinity with gain and offset; it yields a sub-pixel position, a refined frame and a ZNCC score per
+ * correspondence.  It never adds or removes a correspondence.  Every operation is fp64 on fp32 pixels, no contraction.
+ *
+ * Input: laf14[n][14] = x1 y1 a11 a12 a21 a22 s1 | x2 y2 b11 b12 b21 b22 s2, as mods_ctx_verified_lafs returns it.  Per row:
+ *   Roles      M1 = s1 A1, M2 = s2 A2 (entry by entry), d1 = det M1, d2 = det M2, B0 = M2 M1^-1 (M1^-1 = adj(M1) / d1, entry by entry,
+ *              as the local affine filter writes it), dB0 = det B0.  dB0 >= 1: image 1 is the template image (t), image 2 the
+ *              search image (s), B = B0.  Otherwise the roles are swapped and B = B0^-1 = adj(B0) / dB0.  So the window is taken at
+ *              native resolution where the region is smaller and is magnified into the other image.  BAD_FRAME: one of the 14
+ *              values is not finite, d1 == 0, d2 == 0, B0 or dB0 not finite, dB0 <= 0, or sqrt(det B) > max_magnification.
+ *   Sampling   bil(I, x, y): x0 = floor(x), fx = x - x0, y0 = floor(y), fy = y - y0; a = I[y0][x0], b = I[y0][x0+1], c = I[y0+1][x0],
+ *              d = I[y0+1][x0+1];  value = (a (1-fx) + b fx) (1-fy) + (c (1-fx) + d fx) fy;  gx = (b-a) (1-fy) + (d-c) fy;
+ *              gy = (c-a) (1-fx) + (d-b) fx.  A tap with x0 < 0, y0 < 0, x0 > w-2, y0 > h-2 (or a position that is not finite)
+ *              rejects the row with status OUTSIDE - in the template, in any iteration or in the final evaluation.
+ *   Window     S = (2R+1)^2 offsets u_k = (ux, uy), ux = k mod (2R+1) - R, uy = k div (2R+1) - R, k = 0 .. S-1.
+ *   Sums       every sum over the window is taken in one order: lane l = 0 .. 63 adds its terms k = l, l + 64, l + 128, ... in
+ *              ascending k to +0.0; then for o = 32, 16, 8, 4, 2, 1 every lane replaces its value by value + value of lane (l xor o).
+ *              All 64 lanes end with the same bits.  mean(X) = sum(X) / S.
+ *   Template   T_k = bil(I_t, c_t + u_k) (value only), T -= mean(T), Stt = sum(T T).  FLAT when Stt <= 1e-6 S.
+ *   Iteration  (c, B) start at (c_s, B).  p_k = (cx + (B00 ux + B01 uy), cy + (B10 ux + B11 uy)); W_k, gx_k, gy_k = bil(I_s, p_k);
+ *              columns q_0..5 = gx, gy, gx ux, gx uy, gy ux, gy uy; Wc = W - mean(W), d_j = q_j - mean(q_j);
+ *              Swt = sum(Wc T), Sww = sum(Wc Wc); gain a = Swt / Sww; zncc = Swt / sqrt(Sww Stt) (0 when Sww Stt is not > 0);
+ *              r = T - a Wc, J_j = a d_j; N_ij = sum(J_i J_j), g_i = sum(J_i r) for i, j < P (P = 6, or 2 with affine = 0);
+ *              tr = N_00 + .. + N_(P-1)(P-1) in that order; N_ii += lambda tr; delta = N^-1 g by Cholesky (N = L L^T, lower, column
+ *              by column; a pivot that is not > 0 - NaN included - is status FLAT), forward then backward substitution;
+ *              cx += delta_0, cy += delta_1, B00 += delta_2, B01 += delta_3, B10 += delta_4, B11 += delta_5.
+ *              Converged when sqrt(delta_0^2 + delta_1^2) < eps_shift; max_iter iterations without that: MAXITER, values kept.
+ *              iterations = the number of updates applied.  zncc_before = the zncc of the first iteration's sums.
+ *   End        zncc_after = the zncc at the returned (c, B) (one more sampling).  DIVERGED when not
+ *              sqrt((cx-csx)^2 + (cy-csy)^2) <= max_shift, or when q = sqrt(det B / det B_start) is not inside
+ *              [1 / max_scale_change, max_scale_change].  Else LOW_ZNCC when not zncc_after >= min_zncc.  Else MAXITER or OK.
+ *   Output     OK and MAXITER are accepted: the search side of the row gets the centre c and the frame M' = B M_t stored as
+ *              s' = sqrt(|det M'|), A' = M' / s'; the template side is untouched.  Every other row comes back as it went in; only
+ *              its status, its iteration count and the zncc values that were computed (others: 0) are written.
+ *              u6_out[n][6] = x1 y1 1 x2 y2 1 of laf_out.
+ * The result for a row depends only on that row and the two images: not on n, the row's place or the launch geometry.
+ *
+ * MODS_E_ARG with a mods_last_error text starting "refine_matches: ", before any device call: n < 0; radius outside 1 .. 15;
+ * max_iter outside 1 .. 1000; eps_shift, max_shift, lambda not finite or <= 0; max_scale_change, max_magnification not finite or
+ * < 1; min_zncc NaN or outside [-1, 1]; affine not 0 / 1; an image smaller than 2 x 2 or a stride below the width; a null context,
+ * image or (n > 0) laf14.  par == NULL: the defaults.  Any output may be null.  n == 0: MODS_OK, nothing is launched.
+ * The rows are staged in a buffer of the context's own; the matcher's "last search" and the guided / overlap buffers are left
+ * alone.  Timer: MODS_STAGE_REFINE.  mods_refine_matches: the same with host images (dense rows of stride floats), uploaded first.
+ * mods_refit_model: the least-squares model over all n rows of u6 (x1 y1 1 x2 y2 1) through the host fits of the LO steps -
+ * model_type 0: the normalised homography fit (u2h), returned row-major image 1 -> image 2 as mods_pair_result.H holds it, n >= 4;
+ * 1: the normalised 8-point fit with rank-2 projection (u2f), as mods_pair_result.H holds F, n >= 8.  No device, no RANSAC.
+ * mods_test_lsm_iteration: the first iteration of one row through the kernel: N (6 x 6, symmetric, the damped matrix; entries
+ * outside P x P are 0), g[6], the gain a and delta[6]; *status_out = BAD_FRAME / OUTSIDE / FLAT when the row ended before them. */
+enum { MODS_LSM_OK = 0, MODS_LSM_MAXITER = 1, MODS_LSM_BAD_FRAME = 2, MODS_LSM_OUTSIDE = 3, MODS_LSM_FLAT = 4, MODS_LSM_DIVERGED = 5,
+       MODS_LSM_LOW_ZNCC = 6, MODS_LSM_STATUS_COUNT };
+typedef struct mods_lsm_params {
+  int radius;                 /* 10    the window is (2 radius + 1)^2; 1 .. 15 */
+  int max_iter;               /* 20 */
+  double eps_shift;           /* 0.01  px of the search image */
+  double max_shift;           /* 3.0   px of the search image */
+  double max_scale_change;    /* 1.5 */
+  double max_magnification;   /* 8 */
+  double min_zncc;            /* 0.8 */
+  double lambda;              /* 1e-9  damping, relative to the trace */
+  int affine;                 /* 1; 0: translation only */
+  int pad;
+} mods_lsm_params;
+void mods_lsm_defaults(mods_lsm_params *par);
+int mods_refine_matches_dev(mods_ctx *ctx, const float *img1_dev, int w1, int h1, int stride1, const float *img2_dev, int w2, int h2,
+                            int stride2, const double *laf14, int n, const mods_lsm_params *par, double *laf_out, double *u6_out,
+                            int *status_out, int *iters_out, double *zncc_before_out, double *zncc_after_out);
+int mods_refine_matches(mods_ctx *ctx, const float *img1, int w1, int h1, int stride1, const float *img2, int w2, int h2,
+                        int stride2, const double *laf14, int n, const mods_lsm_params *par, double *laf_out, double *u6_out,
+                        int *status_out, int *iters_out, double *zncc_before_out, double *zncc_after_out);
+int mods_refit_model(const double *u6, int n, int model_type, double *model_out);
+int mods_test_lsm_iteration(mods_ctx *ctx, const float *img1, int w1, int h1, int stride1, const float *img2, int w2, int h2,
+                            int stride2, const double *laf14_row, const mods_lsm_params *par, double *N36, double *g6, double *a,
+                            double *delta6, int *status_out);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
 # MODS_STAGE_* added after that list was pinned by its users: their indices follow it
-STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep", "distractor", "distractor_sweep"]
+STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep", "distractor", "distractor_sweep", "refine"]
 
 
 def stage_index(name):
@@ -937,6 +937,18 @@ class Context:
         self.last_laf = laf[:n.value].copy()
         return out[:n.value].copy(), u6[:n.value].copy()
 
+    def refine_matches(self, img1, img2, laf, params=None):
+        """mods_refine_matches: the rows laf[n][14] refined by affine least-squares matching between the host images img1 and
+        img2 (2-D float32; rows may be strided).  Returns a dict: laf, u6, status, iterations, zncc_before, zncc_after"""
+        a, sa = _f32_rows(img1)
+        b, sb = _f32_rows(img2)
+        return _refine(lib().mods_refine_matches, self, (_vp(a), a.shape[1], a.shape[0], sa, _vp(b), b.shape[1], b.shape[0], sb), laf, params)
+
+    def refine_matches_dev(self, img1_ptr, w1, h1, stride1, img2_ptr, w2, h2, stride2, laf, params=None):
+        """mods_refine_matches_dev: as refine_matches on two fp32 images in device memory (strides in floats)"""
+        return _refine(lib().mods_refine_matches_dev, self, (C.c_void_p(img1_ptr), int(w1), int(h1), int(stride1), C.c_void_p(img2_ptr),
+                                                             int(w2), int(h2), int(stride2)), laf, params)
+
     def verified_lafs(self):
         """mods_ctx_verified_lafs: the frames [n][14] (x y a11 a12 a21 a22 s of region 1, then of region 2) of the verified
         correspondences of the last pair / ladder / verify call, in the order of its matches"""
@@ -985,6 +997,74 @@ class LocalAffineParams(C.Structure):
                 raise TypeError("LocalAffineParams has no field %r" % k)
             setattr(p, k, v)
         return p
+
+
+class LsmParams(C.Structure):
+    """mods_lsm_params (include/mods_hip.h): the least-squares refinement of correspondences"""
+    _fields_ = [("radius", C.c_int), ("max_iter", C.c_int), ("eps_shift", C.c_double), ("max_shift", C.c_double),
+                ("max_scale_change", C.c_double), ("max_magnification", C.c_double), ("min_zncc", C.c_double), ("lam", C.c_double),
+                ("affine", C.c_int), ("pad", C.c_int)]
+
+
+LSM_STATUS = ("OK", "MAXITER", "BAD_FRAME", "OUTSIDE", "FLAT", "DIVERGED", "LOW_ZNCC")
+
+
+def lsm_defaults(**kw):
+    """mods_lsm_defaults, with fields replaced by keyword (lam = the header's lambda)"""
+    p = LsmParams()
+    lib().mods_lsm_defaults.restype = None
+    lib().mods_lsm_defaults(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(LsmParams._fields_):
+            raise TypeError("LsmParams has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _f32_rows(img):
+    """a host image as the library takes it: (array that owns the pixels, row stride in floats)"""
+    a = np.asarray(img)
+    if a.dtype != np.float32 or a.ndim != 2 or a.size == 0:
+        raise ValueError("an image is a non-empty 2-D float32 array")
+    if a.strides[1] != 4 or a.strides[0] % 4 or a.strides[0] < 4 * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a, a.strides[0] // 4
+
+
+def _refine(fn, ctx, images, laf, params):
+    lf = np.ascontiguousarray(laf, np.float64).reshape(-1, 14)
+    n = len(lf)
+    out, u6 = np.zeros((max(n, 1), 14)), np.zeros((max(n, 1), 6))
+    st, it = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    zb, za = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    _check(fn(ctx.h if ctx is not None else None, *images, _vp(lf), n, C.byref(params) if params is not None else None,
+              _vp(out), _vp(u6), _vp(st), _vp(it), _vp(zb), _vp(za)))
+    return {"laf": out[:n], "u6": u6[:n], "status": st[:n], "iterations": it[:n], "zncc_before": zb[:n], "zncc_after": za[:n]}
+
+
+def refit_model(u6, model_type):
+    """mods_refit_model: the least-squares H (model_type 0, row-major, image 1 -> image 2) or F (1, as a pair result holds it) over
+    all rows x1 y1 1 x2 y2 1; no device needed"""
+    u = np.ascontiguousarray(u6, np.float64).reshape(-1, 6)
+    out = np.zeros(9)
+    _check(lib().mods_refit_model(_vp(u), len(u), int(model_type), _vp(out)))
+    return out
+
+
+def test_lsm_iteration(ctx, img1, img2, row, params=None):
+    """mods_test_lsm_iteration: (N[6][6], g[6], a, delta[6], status) of the first iteration of one row through the kernel"""
+    a, sa = _f32_rows(img1)
+    b, sb = _f32_rows(img2)
+    r = np.ascontiguousarray(row, np.float64).reshape(14)
+    N, g, d = np.zeros((6, 6)), np.zeros(6), np.zeros(6)
+    gain, st = C.c_double(), C.c_int()
+    _check(lib().mods_test_lsm_iteration(ctx.h if ctx is not None else None, _vp(a), a.shape[1], a.shape[0], sa, _vp(b), b.shape[1],
+                                         b.shape[0], sb, _vp(r), C.byref(params) if params is not None else None, _vp(N), _vp(g),
+                                         C.byref(gain), _vp(d), C.byref(st)))
+    return N, g, gain.value, d, st.value
+
+
+test_lsm_iteration.__test__ = False
 
 
 def local_affine_grid():

@@ -90,6 +90,11 @@ struct Config {
   // bank 1 (2: image 2 through inv(H) joins bank 2 as well) and the banks are matched and verified once more; every output
   // then comes from that pass
   int rematch = 0;
+  // [MatchRefinement] doRefinement (no counterpart in the reference): the verified correspondences are refined by affine least-squares
+  // matching on the two images (mods_refine_matches_dev), last of all; refitModel = 1: the H / F file then takes the least-squares
+  // model of the refined rows (mods_refit_model)
+  int refine = 0, refit_model = 1;
+  mods_lsm_params lsm_par;
   // [OverlapMatching] doOverlapMatch / overlapError (io_mods.cpp:685-687) and matchOriented (ours): with ver_type 1 every detector's
   // banks go through mods_match_overlap_reps under the ground-truth H and the count is printed as mods.cpp:522-523 does
   int overlap = 0, overlap_oriented = 1;
@@ -310,6 +315,24 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
     q.absTol = ini.GetDouble(sec, "absTol", q.absTol); q.relTol = ini.GetDouble(sec, "relTol", q.relTol);
     q.areaTol = ini.GetDouble(sec, "areaTol", q.areaTol); q.minSupport = (int)ini.GetInteger(sec, "minSupport", q.minSupport);
     q.rescue = (int)ini.GetInteger(sec, "rescue", q.rescue); q.keepSparse = (int)ini.GetInteger(sec, "keepSparse", q.keepSparse);
+  }
+  // [MatchRefinement]: the keys under the .ini's spelling; a value outside its range is an error here
+  {
+    const char *sec = "MatchRefinement";
+    mods_lsm_defaults(&cfg->lsm_par);
+    mods_lsm_params &q = cfg->lsm_par;
+    const long on = ini.GetInteger(sec, "doRefinement", 0), refit = ini.GetInteger(sec, "refitModel", 1);
+    const long radius = ini.GetInteger(sec, "radius", q.radius), max_iter = ini.GetInteger(sec, "maxIter", q.max_iter), affine = ini.GetInteger(sec, "affine", q.affine);
+    q.min_zncc = ini.GetDouble(sec, "minZNCC", q.min_zncc); q.max_shift = ini.GetDouble(sec, "maxShift", q.max_shift);
+    if (on != 0 && on != 1) { std::cerr << "[MatchRefinement] doRefinement must be 0 or 1" << std::endl; return 1; }
+    if (refit != 0 && refit != 1) { std::cerr << "[MatchRefinement] refitModel must be 0 or 1" << std::endl; return 1; }
+    if (radius < 1 || radius > 15) { std::cerr << "[MatchRefinement] radius must be 1 .. 15" << std::endl; return 1; }
+    if (max_iter < 1 || max_iter > 1000) { std::cerr << "[MatchRefinement] maxIter must be 1 .. 1000" << std::endl; return 1; }
+    if (affine != 0 && affine != 1) { std::cerr << "[MatchRefinement] affine must be 0 or 1" << std::endl; return 1; }
+    if (!(q.min_zncc >= -1 && q.min_zncc <= 1)) { std::cerr << "[MatchRefinement] minZNCC must be -1 .. 1" << std::endl; return 1; }
+    if (!std::isfinite(q.max_shift) || !(q.max_shift > 0)) { std::cerr << "[MatchRefinement] maxShift must be finite and > 0" << std::endl; return 1; }
+    cfg->refine = (int)on; cfg->refit_model = (int)refit;
+    q.radius = (int)radius; q.max_iter = (int)max_iter; q.affine = (int)affine;
   }
   if (ini.Has("zmqDescriptor", "port")) cfg->zmq_port = ini.GetString("zmqDescriptor", "port", "");
   cfg->zmq_mr = ini.GetDouble("zmqDescriptor", "mrSize", cfg->zmq_mr);
@@ -1093,6 +1116,45 @@ int main(int argc, char **argv) {
       }
     } else if (cfg.guided && cfg.verbose) std::cerr << "Guided matching: no verified model, skipped" << std::endl;
   }
+  // [MatchRefinement] doRefinement = 1: the verified list, refined on the two images the run holds on the device; last of all.  The
+  // rows of the matches file and the frames of the match images take the refined values (a rejected row stays as it was and
+  // stays in the file), the H / F file the refit model; no count changes
+  std::vector<double> refined_laf;
+  int lsm_status[MODS_LSM_STATUS_COUNT] = {0}, lsm_n = -1;
+  double lsm_zncc[2] = {0, 0};
+  bool lsm_refit = false;
+  if (cfg.refine) {
+    if (pre_extracted || multi) std::cerr << "Note: [MatchRefinement] is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
+    else if (ver_type != 0 && ver_type != 2) std::cerr << "Note: [MatchRefinement] is ignored unless RANSAC or ORSA verifies (verification type 0 or 2)" << std::endl;
+    else if (n_guided >= 0) std::cerr << "Note: [MatchRefinement] is ignored with guidedMatching (the matches file holds the guided list, not the verified one)" << std::endl;
+    else {
+      const int n = std::max(res.n_inliers, 0);
+      std::vector<double> laf((size_t)14 * (size_t)std::max(n, 1)), u6((size_t)6 * (size_t)std::max(n, 1)), zb((size_t)std::max(n, 1)), za((size_t)std::max(n, 1));
+      std::vector<int> st((size_t)std::max(n, 1));
+      int n_laf = 0;
+      if (mods_ctx_verified_lafs(ctx, laf.data(), n, &n_laf)) return fail("verified frames");
+      if (n_laf != n) { std::cerr << "[MatchRefinement] " << n_laf << " verified frames for " << n << " matches" << std::endl; return 1; }
+      refined_laf.resize((size_t)14 * (size_t)n);
+      if (mods_refine_matches_dev(ctx, (const float *)d1, img1.w, img1.h, img1.w, (const float *)d2, img2.w, img2.h, img2.w, laf.data(), n, &cfg.lsm_par,
+                                  refined_laf.data(), u6.data(), st.data(), nullptr, zb.data(), za.data()))
+        return fail("[MatchRefinement]");
+      lsm_n = n;
+      int n_z = 0;
+      for (int i = 0; i < n; i++) {
+        lsm_status[st[i]]++;
+        if (st[i] == MODS_LSM_OK || st[i] == MODS_LSM_MAXITER) { lsm_zncc[0] += zb[i]; lsm_zncc[1] += za[i]; n_z++; }
+        matches[4 * (size_t)i] = u6[6 * (size_t)i]; matches[4 * (size_t)i + 1] = u6[6 * (size_t)i + 1];
+        matches[4 * (size_t)i + 2] = u6[6 * (size_t)i + 3]; matches[4 * (size_t)i + 3] = u6[6 * (size_t)i + 4];
+      }
+      if (n_z) { lsm_zncc[0] /= n_z; lsm_zncc[1] /= n_z; }
+      if (cfg.refit_model && n >= (model_is_f ? 8 : 4)) {
+        double M[9];
+        if (mods_refit_model(u6.data(), n, model_is_f ? 1 : 0, M)) return fail("[MatchRefinement] refitModel");
+        for (int i = 0; i < 9; i++) res.H[i] = M[i];
+        lsm_refit = true;
+      }
+    }
+  }
   const int n_written = n_guided >= 0 ? n_guided_unique : res.n_inliers;
   const double final_time = now_s() - c_start;
   const int final_step = res.steps_done <= 0 ? 0 : (hessian_only && !pre_extracted && !multi) ? step_index[res.steps_done - 1] + 1 : res.steps_done;
@@ -1138,6 +1200,12 @@ int main(int argc, char **argv) {
     }
     if (rematch_before >= 0) std::cerr << "Rematch under H: +" << rematch_added[0] << " | +" << rematch_added[1] << " regions, " << rematch_before
                                        << " verified before, " << res.n_inliers << " after" << std::endl;
+    if (lsm_n >= 0) {
+      static const char *const names[MODS_LSM_STATUS_COUNT] = {"ok", "maxiter", "bad frame", "outside", "flat", "diverged", "low zncc"};
+      std::cerr << "Match refinement (radius " << cfg.lsm_par.radius << "): " << lsm_n << " correspondences:";
+      for (int i = 0; i < MODS_LSM_STATUS_COUNT; i++) std::cerr << " " << lsm_status[i] << " " << names[i] << (i + 1 < MODS_LSM_STATUS_COUNT ? "," : ";");
+      std::cerr << " mean zncc of the accepted " << lsm_zncc[0] << " before, " << lsm_zncc[1] << " after" << (lsm_refit ? "; model refit" : "") << std::endl;
+    }
     if (n_guided >= 0) std::cerr << "Guided matching (radius " << cfg.guided_radius << ", ratio " << cfg.guided_ratio << "): " << n_guided
                                  << " correspondences, " << n_guided_unique << " after duplicate filtering" << std::endl;
   }
@@ -1190,6 +1258,7 @@ int main(int argc, char **argv) {
       if (multi ? mods_multi_verified_lafs(multi, laf.data(), res.n_inliers, &n_laf) : mods_ctx_verified_lafs(ctx, laf.data(), res.n_inliers, &n_laf))
         return fail("verified frames");
       laf.resize((size_t)14 * (size_t)std::min(n_laf, std::max(res.n_inliers, 0)));
+      if (refined_laf.size() == laf.size()) laf = refined_laf;   // [MatchRefinement]: the images show the refined frames
       mods_draw_matches_params dp;
       memset(&dp, 0, sizeof(dp));
       dp.draw_only_centers = cfg.draw_only_centers;

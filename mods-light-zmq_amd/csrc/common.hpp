@@ -376,6 +376,10 @@ struct mods_ctx {
   mods::Buf<char> la_buf, la_io;
   mods::PinnedBuf<int> la_count;
   int la_n_in = 0, la_n_kept = 0;
+  // least-squares refinement of correspondences (refine.hip; mods_refine_matches[_dev]).  lsm_buf: the rows in and out, their
+  // statuses, iteration counts and zncc values (and the seam's 49 doubles); lsm_img: the two images of the host entry points
+  mods::Buf<char> lsm_buf;
+  mods::Buf<float> lsm_img;
   // detection masks (mods_ctx_detection_mask*; detection_mask.hpp, detect.hip): det_masks = what the caller set per image of a call
   // (det_mask_own: the context's copies of host masks), gate_tab_host / gate_tab_dev = the table the gate kernel reads, per image
   // slot, as the last call bound it (a view worker of the ladder binds its owner's masks: gate_owner, gate_image), gate_counts_dev =
