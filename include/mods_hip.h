@@ -151,6 +151,8 @@ enum { MODS_STAGE_BLUR = 0, MODS_STAGE_RESPONSE, MODS_STAGE_RESIZE, MODS_STAGE_N
        MODS_STAGE_DISTRACTOR,   /* the distractor-database veto of a search (mods_ctx_distractor_db): gather, sweep, fold and the ratio pass */
        MODS_STAGE_DISTRACTOR_SWEEP, /* the matrix-core kernel of that veto alone (descdb_sweep_kernel, i8 MFMA), inside MODS_STAGE_DISTRACTOR */
        MODS_STAGE_REFINE,       /* the least-squares refinement of a correspondence list (mods_refine_matches[_dev]): its one kernel */
+       MODS_STAGE_PROPAGATE,    /* a match propagation (mods_propagate_matches[_dev]): every launch of the call - the LSM launches of the
+                                   seeds and of each round, mark, propose, list and gate-and-append */
        MODS_STAGE_COUNT };
 int mods_ctx_timing_enable(mods_ctx *ctx, int stage_mask);
 /* on != 0: mods_detect_describe_dev (and what is built on it: the pair entry points, the pipeline's workers) records the ~70
@@ -1547,7 +1549,8 @@ int mods_multi_verified_lafs(mods_multi *m, double *laf14, int max, int *n);
  * work in camera geometry computation", ECCV 2020.  No counterpart in the reference: this is the contract (csrc/refine.hip,
  * restated in tests/lsm_ref.py).  The pixel window of one image is registered onto the other by an iterated Gauss-Newton fit of a
  * translation and a 2 x 2 affinity with gain and offset; it yields a sub-pixel position, a refined frame and a ZNCC score per
- * correspondence.  It never adds or removes a correspondence.  Every operation is fp64 on fp32 pixels, no contraction.
+ * correspondence.  It never adds or removes a correspondence (mods_propagate_matches below does).  Every operation is fp64 on fp32
+ * pixels, no contraction.
  *
  * Input: laf14[n][14] = x1 y1 a11 a12 a21 a22 s1 | x2 y2 b11 b12 b21 b22 s2, as mods_ctx_verified_lafs returns it.  Per row:
  *   Roles      M1 = s1 A1, M2 = s2 A2 (entry by entry), d1 = det M1, d2 = det M2, B0 = M2 M1^-1 (M1^-1 = adj(M1) / d1, entry by entry,
@@ -1618,6 +1621,84 @@ int mods_refit_model(const double *u6, int n, int model_type, double *model_out)
 int mods_test_lsm_iteration(mods_ctx *ctx, const float *img1, int w1, int h1, int stride1, const float *img2, int w2, int h2,
                             int stride2, const double *laf14_row, const mods_lsm_params *par, double *N36, double *g6, double *a,
                             double *delta6, int *status_out);
+
+/* ---- quasi-dense matches by propagation from refined correspondences -------------------------------------------
+ * Lhuillier and Quan, "Match propagation for image-based modeling and rendering", PAMI 2002; Kannala and Brandt, "Quasi-dense wide
+ * baseline matching using match propagation", CVPR 2007 (affine frames).  No counterpart in the reference: this is the contract
+ * (csrc/propagate.hip, restated in tests/propagate_ref.py).  A refined correspondence carries a local affine map of image 1 onto
+ * image 2; the map predicts where the neighbours of the point land, the least-squares matching above tests every prediction
+ * against the pixels, and the accepted ones predict their own neighbours in the next round.  Every operation is fp64 in the order
+ * written, no contraction; "LSM" is the contract of mods_refine_matches, row by row, with the parameters par->lsm.
+ *
+ * Lattice    image 1 is cut into Gx = floor(w1 / cell) by Gy = floor(h1 / cell) cells; cell (gx, gy) has the centre p = ((double)(gx
+ *            cell) + (cell - 1) * 0.5, (double)(gy cell) + (cell - 1) * 0.5).  A cell is free, occupied or closed; all start free.
+ * Round 0    every seed row goes through LSM unchanged; seed_status[n] = its status.  The seeds with status OK are the first front
+ *            (MAXITER does not propagate), in seed order.  A front row's own cell is (floor(x1 / cell), floor(y1 / cell)) of its
+ *            round-0 output row; where that lies inside the grid the cell becomes occupied (outside - the partial last column
+ *            or row - the row still proposes).  The seeds are not part of the output list.
+ * Round r    1 Propose.  Every front row k proposes every cell within `reach` (Chebyshev) of its own cell that is free and inside
+ * (1, 2, ..)   the grid.  With (dx, dy) = p - (x1, y1) of row k: d2 = (float)(dx dx + dy dy); among the proposers of a cell the
+ *              smallest (d2, k) wins, k = the place of the row in the front (the key: bits of d2 << 32 | k, unsigned 64-bit).
+ *            2 List.  The proposed cells in raster order (gy major) become the candidate rows of the round.  With the winner's
+ *              output row: M1, M2, d1 and B0 = M2 M1^-1 entry by entry as the LSM "Roles" paragraph writes them, dB = B0_00 B0_11 -
+ *              B0_01 B0_10, s = sqrt(dB), q = (x2 + (B0_00 dx + B0_01 dy), y2 + (B0_10 dx + B0_11 dy)) with (dx, dy) as above.
+ *              Candidate row = px py 1 0 0 1 1 | qx qy B0_00/s B0_01/s B0_10/s B0_11/s s.
+ *            3 Register.  The candidate rows go through LSM.
+ *            4 Gate.  A candidate is accepted when its status is OK and it passes the model test on its output row (x1, y1, x2,
+ *              y2); a row that fails the test ends with status MODS_PROP_OFF_MODEL.  model_type -1: no test.  Mij as the guided
+ *              matching above defines it; thr2 = model_thr model_thr.
+ *              0 (H): X = (M00 x1 + M01 y1) + M02, Y, W alike; W must be finite and not 0; ex = X / W - x2, ey = Y / W - y2; passes
+ *                when ex ex + ey ey <= thr2.
+ *              1 (F): l_i = (Mi0 x1 + Mi1 y1) + Mi2 for i = 0, 1, 2; m0 = (M00 x2 + M10 y2) + M20, m1 = (M01 x2 + M11 y2) + M21;
+ *                e = (l0 x2 + l1 y2) + l2; den = ((l0 l0 + l1 l1) + m0 m0) + m1 m1; passes when den != 0 and (e e) / den <= thr2
+ *                (Sampson).  A comparison with NaN fails.
+ *            5 State.  The cells of the accepted rows become occupied; their output rows, in raster order, are appended to the
+ *              output list and are the next front; their own cell is the proposed cell, wherever LSM moved x1.  Every other
+ *              proposed cell is closed for good.
+ * End        after `rounds` rounds, after a round that proposed nothing, or after a round that was cut: when the list would pass
+ *            max_out rows, the accepted rows of that round are taken in raster order up to max_out, *truncated = 1 (else 0) and
+ *            no further round runs.
+ * Outputs (any may be null): laf_out[max_out][14]; u6_out[max_out][6] = x1 y1 1 x2 y2 1; zncc_out = zncc_after; iters_out = the LSM
+ * iterations; round_out; cell_out[max_out][2] = gx gy of the row's own cell; parent_out = the winner in the combined list, 0 ..
+ * n - 1 a seed, n + j output row j; *n_out; seed_status[n]; stats[(rounds + 1)][MODS_PROP_STATUS_COUNT] = how many rows of each
+ * round (0: the seeds) ended in each status, rows beyond max_out included, rounds that did not run 0; tried_status[Gy][Gx] and
+ * tried_iters[Gy][Gx] = the status and the iteration count of the one candidate ever tried at a cell (-1: none).
+ * Nothing depends on launch geometry or timing; a repeated call returns the same bytes.
+ *
+ * MODS_E_ARG with a mods_last_error text starting "propagate_matches: ", before any device call: what mods_refine_matches refuses
+ * (for par->lsm, the images, n, laf14); cell outside 2 .. 64, reach outside 1 .. 4, rounds outside 1 .. 64; model_type outside
+ * -1 .. 1; with a model, an entry that is not finite or model_thr not finite or <= 0; max_out < 0; an image 1 smaller than one
+ * cell.  par == NULL: the defaults.  n == 0: MODS_OK, nothing is launched, *n_out = 0, *truncated = 0, stats and the tried maps are
+ * not written.  Grid, rows and images live in buffers of the context's own, grown on demand: the matcher's "last search" and the
+ * guided / overlap / k-NN / refine buffers are left alone.  The host waits for the device once per round that runs (for the number
+ * of candidates) and once at the end; a buffer that has to grow waits once more (the early rounds of a context's first call), and
+ * mods_propagate_matches waits for its image upload.  Timer: MODS_STAGE_PROPAGATE (every launch of the call, the LSM launches included).
+ * mods_test_propagate_round: one Propose and List pass.  front_laf[nf][14] = the front's output rows; front_cell[nf][2] = their own
+ * cells (null: floor(x1 / cell), floor(y1 / cell)); state[Gy][Gx] = 0 free, 1 occupied, 2 closed (null: all free).  winner_out[Gy][Gx]
+ * (-1: not proposed), key_out[Gy][Gx] (all ones: not proposed), cand_cell_out[n_cand] = gy Gx + gx in list order, cand_laf_out[n_cand][14];
+ * the last two hold up to Gx Gy rows. */
+enum { MODS_PROP_OFF_MODEL = MODS_LSM_STATUS_COUNT, MODS_PROP_STATUS_COUNT };
+typedef struct mods_propagate_params {
+  int cell;                   /* 4     px of image 1; 2 .. 64 */
+  int reach;                  /* 1     cells, Chebyshev; 1 .. 4 */
+  int rounds;                 /* 8     1 .. 64 */
+  int model_type;             /* -1    -1 none, 0 H, 1 F, as mods_pair_result.H delivers them */
+  mods_lsm_params lsm;        /* mods_lsm_defaults with radius 5 */
+  double model[9];
+  double model_thr;           /* 2.0   px (H) / px of the Sampson distance (F) */
+} mods_propagate_params;
+void mods_propagate_defaults(mods_propagate_params *par);
+int mods_propagate_matches_dev(mods_ctx *ctx, const float *img1_dev, int w1, int h1, int stride1, const float *img2_dev, int w2, int h2,
+                               int stride2, const double *laf14, int n, const mods_propagate_params *par, int max_out, double *laf_out,
+                               double *u6_out, double *zncc_out, int *iters_out, int *round_out, int *cell_out, int *parent_out,
+                               int *n_out, int *truncated, int *seed_status, int *stats, int *tried_status, int *tried_iters);
+int mods_propagate_matches(mods_ctx *ctx, const float *img1, int w1, int h1, int stride1, const float *img2, int w2, int h2,
+                           int stride2, const double *laf14, int n, const mods_propagate_params *par, int max_out, double *laf_out,
+                           double *u6_out, double *zncc_out, int *iters_out, int *round_out, int *cell_out, int *parent_out,
+                           int *n_out, int *truncated, int *seed_status, int *stats, int *tried_status, int *tried_iters);
+int mods_test_propagate_round(mods_ctx *ctx, int w1, int h1, int cell, int reach, const double *front_laf, const int *front_cell, int nf,
+                              const unsigned char *state, int *winner_out, unsigned long long *key_out, int *cand_cell_out,
+                              double *cand_laf_out, int *n_cand_out);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,7 @@ STAGES = ["blur", "response", "resize", "nms", "localize", "baumberg", "sort", "
           "ransac_score", "synth", "blur_small", "pyramid", "match_nn1", "extract", "sift", "guided", "match_mutual",
           "overlap", "overlap_area"]
 # MODS_STAGE_* added after that list was pinned by its users: their indices follow it
-STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep", "distractor", "distractor_sweep", "refine"]
+STAGES_LATER = ["local_affine", "reproject_h", "spatial_select", "knn", "knn_sweep", "distractor", "distractor_sweep", "refine", "propagate"]
 
 
 def stage_index(name):
@@ -949,6 +949,21 @@ class Context:
         return _refine(lib().mods_refine_matches_dev, self, (C.c_void_p(img1_ptr), int(w1), int(h1), int(stride1), C.c_void_p(img2_ptr),
                                                              int(w2), int(h2), int(stride2)), laf, params)
 
+    def propagate_matches(self, img1, img2, laf, params=None, max_out=None):
+        """mods_propagate_matches: the seed rows laf[n][14] grown into quasi-dense correspondences by match propagation between the
+        host images img1 and img2 (2-D float32; rows may be strided).  max_out: the most rows returned (default: one per cell).
+        Returns a dict: laf, u6, zncc, iterations, round, cell, parent, truncated, seed_status, stats[rounds + 1][8],
+        tried_status[Gy][Gx], tried_iterations[Gy][Gx]"""
+        a, sa = _f32_rows(img1)
+        b, sb = _f32_rows(img2)
+        return _propagate(lib().mods_propagate_matches, self, (_vp(a), a.shape[1], a.shape[0], sa, _vp(b), b.shape[1], b.shape[0], sb), laf, params,
+                          max_out)
+
+    def propagate_matches_dev(self, img1_ptr, w1, h1, stride1, img2_ptr, w2, h2, stride2, laf, params=None, max_out=None):
+        """mods_propagate_matches_dev: as propagate_matches on two fp32 images in device memory (strides in floats)"""
+        return _propagate(lib().mods_propagate_matches_dev, self, (C.c_void_p(img1_ptr), int(w1), int(h1), int(stride1), C.c_void_p(img2_ptr),
+                                                                   int(w2), int(h2), int(stride2)), laf, params, max_out)
+
     def verified_lafs(self):
         """mods_ctx_verified_lafs: the frames [n][14] (x y a11 a12 a21 a22 s of region 1, then of region 2) of the verified
         correspondences of the last pair / ladder / verify call, in the order of its matches"""
@@ -1040,6 +1055,75 @@ def _refine(fn, ctx, images, laf, params):
     _check(fn(ctx.h if ctx is not None else None, *images, _vp(lf), n, C.byref(params) if params is not None else None,
               _vp(out), _vp(u6), _vp(st), _vp(it), _vp(zb), _vp(za)))
     return {"laf": out[:n], "u6": u6[:n], "status": st[:n], "iterations": it[:n], "zncc_before": zb[:n], "zncc_after": za[:n]}
+
+
+class PropagateParams(C.Structure):
+    """mods_propagate_params (include/mods_hip.h): match propagation from refined correspondences"""
+    _fields_ = [("cell", C.c_int), ("reach", C.c_int), ("rounds", C.c_int), ("model_type", C.c_int), ("lsm", LsmParams),
+                ("model", C.c_double * 9), ("model_thr", C.c_double)]
+
+
+PROP_STATUS = LSM_STATUS + ("OFF_MODEL",)
+
+
+def propagate_defaults(**kw):
+    """mods_propagate_defaults, with fields replaced by keyword: cell, reach, rounds, model_type, model (9 values), model_thr, lsm
+    (an LsmParams), or a field of LsmParams (radius, min_zncc, ...) for the nested structure"""
+    p = PropagateParams()
+    lib().mods_propagate_defaults.restype = None
+    lib().mods_propagate_defaults(C.byref(p))
+    own, nested = dict(PropagateParams._fields_), dict(LsmParams._fields_)
+    for k, v in kw.items():
+        if k == "model":
+            p.model = (C.c_double * 9)(*[float(x) for x in np.asarray(v, np.float64).reshape(9)])
+        elif k in own:
+            setattr(p, k, v)
+        elif k in nested:
+            setattr(p.lsm, k, v)
+        else:
+            raise TypeError("PropagateParams has no field %r" % k)
+    return p
+
+
+def _propagate(fn, ctx, images, laf, params, max_out):
+    lf = np.ascontiguousarray(laf, np.float64).reshape(-1, 14)
+    n = len(lf)
+    par = params if params is not None else propagate_defaults()
+    w1, h1 = images[1], images[2]
+    gx, gy = max(w1 // max(par.cell, 1), 1), max(h1 // max(par.cell, 1), 1)
+    cap = gx * gy if max_out is None else int(max_out)
+    room = max(cap, 1)
+    out, u6, z = np.zeros((room, 14)), np.zeros((room, 6)), np.zeros(room)
+    it, rnd, par_ = np.zeros(room, np.int32), np.zeros(room, np.int32), np.zeros(room, np.int32)
+    cell = np.zeros((room, 2), np.int32)
+    n_out, trunc = C.c_int(0), C.c_int(0)
+    seed = np.zeros(max(n, 1), np.int32)
+    stats = np.zeros((max(par.rounds, 0) + 1, len(PROP_STATUS)), np.int32)
+    ts, ti = np.full((gy, gx), -1, np.int32), np.full((gy, gx), -1, np.int32)
+    _check(fn(ctx.h if ctx is not None else None, *images, _vp(lf), n, C.byref(params) if params is not None else None, cap, _vp(out), _vp(u6),
+              _vp(z), _vp(it), _vp(rnd), _vp(cell), _vp(par_), C.byref(n_out), C.byref(trunc), _vp(seed), _vp(stats), _vp(ts), _vp(ti)))
+    m = n_out.value
+    return {"laf": out[:m], "u6": u6[:m], "zncc": z[:m], "iterations": it[:m], "round": rnd[:m], "cell": cell[:m], "parent": par_[:m],
+            "truncated": bool(trunc.value), "seed_status": seed[:n], "stats": stats, "tried_status": ts, "tried_iterations": ti}
+
+
+def test_propagate_round(ctx, w1, h1, cell, reach, front_laf, front_cell=None, state=None):
+    """mods_test_propagate_round: one proposal and list pass.  Returns (winner[Gy][Gx], key[Gy][Gx], cand_cell[n_cand],
+    cand_laf[n_cand][14])"""
+    f = np.ascontiguousarray(front_laf, np.float64).reshape(-1, 14)
+    gx, gy = max(int(w1) // max(int(cell), 1), 1), max(int(h1) // max(int(cell), 1), 1)
+    fc = np.ascontiguousarray(front_cell, np.int32).reshape(-1, 2) if front_cell is not None else None
+    st = np.ascontiguousarray(state, np.uint8).reshape(gy, gx) if state is not None else None
+    win, key = np.full((gy, gx), -1, np.int32), np.zeros((gy, gx), np.uint64)
+    cc, cl = np.zeros(gx * gy, np.int32), np.zeros((gx * gy, 14))
+    n = C.c_int(0)
+    _check(lib().mods_test_propagate_round(ctx.h if ctx is not None else None, int(w1), int(h1), int(cell), int(reach), _vp(f),
+                                           _vp(fc) if fc is not None else None, len(f), _vp(st) if st is not None else None, _vp(win), _vp(key),
+                                           _vp(cc), _vp(cl), C.byref(n)))
+    return win, key, cc[:n.value], cl[:n.value]
+
+
+test_propagate_round.__test__ = False
 
 
 def refit_model(u6, model_type):

@@ -95,6 +95,14 @@ struct Config {
   // model of the refined rows (mods_refit_model)
   int refine = 0, refit_model = 1;
   mods_lsm_params lsm_par;
+  // [MatchPropagation] doPropagation (no counterpart in the reference): the verified correspondences (the refined ones with
+  // [MatchRefinement]) grow into quasi-dense ones by match propagation on the two images (mods_propagate_matches_dev), after
+  // everything else; useModel = 1: under the model that goes to the H / F file, within modelThreshold (default: [RANSAC]
+  // err_threshold).  `output` receives them; the matches file, the log and every count stay as they are
+  int propagate = 0, prop_use_model = 1;
+  bool prop_thr_set = false;
+  mods_propagate_params prop_par;
+  std::string prop_output;
   // [OverlapMatching] doOverlapMatch / overlapError (io_mods.cpp:685-687) and matchOriented (ours): with ver_type 1 every detector's
   // banks go through mods_match_overlap_reps under the ground-truth H and the count is printed as mods.cpp:522-523 does
   int overlap = 0, overlap_oriented = 1;
@@ -333,6 +341,31 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
     if (!std::isfinite(q.max_shift) || !(q.max_shift > 0)) { std::cerr << "[MatchRefinement] maxShift must be finite and > 0" << std::endl; return 1; }
     cfg->refine = (int)on; cfg->refit_model = (int)refit;
     q.radius = (int)radius; q.max_iter = (int)max_iter; q.affine = (int)affine;
+  }
+  // [MatchPropagation]: as above
+  {
+    const char *sec = "MatchPropagation";
+    mods_propagate_defaults(&cfg->prop_par);
+    mods_propagate_params &q = cfg->prop_par;
+    const long on = ini.GetInteger(sec, "doPropagation", 0), use_model = ini.GetInteger(sec, "useModel", 1);
+    const long cell = ini.GetInteger(sec, "cell", q.cell), reach = ini.GetInteger(sec, "reach", q.reach), rounds = ini.GetInteger(sec, "rounds", q.rounds);
+    const long radius = ini.GetInteger(sec, "radius", q.lsm.radius);
+    q.lsm.min_zncc = ini.GetDouble(sec, "minZNCC", q.lsm.min_zncc); q.lsm.max_shift = ini.GetDouble(sec, "maxShift", q.lsm.max_shift);
+    cfg->prop_thr_set = ini.Has(sec, "modelThreshold");
+    q.model_thr = ini.GetDouble(sec, "modelThreshold", q.model_thr);
+    cfg->prop_output = ini.GetString(sec, "output", "");
+    if (on != 0 && on != 1) { std::cerr << "[MatchPropagation] doPropagation must be 0 or 1" << std::endl; return 1; }
+    if (use_model != 0 && use_model != 1) { std::cerr << "[MatchPropagation] useModel must be 0 or 1" << std::endl; return 1; }
+    if (cell < 2 || cell > 64) { std::cerr << "[MatchPropagation] cell must be 2 .. 64" << std::endl; return 1; }
+    if (reach < 1 || reach > 4) { std::cerr << "[MatchPropagation] reach must be 1 .. 4" << std::endl; return 1; }
+    if (rounds < 1 || rounds > 64) { std::cerr << "[MatchPropagation] rounds must be 1 .. 64" << std::endl; return 1; }
+    if (radius < 1 || radius > 15) { std::cerr << "[MatchPropagation] radius must be 1 .. 15" << std::endl; return 1; }
+    if (!(q.lsm.min_zncc >= -1 && q.lsm.min_zncc <= 1)) { std::cerr << "[MatchPropagation] minZNCC must be -1 .. 1" << std::endl; return 1; }
+    if (!std::isfinite(q.lsm.max_shift) || !(q.lsm.max_shift > 0)) { std::cerr << "[MatchPropagation] maxShift must be finite and > 0" << std::endl; return 1; }
+    if (!std::isfinite(q.model_thr) || !(q.model_thr > 0)) { std::cerr << "[MatchPropagation] modelThreshold must be finite and > 0" << std::endl; return 1; }
+    if (on && cfg->prop_output.empty()) { std::cerr << "[MatchPropagation] doPropagation = 1 needs output = FILE" << std::endl; return 1; }
+    cfg->propagate = (int)on; cfg->prop_use_model = (int)use_model;
+    q.cell = (int)cell; q.reach = (int)reach; q.rounds = (int)rounds; q.lsm.radius = (int)radius;
   }
   if (ini.Has("zmqDescriptor", "port")) cfg->zmq_port = ini.GetString("zmqDescriptor", "port", "");
   cfg->zmq_mr = ini.GetDouble("zmqDescriptor", "mrSize", cfg->zmq_mr);
@@ -1155,6 +1188,53 @@ int main(int argc, char **argv) {
       }
     }
   }
+  // [MatchPropagation] doPropagation = 1: after everything else, from the verified frames (the refined ones when the refinement
+  // ran) under the model that goes to the H / F file; its rows go to a file of their own and nothing else changes
+  std::vector<double> prop_rows;        // x1 y1 x2 y2 zncc round
+  std::vector<int> prop_stats;
+  int prop_n = -1, prop_trunc = 0;
+  if (cfg.propagate) {
+    if (pre_extracted || multi) std::cerr << "Note: [MatchPropagation] is ignored in pre-extracted mode and with MODS_DEVICES" << std::endl;
+    else if (ver_type != 0 && ver_type != 2) std::cerr << "Note: [MatchPropagation] is ignored unless RANSAC or ORSA verifies (verification type 0 or 2)" << std::endl;
+    else if (n_guided >= 0) std::cerr << "Note: [MatchPropagation] is ignored with guidedMatching (the verified list is not what the run ends with)" << std::endl;
+    else {
+      const int n = std::max(res.n_inliers, 0);
+      std::vector<double> laf((size_t)14 * (size_t)std::max(n, 1));
+      if (refined_laf.size() == (size_t)14 * (size_t)n && n > 0) laf = refined_laf;
+      else {
+        int n_laf = 0;
+        if (mods_ctx_verified_lafs(ctx, laf.data(), n, &n_laf)) return fail("verified frames");
+        if (n_laf != n) { std::cerr << "[MatchPropagation] " << n_laf << " verified frames for " << n << " matches" << std::endl; return 1; }
+      }
+      mods_propagate_params pp = cfg.prop_par;
+      if (!cfg.prop_thr_set) pp.model_thr = cfg.pair.ransac.err_threshold;
+      pp.model_type = -1;
+      if (cfg.prop_use_model && n > 0) {
+        pp.model_type = model_is_f ? 1 : 0;
+        for (int i = 0; i < 9; i++) {   // the model as the H / F file will hold it: through the stream's digits
+          std::ostringstream os;
+          os << res.H[i];
+          pp.model[i] = strtod(os.str().c_str(), nullptr);
+        }
+      }
+      const size_t cap = (size_t)(img1.w / pp.cell) * (size_t)(img1.h / pp.cell);
+      if (cap == 0 || cap > (size_t)1 << 28) { std::cerr << "[MatchPropagation] image 1 of " << img1.w << " x " << img1.h << " and cell " << pp.cell << std::endl; return 1; }
+      std::vector<double> u6(6 * cap), z(cap);
+      std::vector<int> rnd(cap);
+      prop_stats.assign((size_t)(pp.rounds + 1) * MODS_PROP_STATUS_COUNT, 0);
+      int m = 0;
+      if (mods_propagate_matches_dev(ctx, (const float *)d1, img1.w, img1.h, img1.w, (const float *)d2, img2.w, img2.h, img2.w, laf.data(), n, &pp, (int)cap,
+                                     nullptr, u6.data(), z.data(), nullptr, rnd.data(), nullptr, nullptr, &m, &prop_trunc, nullptr, prop_stats.data(), nullptr,
+                                     nullptr))
+        return fail("[MatchPropagation]");
+      prop_n = m;
+      prop_rows.resize((size_t)6 * (size_t)m);
+      for (int i = 0; i < m; i++) {
+        double *r = &prop_rows[6 * (size_t)i];
+        r[0] = u6[6 * (size_t)i]; r[1] = u6[6 * (size_t)i + 1]; r[2] = u6[6 * (size_t)i + 3]; r[3] = u6[6 * (size_t)i + 4]; r[4] = z[i]; r[5] = rnd[i];
+      }
+    }
+  }
   const int n_written = n_guided >= 0 ? n_guided_unique : res.n_inliers;
   const double final_time = now_s() - c_start;
   const int final_step = res.steps_done <= 0 ? 0 : (hessian_only && !pre_extracted && !multi) ? step_index[res.steps_done - 1] + 1 : res.steps_done;
@@ -1206,6 +1286,16 @@ int main(int argc, char **argv) {
       for (int i = 0; i < MODS_LSM_STATUS_COUNT; i++) std::cerr << " " << lsm_status[i] << " " << names[i] << (i + 1 < MODS_LSM_STATUS_COUNT ? "," : ";");
       std::cerr << " mean zncc of the accepted " << lsm_zncc[0] << " before, " << lsm_zncc[1] << " after" << (lsm_refit ? "; model refit" : "") << std::endl;
     }
+    if (prop_n >= 0) {
+      std::cerr << "Match propagation (cell " << cfg.prop_par.cell << ", reach " << cfg.prop_par.reach << ", radius " << cfg.prop_par.lsm.radius << "): "
+                << prop_n << " correspondences" << (prop_trunc ? " (cut)" : "") << std::endl;
+      for (int r = 0; r <= cfg.prop_par.rounds; r++) {
+        int tried = 0;
+        for (int q = 0; q < MODS_PROP_STATUS_COUNT; q++) tried += prop_stats[(size_t)r * MODS_PROP_STATUS_COUNT + q];
+        if (r > 0 && tried == 0) break;
+        std::cerr << "  round " << r << ": " << tried << " rows tried, " << prop_stats[(size_t)r * MODS_PROP_STATUS_COUNT + MODS_LSM_OK] << " accepted" << std::endl;
+      }
+    }
     if (n_guided >= 0) std::cerr << "Guided matching (radius " << cfg.guided_radius << ", ratio " << cfg.guided_ratio << "): " << n_guided
                                  << " correspondences, " << n_guided_unique << " after duplicate filtering" << std::endl;
   }
@@ -1237,6 +1327,15 @@ int main(int argc, char **argv) {
     if (hf.is_open())
       hf << res.H[0] << " " << res.H[1] << " " << res.H[2] << std::endl << res.H[3] << " " << res.H[4] << " " << res.H[5] << std::endl
          << res.H[6] << " " << res.H[7] << " " << res.H[8] << std::endl;
+  }
+  if (prop_n >= 0) {   // [MatchPropagation] output
+    std::ofstream pf(cfg.prop_output);
+    if (!pf.is_open()) { std::cerr << "[MatchPropagation] cannot write " << cfg.prop_output << std::endl; return 1; }
+    pf.precision(10);
+    for (int i = 0; i < prop_n; i++) {
+      const double *r = &prop_rows[6 * (size_t)i];
+      pf << r[0] << " " << r[1] << " " << r[2] << " " << r[3] << " " << r[4] << " " << (int)r[5] << std::endl;
+    }
   }
   if (!log_only) {
     if (cfg.write_matches) {

@@ -380,6 +380,13 @@ struct mods_ctx {
   // statuses, iteration counts and zncc values (and the seam's 49 doubles); lsm_img: the two images of the host entry points
   mods::Buf<char> lsm_buf;
   mods::Buf<float> lsm_img;
+  // match propagation (propagate.hip; mods_propagate_matches[_dev]).  prop_grid: per cell the state, the proposal key and the tried
+  // maps, then the scan's block sums, the counters and the statistics; prop_seed: the seed rows in and out; prop_cand: the candidate
+  // rows of a round in and out; prop_out: the output list (the front of the next round is its tail); prop_img: the two images of the
+  // host entry point; prop_ctr: the counters the host reads, pinned
+  mods::Buf<char> prop_grid, prop_seed, prop_cand, prop_out;
+  mods::Buf<float> prop_img;
+  mods::PinnedBuf<int> prop_ctr;
   // detection masks (mods_ctx_detection_mask*; detection_mask.hpp, detect.hip): det_masks = what the caller set per image of a call
   // (det_mask_own: the context's copies of host masks), gate_tab_host / gate_tab_dev = the table the gate kernel reads, per image
   // slot, as the last call bound it (a view worker of the ladder binds its owner's masks: gate_owner, gate_image), gate_counts_dev =
