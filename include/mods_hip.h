@@ -333,6 +333,25 @@ int mods_ctx_set_external_orientation(mods_ctx *ctx, mods_descriptor_fn fn, void
 typedef struct mods_net mods_net;
 enum { MODS_NET_AFFNET = 0, MODS_NET_ORINET = 1, MODS_NET_HARDNET = 2 };
 int  mods_net_create(int device, int kind, const float *const *tensors, const size_t *n_floats, int n_tensors, mods_net **out);
+/* Precision of a network, chosen at creation.  MODS_NET_FP32 is the mode described above and what mods_net_create makes.
+ * MODS_NET_BF16 ("bf16 mode") runs the bulk of the arithmetic on the matrix cores with bf16 operands; its outputs differ from the
+ * fp32 mode's.  The arithmetic contract, with bf16(x) = the fp32 value x rounded to the nearest bf16, ties to even (inputs finite
+ * and normal):
+ *   - stage 0 (input normalisation) and stage 1 (conv 1 -> C, K = 9) compute what the fp32 mode computes, with the same arithmetic;
+ *   - activations are stored as bf16 on leaving stages 1..6: bf16(relu(acc + bias)); stage 1's output is bf16(the fp32 mode's
+ *     stage-1 output) to the bit;
+ *   - the weights of stages 2..6 of all three networks and of HardNet's head are the fp32 mode's folded weights rounded once more:
+ *     bf16((float)((double)W * inv)), inv = 1.0 / sqrt((double)var + 1e-5); the folded bias stays fp32.  Products are
+ *     bf16 x bf16 (exact in fp32), accumulated in fp32 on the matrix cores; the bias is added in fp32 after the last k-step;
+ *   - the order of every sum is fixed by the architecture and the kernel's tiling alone: a patch's output does not depend on the
+ *     number of patches in the call, on their order or on the chunking;
+ *   - the heads of AffNet and OriNet keep their fp32 weights and the fp32 mode's arithmetic on the bf16 activations widened to
+ *     fp32 (exact); HardNet's tail behind the head GEMM is unchanged: + bias, L2 normalisation, trunc(clip(210 (y + 0.45))).
+ * An unknown precision is MODS_E_ARG (checked with the other arguments, before the device is looked for).  Either kind of network
+ * is immutable and shareable, and is taken by mods_net_forward[_dev] and mods_ctx_set_builtin_*. */
+enum { MODS_NET_FP32 = 0, MODS_NET_BF16 = 1 };
+int  mods_net_create_ex(int device, int kind, const float *const *tensors, const size_t *n_floats, int n_tensors, int precision, mods_net **out);
+int  mods_net_precision(const mods_net *net);                 /* MODS_NET_FP32 or MODS_NET_BF16 */
 void mods_net_destroy(mods_net *net);
 int  mods_net_dim(const mods_net *net);                       /* 3, 2, 128 */
 int  mods_net_chunk(void);                                    /* patches per set of launches (a call of more is cut into chunks) */
@@ -351,8 +370,13 @@ int  mods_ctx_set_builtin_descriptor(mods_ctx *ctx, mods_net *net, double mrSize
  * blocks ([n][cin][h][h] -> [n][cout][h / stride][h / stride]; channels C, C, 2C, 2C, 4C, 4C with C = 16 or 32 (HardNet), maps of
  * 32, 32, 16, 16, 8, 8 pixels a side at the output), 7 = the head ([n][4C * 64] -> [n][dim]).  1 <= n <= mods_net_chunk().  The
  * device output has one more patch's worth of elements behind it, filled with a sentinel before the launch; *guard_ok = 1 when
- * the stage left them alone. */
+ * the stage left them alone.  On a bf16 network the shapes are the same: the host input of stages 2..7 is rounded to bf16 on its way
+ * in, the output of stages 1..6 (bf16 on the device, with a bf16 guard) comes back widened to fp32. */
 int  mods_test_net_stage(mods_net *net, int stage, const float *in_host, int n, int quantise_u8, float *out_host, int *guard_ok);
+/* timing hook: mods_net_forward_dev with a device event in front of every launch; waits for the stream, then stage_ms[0..7] = the
+ * time between the events around stage 0..7, summed over the chunks of the call (tools/bench_nets_bf16.py).  It creates, records
+ * and destroys 8 events per chunk and one more, and synchronises the stream: not for a stream that is being captured into a graph. */
+int  mods_test_net_stage_times(mods_net *net, void *hip_stream, const float *patches_dev, int n, int quantise_u8, float *out_dev, float *stage_ms);
 int mods_patches_fetch(mods_ctx *ctx, int img, int ps, float *out, int max_regions, int *n_out);   /* patches of the last describe call */
 /* Baumberg work counters of image slot img (bench.py's per-keypoint figures): keypoints that entered the affine-shape iteration and
  * iterations run since mods_baumberg_stats_enable(ctx, 1); one iteration = smmWindowSize^2 bilinear taps (affine.cpp:26-158). */

@@ -231,6 +231,7 @@ class ClaheParams(C.Structure):
 
 NET_KINDS = {"affnet": 0, "orinet": 1, "hardnet": 2}
 NET_DIMS = {"affnet": 3, "orinet": 2, "hardnet": 128}
+NET_PRECISIONS = {"fp32": 0, "bf16": 1}          # MODS_NET_FP32, MODS_NET_BF16
 _NET_SLOTS = {"shape": "affnet", "orientation": "orinet", "descriptor": "hardnet"}
 
 
@@ -284,15 +285,19 @@ def net_chunk():
 
 class Net:
     """AffNet / OriNet / HardNet as HIP kernels (mods_net_*): kind "affnet" | "orinet" | "hardnet", state = the tensors by the
-    names of the daemon's state dict.  Immutable; several contexts and threads may use one Net."""
+    names of the daemon's state dict.  Immutable; several contexts and threads may use one Net.
+    precision "fp32" (the default) | "bf16": the bf16 mode runs the convolutions behind the first and HardNet's head on the matrix
+    cores with bf16 operands and fp32 accumulators (the contract is in include/mods_hip.h); its outputs differ from fp32's."""
 
-    def __init__(self, kind, state, device=0):
+    def __init__(self, kind, state, device=0, precision="fp32"):
         self.h = C.c_void_p()
         tensors = net_tensors(kind, state)                     # raises before any device call
-        self.kind, self.dim, self.device = kind, NET_DIMS[kind], device
+        if precision not in NET_PRECISIONS:
+            raise ModsError("Net: precision %r, one of %s expected" % (precision, " | ".join(map(repr, NET_PRECISIONS))))
+        self.kind, self.dim, self.device, self.precision = kind, NET_DIMS[kind], device, precision
         ptrs = (C.POINTER(C.c_float) * len(tensors))(*[_fp(t) for t in tensors])
         sizes = (C.c_size_t * len(tensors))(*[t.size for t in tensors])
-        _check(lib().mods_net_create(device, NET_KINDS[kind], ptrs, sizes, len(tensors), C.byref(self.h)))
+        _check(lib().mods_net_create_ex(device, NET_KINDS[kind], ptrs, sizes, len(tensors), NET_PRECISIONS[precision], C.byref(self.h)))
 
     def forward(self, patches, quantise=True):
         """patches [n][32][32] (values 0..255) -> float32 [n][dim]; quantise: round to 8 bits first, as the wire to a daemon does."""
@@ -309,6 +314,12 @@ class Net:
     def forward_dev(self, stream, patches_ptr, n, out_ptr, quantise=True):
         """device pointers ([n][32][32] fp32 in, [n][dim] fp32 out) on hipStream_t `stream` (an integer address); does not wait"""
         _check(lib().mods_net_forward_dev(self.h, C.c_void_p(stream), C.c_void_p(patches_ptr), n, 1 if quantise else 0, C.c_void_p(out_ptr)))
+
+    def stage_times(self, stream, patches_ptr, n, out_ptr, quantise=True):
+        """forward_dev with device events between the launches (mods_test_net_stage_times); waits; milliseconds of stages 0..7"""
+        ms = np.zeros(8, np.float32)
+        _check(lib().mods_test_net_stage_times(self.h, C.c_void_p(stream), C.c_void_p(patches_ptr), n, 1 if quantise else 0, C.c_void_p(out_ptr), _fp(ms)))
+        return ms
 
     def stage_shapes(self, stage):
         """per-patch shapes (input, output) of stage 0 (normalisation), 1..6 (convolution blocks), 7 (head)"""

@@ -123,6 +123,9 @@ struct Config {
   int aff_ps = 32, ori_ps = 32;
   // weights=FILE.npz in [AffNet] / [OriNet] / [zmqDescriptor]: the network runs in-process (mods_net_*), no daemon, no port
   std::string aff_weights, ori_weights, zmq_weights;
+  // precision = fp32 | bf16 beside weights=: MODS_NET_FP32 / MODS_NET_BF16; *_named: the key is in the file (verbose then names the mode)
+  int aff_prec = MODS_NET_FP32, ori_prec = MODS_NET_FP32, zmq_prec = MODS_NET_FP32;
+  bool aff_prec_named = false, ori_prec_named = false, zmq_prec_named = false;
   // [ImageOutput] (io_mods.cpp:647-652).  writeImages absent means 0 here (the reference: 1): a configuration without the section
   // runs as it always did; the other keys keep the reference's defaults
   int write_images = 0, draw_only_centers = 1, draw_reprojected = 1, draw_epipolar = 0, draw_regions = 0;
@@ -381,6 +384,21 @@ int read_config(const std::string &config_fn, const std::string &iters_fn, int v
   cfg->aff_weights = ini.GetString("AffNet", "weights", "");
   cfg->ori_weights = ini.GetString("OriNet", "weights", "");
   cfg->zmq_weights = ini.GetString("zmqDescriptor", "weights", "");
+  // precision of an in-process network; any value but fp32 / bf16 ends the run here, before an image is opened
+  auto read_precision = [&](const char *sec, const std::string &weights, int *prec, bool *named) {
+    if (!ini.Has(sec, "precision")) return true;
+    std::string v = ini.GetString(sec, "precision", "fp32");
+    while (!v.empty() && (isspace((unsigned char)v.back()) || v.back() == ';')) v.pop_back();
+    if (v == "fp32") *prec = MODS_NET_FP32;
+    else if (v == "bf16") *prec = MODS_NET_BF16;
+    else { std::cerr << "mods: [" << sec << "] precision = " << v << ": fp32 or bf16 expected" << std::endl; return false; }
+    *named = true;
+    if (weights.empty()) std::cerr << "Note: [" << sec << "] precision has no effect without weights= (it is the arithmetic of the in-process network)" << std::endl;
+    return true;
+  };
+  if (!read_precision("AffNet", cfg->aff_weights, &cfg->aff_prec, &cfg->aff_prec_named) ||
+      !read_precision("OriNet", cfg->ori_weights, &cfg->ori_prec, &cfg->ori_prec_named) ||
+      !read_precision("zmqDescriptor", cfg->zmq_weights, &cfg->zmq_prec, &cfg->zmq_prec_named)) return 1;
   // iterations file :457-492
   cfg->max_steps = (int)it.GetInteger("Iterations", "Steps", 4);
   cfg->min_matches = (int)it.GetInteger("Iterations", "minMatches", 15);
@@ -648,7 +666,7 @@ bool write_regions_npz(const std::string &fn, const std::vector<mods_imgrep *> &
 
 // A built-in network from the arrays `<prefix>.features.N.*` of a weights file written with np.savez (the names of the daemon's
 // --weights FILE.npz), in network order; every missing or misshapen array is an error that names it
-mods_net *load_net(int device, int kind, const std::string &prefix, std::string fn) {
+mods_net *load_net(int device, int kind, int precision, const std::string &prefix, std::string fn) {
   while (!fn.empty() && (isspace((unsigned char)fn.back()) || fn.back() == ';')) fn.pop_back();
   static std::map<std::string, std::map<std::string, modscli::NpyArray>> files;      // one file usually serves all three sections
   if (!files.count(fn)) {
@@ -679,7 +697,7 @@ mods_net *load_net(int device, int kind, const std::string &prefix, std::string 
   }
   if (!missing.empty()) { std::cerr << "mods: " << fn << " has no arrays " << missing << std::endl; return nullptr; }
   mods_net *net = nullptr;
-  if (mods_net_create(device, kind, ptr.data(), cnt.data(), (int)ptr.size(), &net)) {
+  if (mods_net_create_ex(device, kind, ptr.data(), cnt.data(), (int)ptr.size(), precision, &net)) {
     std::cerr << "mods: " << fn << " (" << prefix << ".*): " << mods_last_error() << std::endl;
     return nullptr;
   }
@@ -1000,14 +1018,17 @@ int main(int argc, char **argv) {
   for (const mods_ladder_step &st : cfg.steps) if (st.n_tilts >= 0 && st.fginn_ratio > 0) { first_ratio = st.fginn_ratio; break; }
   // a section with weights= serves its slot in-process: 32 x 32 patches only, rounded to 8 bits as over the wire
   mods_net *net_desc = nullptr, *net_aff = nullptr, *net_ori = nullptr;
-  auto builtin = [&](const char *section, const std::string &weights, int ps, int kind, const char *name, const char *prefix, mods_net **net) {
+  auto builtin = [&](const char *section, const std::string &weights, int ps, int kind, const char *name, const char *prefix, int prec, bool prec_named,
+                     mods_net **net) {
     if (ps != 32) { std::cerr << "mods: [" << section << "] weights= runs the network in-process on 32x32 patches; patchSize=" << ps << " is not supported" << std::endl; return false; }
-    if (cfg.verbose) std::cerr << "[" << section << "]: " << name << " in-process, weights from " << weights << std::endl;
-    *net = load_net(device, kind, prefix, weights);
+    if (cfg.verbose)
+      std::cerr << "[" << section << "]: " << name << " in-process" << (prec_named ? (prec == MODS_NET_BF16 ? " (precision bf16)" : " (precision fp32)") : "")
+                << ", weights from " << weights << std::endl;
+    *net = load_net(device, kind, prec, prefix, weights);
     return *net != nullptr;
   };
   if (cfg.use_zmq && !cfg.zmq_weights.empty()) {
-    if (!builtin("zmqDescriptor", cfg.zmq_weights, cfg.zmq_ps, MODS_NET_HARDNET, "HardNet", "hardnet", &net_desc)) return 1;
+    if (!builtin("zmqDescriptor", cfg.zmq_weights, cfg.zmq_ps, MODS_NET_HARDNET, "HardNet", "hardnet", cfg.zmq_prec, cfg.zmq_prec_named, &net_desc)) return 1;
     if (mods_ctx_set_builtin_descriptor(ctx, net_desc, cfg.zmq_mr, 1)) return fail("built-in descriptor");
   } else if (cfg.use_zmq) {
     while (!cfg.zmq_port.empty() && isspace((unsigned char)cfg.zmq_port.back())) cfg.zmq_port.pop_back();
@@ -1017,7 +1038,7 @@ int main(int argc, char **argv) {
   auto rtrim = [](std::string &t) { while (!t.empty() && isspace((unsigned char)t.back())) t.pop_back(); };
   if (cfg.aff_zmq && cfg.pair.det.doBaumberg) std::cerr << "Warning: [AffineAdaptation] useZMQ=1 with doBaumberg=1 in [HessianAffine]: the Baumberg frames are replaced" << std::endl;
   if (cfg.aff_zmq && !cfg.aff_weights.empty()) {
-    if (!builtin("AffNet", cfg.aff_weights, cfg.aff_ps, MODS_NET_AFFNET, "AffNet", "affnet", &net_aff)) return 1;
+    if (!builtin("AffNet", cfg.aff_weights, cfg.aff_ps, MODS_NET_AFFNET, "AffNet", "affnet", cfg.aff_prec, cfg.aff_prec_named, &net_aff)) return 1;
     if (mods_ctx_set_builtin_shape(ctx, net_aff, cfg.aff_mr, 1)) return fail("built-in shape");
   } else if (cfg.aff_zmq) {
     rtrim(cfg.aff_port);
@@ -1025,7 +1046,7 @@ int main(int argc, char **argv) {
     if (mods_ctx_set_external_shape(ctx, &mods_zmq_descriptor_hook, (void *)cfg.aff_port.c_str(), cfg.aff_mr, cfg.aff_ps)) return fail("external shape");
   }
   if (cfg.ori_zmq && !cfg.ori_weights.empty()) {
-    if (!builtin("OriNet", cfg.ori_weights, cfg.ori_ps, MODS_NET_ORINET, "OriNet", "orinet", &net_ori)) return 1;
+    if (!builtin("OriNet", cfg.ori_weights, cfg.ori_ps, MODS_NET_ORINET, "OriNet", "orinet", cfg.ori_prec, cfg.ori_prec_named, &net_ori)) return 1;
     if (mods_ctx_set_builtin_orientation(ctx, net_ori, cfg.ori_mr, 1)) return fail("built-in orientation");
   } else if (cfg.ori_zmq) {
     rtrim(cfg.ori_port);

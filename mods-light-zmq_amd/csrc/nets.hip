@@ -16,7 +16,16 @@
 // LDS feeds 16 output channels held in registers.
 // Every sum runs in an order fixed by the architecture alone (input channel, then tap; fixed trees across lanes), and no patch's
 // arithmetic touches another patch's data: a patch's output does not depend on the call's size, order or chunking.
+//
+// That is the fp32 mode (MODS_NET_FP32, the default).  A network created with MODS_NET_BF16 keeps this file's normalisation and
+// its host code (creation, scratch, chunking, the test hook) and runs everything behind the normalisation through the kernels of
+// nets_mfma.hip: stages 2..6 (the convolution blocks behind the first; stage = block index l + 1, as in mods_test_net_stage)
+// and HardNet's head on the matrix cores with bf16 operands and fp32 accumulators (which do have a rate advantage: 16 x the
+// fp32 vector rate), stage 1 and the small heads with this file's arithmetic, activations bf16 channels
+// last in half the scratch.  The contract of that mode is in include/mods_hip.h; the matrix-core kernels own their SIMDs
+// (match.hip), which is what keeps the fp64 RANSAC kernels safe beside them.
 #include "common.hpp"
+#include "nets_mfma.hpp"
 #include <algorithm>
 #include <cmath>
 #include <mutex>
@@ -29,13 +38,18 @@ constexpr int kPP = 32 * 32;          // pixels of a patch
 constexpr int kChunk = 512;           // patches per set of launches (what the scratch buffers hold)
 constexpr int kCoutT = 16;            // output channels a thread of the convolution holds
 
-struct NetScratch { float *a = nullptr, *b = nullptr; hipEvent_t done = nullptr; };
+// fp32 mode: a | b, the two activation buffers.  bf16 mode: a = the normalised patches (fp32), h0 | h1 the bf16 activations
+struct NetScratch { float *a = nullptr, *b = nullptr; mods::bf16_t *h0 = nullptr, *h1 = nullptr; hipEvent_t done = nullptr; };
 
 }  // namespace
 
 struct mods_net {
-  int device = 0, kind = 0, C = 16, dim = 0;
+  int device = 0, kind = 0, C = 16, dim = 0, precision = MODS_NET_FP32;
   float *params = nullptr;                       // every folded tensor, one allocation
+  // bf16 mode: the folded weights of stages 2..6 (l = 1..5) rounded to bf16, cout x mfma_conv_kp(cin) with k = tap * cin + input channel,
+  // and HardNet's head 128 x 8192 with k = pixel * 128 + channel, both in fragment order (mods::mfma_w_index) (params then holds stage 1, the biases and the small heads)
+  mods::bf16_t *params16 = nullptr;
+  size_t w16_off[6] = {0}, head_w16 = 0;
   size_t w_off[6] = {0}, b_off[6] = {0};         // per block: weights [cout / 16][cin][9][16], bias [cout]
   size_t head_w = 0, head_b = 0;
   // scratch of calls in flight: a call takes a pair of buffers (or makes one), and hands it back with an event that the next
@@ -286,6 +300,20 @@ void launch_head(const mods_net *net, hipStream_t s, const float *in, float *out
   else hipLaunchKernelGGL(net_head_hard_kernel, dim3((n + kHeadP - 1) / kHeadP), dim3(256), 0, s, in, w, b, out, n);
 }
 
+// the blocks (l = stage - 1) and the head of a bf16 network (nets_mfma.hip); l = 0 reads the fp32 normalised patches
+hipError_t launch_block16(const mods_net *net, hipStream_t s, int l, const void *in, mods::bf16_t *out, int n) {
+  const float *b = net->params + net->b_off[l];
+  if (l == 0) return mods::mfma_launch_conv1(s, net->device, net->C, (const float *)in, out, net->params + net->w_off[0], b, n);
+  return mods::mfma_launch_conv3(s, net->device, net->C, l, (const mods::bf16_t *)in, out, net->params16 + net->w16_off[l], b, n);
+}
+
+hipError_t launch_head16(const mods_net *net, hipStream_t s, const mods::bf16_t *in, float *out, int n) {
+  const float *w = net->params + net->head_w, *b = net->params + net->head_b;
+  if (net->kind == MODS_NET_AFFNET) return mods::mfma_launch_head_aff(s, in, w, b, out, n);
+  if (net->kind == MODS_NET_ORINET) return mods::mfma_launch_head_ori(s, in, w, b, out, n);
+  return mods::mfma_launch_head_hard(s, in, net->params16 + net->head_w16, b, out, n);
+}
+
 // floats of one patch at the input (out = false) or the output of stage 0 (normalisation), 1..6 (blocks), 7 (head)
 size_t stage_elems(const mods_net *net, int stage, bool out) {
   const int C = net->C;
@@ -315,8 +343,14 @@ int scratch_take(mods_net *net, hipStream_t s, NetScratch *out) {
   }
   if (out->a) { MODS_HIP_CHECK(hipStreamWaitEvent(s, out->done, 0)); return MODS_OK; }
   const size_t elems = (size_t)kChunk * net->C * kPP;       // the widest activation: C x 32 x 32 per patch
-  MODS_HIP_CHECK(hipMalloc(&out->a, 2 * elems * sizeof(float)));
-  out->b = out->a + elems;
+  if (net->precision == MODS_NET_BF16) {
+    MODS_HIP_CHECK(hipMalloc(&out->a, (size_t)kChunk * kPP * sizeof(float) + 2 * elems * sizeof(mods::bf16_t)));
+    out->h0 = (mods::bf16_t *)(out->a + (size_t)kChunk * kPP);
+    out->h1 = out->h0 + elems;
+  } else {
+    MODS_HIP_CHECK(hipMalloc(&out->a, 2 * elems * sizeof(float)));
+    out->b = out->a + elems;
+  }
   MODS_HIP_CHECK(hipEventCreateWithFlags(&out->done, hipEventDisableTiming));
   return MODS_OK;
 }
@@ -326,9 +360,17 @@ int scratch_take(mods_net *net, hipStream_t s, NetScratch *out) {
 extern "C" {
 
 int mods_net_create(int device, int kind, const float *const *tensors, const size_t *n_floats, int n_tensors, mods_net **out) {
+  return mods_net_create_ex(device, kind, tensors, n_floats, n_tensors, MODS_NET_FP32, out);
+}
+
+int mods_net_create_ex(int device, int kind, const float *const *tensors, const size_t *n_floats, int n_tensors, int precision, mods_net **out) {
   if (!out) { set_error("net_create: null output"); return MODS_E_ARG; }
   *out = nullptr;
   if (kind != MODS_NET_AFFNET && kind != MODS_NET_ORINET && kind != MODS_NET_HARDNET) { set_error("net_create: unknown kind %d", kind); return MODS_E_ARG; }
+  if (precision != MODS_NET_FP32 && precision != MODS_NET_BF16) {
+    set_error("net_create: unknown precision %d (MODS_NET_FP32 = %d, MODS_NET_BF16 = %d)", precision, MODS_NET_FP32, MODS_NET_BF16);
+    return MODS_E_ARG;
+  }
   const std::vector<size_t> want = net_tensor_sizes(kind);
   if (!tensors || !n_floats || n_tensors != (int)want.size()) {
     set_error("net_create: %s takes %d tensors, %d given", net_name(kind), (int)want.size(), n_tensors);
@@ -347,23 +389,41 @@ int mods_net_create(int device, int kind, const float *const *tensors, const siz
   }
   const int C = kind == MODS_NET_HARDNET ? 32 : 16;
   const int cin[6] = {1, C, C, 2 * C, 2 * C, 4 * C}, cout[6] = {C, C, 2 * C, 2 * C, 4 * C, 4 * C};
+  const bool bf = precision == MODS_NET_BF16;
   std::vector<float> host;
+  std::vector<mods::bf16_t> host16;
   mods_net *net = new mods_net;
-  net->device = device; net->kind = kind; net->C = C; net->dim = kind == MODS_NET_AFFNET ? 3 : kind == MODS_NET_ORINET ? 2 : 128;
+  net->device = device; net->kind = kind; net->precision = precision; net->C = C; net->dim = kind == MODS_NET_AFFNET ? 3 : kind == MODS_NET_ORINET ? 2 : 128;
   auto reserve = [&](size_t n) { const size_t o = (host.size() + 15) & ~(size_t)15; host.resize(o + n, 0.f); return o; };   // 64-byte aligned
+  auto reserve16 = [&](size_t n) { const size_t o = (host16.size() + 31) & ~(size_t)31; host16.resize(o + n, 0); return o; };
   for (int l = 0; l < 6; l++) {
     const float *W = tensors[3 * l], *mean = tensors[3 * l + 1], *var = tensors[3 * l + 2];
-    const size_t wo = reserve((size_t)cout[l] * cin[l] * 9), bo = reserve(cout[l]);
-    net->w_off[l] = wo; net->b_off[l] = bo;
+    const bool w16 = bf && l >= 1;                            // bf16 mode, stages 2..6: the folded weight rounded once more
+    const int kp = mods::mfma_conv_kp(cin[l]);
+    const size_t wo = w16 ? reserve16((size_t)cout[l] * kp) : reserve((size_t)cout[l] * cin[l] * 9), bo = reserve(cout[l]);
+    (w16 ? net->w16_off[l] : net->w_off[l]) = wo; net->b_off[l] = bo;
     for (int co = 0; co < cout[l]; co++) {
       const double inv = 1.0 / sqrt((double)var[co] + 1e-5);
       host[bo + co] = (float)(-(double)mean[co] * inv);
       for (int ci = 0; ci < cin[l]; ci++)
-        for (int k = 0; k < 9; k++)
-          host[wo + (((size_t)(co / kCoutT) * cin[l] + ci) * 9 + k) * kCoutT + co % kCoutT] = (float)((double)W[((size_t)co * cin[l] + ci) * 9 + k] * inv);
+        for (int k = 0; k < 9; k++) {
+          const float wf = (float)((double)W[((size_t)co * cin[l] + ci) * 9 + k] * inv);
+          if (w16) host16[wo + mods::mfma_w_index(co, k * cin[l] + ci, kp / 32)] = mods::bf16_round_host(wf);
+          else host[wo + (((size_t)(co / kCoutT) * cin[l] + ci) * 9 + k) * kCoutT + co % kCoutT] = wf;
+        }
     }
   }
-  if (kind == MODS_NET_HARDNET) {
+  if (kind == MODS_NET_HARDNET && bf) {
+    const float *W = tensors[18], *mean = tensors[19], *var = tensors[20];
+    net->head_w16 = reserve16((size_t)128 * 8192); net->head_b = reserve(128);
+    for (int co = 0; co < 128; co++) {
+      const double inv = 1.0 / sqrt((double)var[co] + 1e-5);
+      host[net->head_b + co] = (float)(-(double)mean[co] * inv);
+      for (int c = 0; c < 128; c++)
+        for (int px = 0; px < 64; px++)
+          host16[net->head_w16 + mods::mfma_w_index(co, px * 128 + c, 8192 / 32)] = mods::bf16_round_host((float)((double)W[(size_t)co * 8192 + c * 64 + px] * inv));
+    }
+  } else if (kind == MODS_NET_HARDNET) {
     const float *W = tensors[18], *mean = tensors[19], *var = tensors[20];
     net->head_w = reserve((size_t)8192 * 128); net->head_b = reserve(128);
     for (int co = 0; co < 128; co++) {
@@ -381,10 +441,13 @@ int mods_net_create(int device, int kind, const float *const *tensors, const siz
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipMalloc(&net->params, host.size() * sizeof(float));
   if (e == hipSuccess) e = mods::copy_wait(mods::thread_stream(device), net->params, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess && bf) e = hipMalloc(&net->params16, host16.size() * sizeof(mods::bf16_t));
+  if (e == hipSuccess && bf) e = mods::copy_wait(mods::thread_stream(device), net->params16, host16.data(), host16.size() * sizeof(mods::bf16_t), hipMemcpyHostToDevice);
   (void)hipSetDevice(prev);
   if (e != hipSuccess) {
     set_error("net_create: %s", hipGetErrorString(e));
     if (net->params) (void)hipFree(net->params);
+    if (net->params16) (void)hipFree(net->params16);
     delete net;
     return MODS_E_HIP;
   }
@@ -399,28 +462,49 @@ void mods_net_destroy(mods_net *net) {
   (void)hipSetDevice(net->device);
   for (NetScratch &s : net->idle) { (void)hipEventSynchronize(s.done); (void)hipEventDestroy(s.done); (void)hipFree(s.a); }
   (void)hipFree(net->params);
+  if (net->params16) (void)hipFree(net->params16);
   (void)hipSetDevice(prev);
   delete net;
 }
 
 int mods_net_dim(const mods_net *net) { return net ? net->dim : 0; }
+int mods_net_precision(const mods_net *net) { return net ? net->precision : MODS_NET_FP32; }
 int mods_net_chunk(void) { return kChunk; }
 
-int mods_net_forward_dev(mods_net *net, void *hip_stream, const float *patches_dev, int n, int quantise_u8, float *out_dev) {
-  if (!net || n < 0 || (n > 0 && (!patches_dev || !out_dev))) { set_error("net_forward: null argument"); return MODS_E_ARG; }
-  if (n == 0) return MODS_OK;
-  MODS_HIP_CHECK(hipSetDevice(net->device));
-  hipStream_t s = (hipStream_t)hip_stream;
+// the launches of one call; `marks` (the timing hook): an event in front of every stage of every chunk and one behind the last
+static int forward_launches(mods_net *net, hipStream_t s, const float *patches_dev, int n, int quantise_u8, float *out_dev, std::vector<hipEvent_t> *marks) {
   NetScratch sc;
   int rc = scratch_take(net, s, &sc);
   if (rc) { if (sc.a) (void)hipFree(sc.a); return rc; }
+  // the first host-side failure of the call: a kernel's LDS attribute could not be set (bf16 mode), or an event of the timing hook
+  // could not be made or recorded.  After one, the remaining bf16 launches and marks are skipped and the call reports it.
+  hipError_t e_host = hipSuccess;
+  auto mark = [&]() {
+    if (!marks || e_host != hipSuccess) return;
+    hipEvent_t ev = nullptr;
+    e_host = hipEventCreate(&ev);
+    if (e_host == hipSuccess) { marks->push_back(ev); e_host = hipEventRecord(ev, s); }
+  };
   for (int i0 = 0; i0 < n; i0 += kChunk) {
     const int m = std::min(kChunk, n - i0);
+    if (net->precision == MODS_NET_BF16) {
+      mark();
+      launch_norm(s, patches_dev + (size_t)i0 * kPP, sc.a, m, quantise_u8);
+      mark();
+      if (e_host == hipSuccess) e_host = launch_block16(net, s, 0, sc.a, sc.h0, m);
+      for (int l = 1; l < 6 && e_host == hipSuccess; l++) { mark(); e_host = launch_block16(net, s, l, l % 2 ? sc.h0 : sc.h1, l % 2 ? sc.h1 : sc.h0, m); }
+      mark();
+      if (e_host == hipSuccess) e_host = launch_head16(net, s, sc.h1, out_dev + (size_t)i0 * net->dim, m);
+      continue;
+    }
+    mark();
     launch_norm(s, patches_dev + (size_t)i0 * kPP, sc.b, m, quantise_u8);
-    for (int l = 0; l < 6; l++) launch_block(net, s, l, l % 2 ? sc.a : sc.b, l % 2 ? sc.b : sc.a, m);
+    for (int l = 0; l < 6; l++) { mark(); launch_block(net, s, l, l % 2 ? sc.a : sc.b, l % 2 ? sc.b : sc.a, m); }
+    mark();
     launch_head(net, s, sc.b, out_dev + (size_t)i0 * net->dim, m);
   }
-  const hipError_t e_launch = hipGetLastError();
+  mark();
+  const hipError_t e_launch = e_host != hipSuccess ? e_host : hipGetLastError();
   const hipError_t e_rec = hipEventRecord(sc.done, s);
   {
     std::lock_guard<std::mutex> g(net->mu);
@@ -428,6 +512,39 @@ int mods_net_forward_dev(mods_net *net, void *hip_stream, const float *patches_d
   }
   MODS_HIP_CHECK(e_launch);
   MODS_HIP_CHECK(e_rec);
+  return MODS_OK;
+}
+
+int mods_net_forward_dev(mods_net *net, void *hip_stream, const float *patches_dev, int n, int quantise_u8, float *out_dev) {
+  if (!net || n < 0 || (n > 0 && (!patches_dev || !out_dev))) { set_error("net_forward: null argument"); return MODS_E_ARG; }
+  if (n == 0) return MODS_OK;
+  MODS_HIP_CHECK(hipSetDevice(net->device));
+  return forward_launches(net, (hipStream_t)hip_stream, patches_dev, n, quantise_u8, out_dev, nullptr);
+}
+
+int mods_test_net_stage_times(mods_net *net, void *hip_stream, const float *patches_dev, int n, int quantise_u8, float *out_dev, float *stage_ms) {
+  if (!net || n < 1 || !patches_dev || !out_dev || !stage_ms) { set_error("net_stage_times: bad argument"); return MODS_E_ARG; }
+  MODS_HIP_CHECK(hipSetDevice(net->device));
+  hipStream_t s = (hipStream_t)hip_stream;
+  std::vector<hipEvent_t> marks;
+  int rc = forward_launches(net, s, patches_dev, n, quantise_u8, out_dev, &marks);
+  hipError_t e = hipStreamSynchronize(s);
+  for (int i = 0; i < 8; i++) stage_ms[i] = 0.f;
+  const size_t chunks = ((size_t)n + kChunk - 1) / kChunk;
+  if (rc == MODS_OK && e == hipSuccess && marks.size() == 8 * chunks + 1) {
+    // events 8 c .. 8 c + 7 stand in front of the stages of chunk c; the event behind a chunk's head is the next chunk's first
+    for (size_t i = 0; i + 1 < marks.size() && e == hipSuccess; i++) {
+      float ms = 0.f;
+      e = hipEventElapsedTime(&ms, marks[i], marks[i + 1]);
+      stage_ms[i % 8] += ms;
+    }
+  } else if (rc == MODS_OK && e == hipSuccess) {
+    set_error("net_stage_times: %zu events for %zu chunks", marks.size(), chunks);
+    rc = MODS_E_HIP;
+  }
+  for (hipEvent_t ev : marks) (void)hipEventDestroy(ev);
+  if (rc) return rc;
+  MODS_HIP_CHECK(e);
   return MODS_OK;
 }
 
@@ -454,6 +571,46 @@ int mods_test_net_stage(mods_net *net, int stage, const float *in_host, int n, i
   MODS_HIP_CHECK(hipSetDevice(net->device));
   hipStream_t s = mods::thread_stream(net->device);
   const size_t in_elems = n * stage_elems(net, stage, false), per_out = stage_elems(net, stage, true), out_elems = (n + 1) * per_out;
+  if (net->precision == MODS_NET_BF16 && stage >= 1) {
+    // bf16 mode: the activations between the stages are bf16, channels last.  The host's [n][c][h][w] floats are rounded and
+    // transposed on their way in (stages 2..7), the outputs of stages 1..6 widened and transposed back.
+    const bool in16 = stage >= 2, out16 = stage <= 6;
+    const size_t per_in = stage_elems(net, stage, false);
+    const int C = net->C;
+    const int ch[7] = {1, C, C, 2 * C, 2 * C, 4 * C, 4 * C};                    // channels of the maps between the stages
+    const size_t cin = ch[stage - 1], hw_in = per_in / cin, cout = out16 ? ch[stage] : 1, hw_out = per_out / cout;
+    mods::Buf<float> in_dev, out_dev;                                          // (bf16 data takes half of the words)
+    MODS_HIP_CHECK(mods::reserve_group(in_dev, in_elems, out_dev, out_elems));
+    if (in16) {
+      std::vector<mods::bf16_t> h(in_elems);
+      for (int p = 0; p < n; p++)
+        for (size_t c = 0; c < cin; c++)
+          for (size_t i = 0; i < hw_in; i++) h[(p * hw_in + i) * cin + c] = mods::bf16_round_host(in_host[(p * cin + c) * hw_in + i]);
+      MODS_HIP_CHECK(mods::copy_wait(s, in_dev, h.data(), in_elems * sizeof(mods::bf16_t), hipMemcpyHostToDevice));
+    } else {
+      MODS_HIP_CHECK(mods::copy_wait(s, in_dev, in_host, in_elems * sizeof(float), hipMemcpyHostToDevice));
+    }
+    const size_t out_bytes = out_elems * (out16 ? sizeof(mods::bf16_t) : sizeof(float));
+    MODS_HIP_CHECK(mods::fill_wait(s, out_dev, 0xA5, out_bytes));
+    if (out16) MODS_HIP_CHECK(launch_block16(net, s, stage - 1, (const float *)in_dev, (mods::bf16_t *)(float *)out_dev, n));
+    else MODS_HIP_CHECK(launch_head16(net, s, (const mods::bf16_t *)(const float *)in_dev, out_dev, n));
+    MODS_HIP_CHECK(hipGetLastError());
+    std::vector<unsigned char> host(out_bytes);
+    MODS_HIP_CHECK(mods::copy_wait(s, host.data(), out_dev, out_bytes, hipMemcpyDeviceToHost));
+    if (out16) {
+      const mods::bf16_t *h = (const mods::bf16_t *)host.data();
+      for (int p = 0; p < n; p++)
+        for (size_t c = 0; c < cout; c++)
+          for (size_t i = 0; i < hw_out; i++) out_host[(p * cout + c) * hw_out + i] = mods::bf16_widen_host(h[(p * hw_out + i) * cout + c]);
+    } else {
+      memcpy(out_host, host.data(), n * per_out * sizeof(float));
+    }
+    int ok = 1;
+    for (size_t i = n * per_out * (out16 ? sizeof(mods::bf16_t) : sizeof(float)); i < out_bytes; i++)
+      if (host[i] != 0xA5) ok = 0;
+    *guard_ok = ok;
+    return MODS_OK;
+  }
   mods::Buf<float> in_dev, out_dev;
   MODS_HIP_CHECK(mods::reserve_group(in_dev, in_elems, out_dev, out_elems));
   MODS_HIP_CHECK(mods::copy_wait(s, in_dev, in_host, in_elems * sizeof(float), hipMemcpyHostToDevice));

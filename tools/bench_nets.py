@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Timing of the in-process networks (csrc/nets.hip) on the MI355X; writes profiles/nets_timing.txt.
 
-    python tools/bench_nets.py [--out FILE]
+    python tools/bench_nets.py [--out FILE] [--precision fp32|bf16]
+
+--precision: the arithmetic of the built-in networks (pkg.Net(..., precision=...)); the comparison of the two modes with each
+other is tools/bench_nets_bf16.py.
 
 Three steps, each a process of its own under a time limit; the script stops at the first step that fails:
   kernels  per network and n in {512, 6000}: mods_net_forward_dev between device events (warm, median of 20), beside the same
@@ -29,6 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "mods-light-zmq_amd"))
 KINDS = ("affnet", "orinet", "hardnet")
 MR = 3.0 * np.sqrt(3.0)
 PEAK_FP32 = 157.3e12
+PRECISION = "fp32"      # --precision
 
 
 def macs(kind):
@@ -59,7 +63,7 @@ def step_kernels():
     print("# kernels: time of one call for n patches, median of 20 warm calls between device events; FLOP/s against %.1f TF fp32" % (PEAK_FP32 / 1e12))
     print("# %-8s %6s %12s %10s %8s %14s %10s" % ("network", "n", "built-in ms", "TFLOP/s", "of peak", "PyTorch ms", "TFLOP/s"))
     for kind in KINDS:
-        net = pkg.Net(kind, st[kind])
+        net = pkg.Net(kind, st[kind], precision=PRECISION)
         model = zd.build_model(kind, st[kind], 0, "cuda")
         model.warm_up()
         module = tg._module_of(model)
@@ -113,7 +117,7 @@ def step_e2e():
     det.doBaumberg = 0
     ctx = pkg.Context(0, w, h, 1)
     keys = ctx.detect_hessian_affine(img, det)
-    nets = {k: pkg.Net(k, st[k]) for k in KINDS}
+    nets = {k: pkg.Net(k, st[k], precision=PRECISION) for k in KINDS}
 
     def timed(reps=7):
         r = ctx.orient_describe(img, keys)         # warm
@@ -195,7 +199,7 @@ def step_ladder():
     par.det.doBaumberg = 0
     t = torch.from_numpy(np.stack([a, b])).cuda()
     torch.cuda.synchronize()
-    nets = {k: pkg.Net(k, st[k]) for k in KINDS}
+    nets = {k: pkg.Net(k, st[k], precision=PRECISION) for k in KINDS}
     ctx = pkg.Context(0, d[0], d[1], 2)
     ctx.set_builtin_shape(nets["affnet"], MR, True)
     ctx.set_builtin_orientation(nets["orinet"], MR, True)
@@ -215,21 +219,26 @@ def step_ladder():
 
 
 def main():
+    global PRECISION
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nets_timing.txt"))
+    ap.add_argument("--precision", default=PRECISION, choices=["fp32", "bf16"], help="arithmetic of the built-in networks")
     ap.add_argument("--step", default=None, help="run one step in this process (what the driver does for each of them)")
     args = ap.parse_args()
+    PRECISION = args.precision
     if args.step:
         {"kernels": step_kernels, "e2e": step_e2e, "ladder": step_ladder}[args.step]()
         return 0
     plan = [("kernels", {}, 300), ("e2e", {}, 300),
             ("ladder", {"MODS_LADDER_WORKERS": "1"}, 200), ("ladder", {}, 200)]
     lines = ["# tools/bench_nets.py - AffNet / OriNet / HardNet in-process (csrc/nets.hip) on the MI355X"]
+    if args.precision != "fp32":
+        lines.append("# built-in networks in %s mode (csrc/nets_mfma.hip)" % args.precision)
     rc = 0
     for step, env, limit in plan:
         if step == "ladder" and env:
             lines.append("# ladder: two-step HessianAffine ladder of a 480x360 pair, three built-in networks, wall time of mods_match_ladder_dev")
-        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step],
+        p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--step", step, "--precision", args.precision],
                            env=dict(os.environ, **env), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         lines += p.stdout.decode().rstrip().splitlines()
         if p.returncode:
